@@ -6,7 +6,15 @@ complex-float forward FFTs — configs[1] ("N=1024 complex float fwd+inv, batch=
 A "step" is one pass of the hot path (pffft_transform semantics, internal-layout spectrum) over the
 whole device-resident batch = ONE kernel launch through the C ABI (pffft_hip_transform_batch).
 
-    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5] [--scaling weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5] [--scaling weak|strong] [--full] [--dump-outputs DIR]
+
+A plain run sets up, runs W untimed + K timed steps of the config, writes the last step's output when --dump-outputs is given
+and prints its line.  `--full` adds everything else this file measures or checks: the in-run parity check against the real
+reference, the side rates and the other BASELINE configs, the batch sweep, the sizes table and the CPU baselines.
+`--dump-outputs DIR` writes what the timed path returned in its last step as DIR/<name>.npy (float32 / float64, rows drawn
+by a fixed seed when the whole would exceed 32 MiB): `spectrum.npy` for the FFT configs (rank 0's shard; the first part
+with --single-process), `fir_output.npy` for c4.  The inputs are the same from run to run, so two builds can be compared
+output for output.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment re-executes itself under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`, one rank per GPU
@@ -21,15 +29,15 @@ combines the final number (all_reduce MAX of elapsed, SUM of transforms), bracke
 
 Prints ONE JSON line on rank 0.  `value` = whole-job throughput with inputs resident in HBM.
 `roofline` prices the dominant kernel's ALGORITHMIC bytes (2 x vector bytes per transform,
-8 B per FIR output sample) against 8 TB/s.  `cpu_baseline` times the real reference (oracle/_ref) on the
+8 B per FIR output sample) against 8 TB/s.  `cpu_baseline` (--full) times the real reference (oracle/_ref) on the
 host cores of this box on a bounded sample of the same workload (test infrastructure, never the product).
-At N = 1 the default line also carries `configs`: every other BASELINE config at its stated size, each with
+At N = 1 the `--full` line also carries `configs`: every other BASELINE config at its stated size, each with
 its own `roofline` and `cpu_baseline` (no warm-up beyond --warmup; the first launches of each are reported as
 `first_launches_ms` next to the timed region), and `sizes`: the reference's benchmark table
 (benchmarks/bench_pffft.c:445,547-550,1140-1150: every size of its lists, real and complex, float and double, ordered and
 unordered, forward and backward; plus eight legal sizes with factors 3 and 5 beyond LDS, which that list does not hold).  All GPU work runs back to back, the CPU baselines afterwards (an idle gap between
-configs lets the clocks drop and the next config starts cold).  At N > 1 the line carries the C5 sharded config, weak and
-strong, `ranks_seen` from the RCCL all-reduce and the fastest / slowest rank's ms_per_step.
+configs lets the clocks drop and the next config starts cold).  At N > 1 the `--full` line carries the C5 sharded config, weak
+and strong; every line at N > 1 carries `ranks_seen` from the RCCL all-reduce and the fastest / slowest rank's ms_per_step.
 Inputs are a counter hash of (seed, GLOBAL element index) (pffft_amd/sharding.py): a shard holds the same data whatever
 the number of ranks, and the in-run parity check rebuilds its sampled vectors on the host from their indices.
 """
@@ -261,6 +269,20 @@ def roofline(alg_bytes_per_launch, kernel_s, traffic_key=None):
     return out
 
 
+DUMP_BYTES = 32 << 20            # per array written by --dump-outputs (64 MB in all at most)
+
+
+def dump_rows(torch, y, path, seed=0):
+    """--dump-outputs: the rows of the 2-D result `y` [vectors, scalars] as a float32 / float64 .npy - all of them when they fit
+    in DUMP_BYTES, otherwise a fixed sample (numpy default_rng(seed), in ascending order), the same for every build."""
+    rows = y.shape[0]
+    keep = max(1, min(rows, DUMP_BYTES // (y.shape[1] * y.element_size())))
+    if keep < rows:
+        idx = np.sort(np.random.default_rng(seed).choice(rows, keep, replace=False))
+        y = y[torch.from_numpy(idx).to(y.device)]
+    np.save(path, y.cpu().numpy())
+
+
 def make_input(torch, dev, batch, vec_scalars, tdt, seed, first_vector=0):
     """Uniform [-1, 1): counter hash of (seed, GLOBAL element index), generated on the device (pffft_amd/sharding.py).
     `first_vector` = global index of this shard's first vector: the same vectors whatever the number of ranks."""
@@ -280,8 +302,9 @@ def sample_indices(batch, want=4096):
     return sorted({0, 1, batch // 2, batch - 2, batch - 1} & set(range(batch)) | set(range(3, batch, step)))
 
 
-def fft_config_run(torch, pa, dev, cfg, batch, first_vector, steps, warmup, in_place, dist, rank, seed):
-    """One FFT config on this rank's shard: W warm-up + K timed steps inside the barrier bracket.
+def fft_config_run(torch, pa, dev, cfg, batch, first_vector, steps, warmup, in_place, dist, rank, seed, check=True, dump=None):
+    """One FFT config on this rank's shard: W warm-up + K timed steps inside the barrier bracket.  `check`: the parity check
+    against the real reference afterwards; `dump`: path of the .npy that receives the last step's output (dump_rows).
     Returns (elapsed_s of this rank, kernel_s from HIP events, kernel name, parity, first launches in ms)."""
     from pffft_amd.sharding import global_uniform_np, timed_steps
     dt = _np_dtype(cfg["dtype"])
@@ -317,14 +340,16 @@ def fft_config_run(torch, pa, dev, cfg, batch, first_vector, steps, warmup, in_p
     elapsed = timed_steps(timed_step, steps, rest, dist, torch.cuda.synchronize)
     kernel_s = e0.elapsed_time(e1) * 1e-3 / steps
     first_ms = [round(a.elapsed_time(b), 4) for a, b in first]
+    if dump:
+        dump_rows(torch, y, dump)
     # parity against the real reference when it travelled, AFTER the timed region (host work before it would leave the GPU
     # idle and the timed region cold): >= 4096 sampled transforms whose inputs are rebuilt on the host from their GLOBAL
     # indices.  In place: the buffer is regenerated and transformed once more.  (tests/ are the gate.)
-    parity = None
+    parity = None if check else "unchecked: plain run (--full checks against the reference)"
     idx = sample_indices(batch)
     try:
         from oracle import ref as oref
-        if oref.available():
+        if check and oref.available():
             if in_place:
                 make_input_into(torch, x, seed, first_vector)
                 step()
@@ -519,11 +544,13 @@ def fir_flops_per_output(nfft, taps):
     return (5.0 * nfft * np.log2(nfft) + 3.0 * nfft + nfft) / (nfft - taps + 1)
 
 
-def fir_config(torch, pa, dev, timer, warmup):
+def fir_config(torch, pa, dev, timer, warmup, steps=40, full=True, dump=None):
     """BASELINE configs[3].  The single 2^20-sample call is latency-bound (255 blocks); the throughput regime is
     measured on (i) a batch of independent 2^20-sample signals through pffastconv_hip_apply_batch and (ii) one
     2^26-sample signal — `roofline` is (ii): 8 B per output sample (read x once, write y once), with a second leg
     `roofline_valu` that prices the same run against the measured VALU peak (at 4096 taps the arithmetic binds before HBM).
+    (ii) is timed over `steps` launches; the single call, its parity check and (i) run only when `full`.  `dump`: path of the
+    .npy that receives (ii)'s output (dump_rows over rows of 4096 samples).
     Returns (record, closure that adds the CPU baseline later)."""
     taps, L = FIR["taps"], 1 << FIR["signal_log2"]
     h = np.random.default_rng(4).uniform(-1, 1, taps).astype(np.float32)
@@ -531,22 +558,23 @@ def fir_config(torch, pa, dev, timer, warmup):
     fc = pa.FastConv(h, 0, 0)
     sig = make_input(torch, dev, 1, L, torch.float32, seed=4).reshape(-1)
     y = torch.empty_like(sig)
-    t = timer(lambda: fc.apply(sig, True, out=y), 200, warm=max(3, warmup))
     n_out = L - taps + 1
-    out["single_call_us"] = round(t * 1e6, 2)
-    out["single_call_Gsamples_per_s"] = round(n_out / t / 1e9, 2)
-    out["single_call_frac"] = round(8 * n_out / t / HBM_PEAK, 4)
-    # parity of the same call against the real reference (spot check; tests/ are the gate)
     x_host = sig.cpu().numpy()
-    try:
-        from oracle import ref as oref
-        if oref.available():
-            yw, nw, _ = oref.get().fastconv(x_host, h, 0, 0, 1)
-            got = y[:nw].cpu().numpy()
-            out["parity_max_err_over_range"] = float(np.abs(got - yw).max() / (yw.max() - yw.min()))
-    except Exception as e:
-        out["parity_max_err_over_range"] = f"unchecked: {e}"
-    if hasattr(fc, "apply_batch"):
+    if full:
+        t = timer(lambda: fc.apply(sig, True, out=y), 200, warm=max(3, warmup))
+        out["single_call_us"] = round(t * 1e6, 2)
+        out["single_call_Gsamples_per_s"] = round(n_out / t / 1e9, 2)
+        out["single_call_frac"] = round(8 * n_out / t / HBM_PEAK, 4)
+        # parity of the same call against the real reference (spot check; tests/ are the gate)
+        try:
+            from oracle import ref as oref
+            if oref.available():
+                yw, nw, _ = oref.get().fastconv(x_host, h, 0, 0, 1)
+                got = y[:nw].cpu().numpy()
+                out["parity_max_err_over_range"] = float(np.abs(got - yw).max() / (yw.max() - yw.min()))
+        except Exception as e:
+            out["parity_max_err_over_range"] = f"unchecked: {e}"
+    if full and hasattr(fc, "apply_batch"):
         nsig = 256
         xs = make_input(torch, dev, nsig, L, torch.float32, seed=5)
         ys = torch.empty_like(xs)
@@ -561,8 +589,10 @@ def fir_config(torch, pa, dev, timer, warmup):
     first = []
     for _ in range(6):
         first.append(round(timer(lambda: fc.apply(xl, True, out=yl), 1, warm=0) * 1e3, 4))
-    t = timer(lambda: fc.apply(xl, True, out=yl), 40, warm=warmup)
+    t = timer(lambda: fc.apply(xl, True, out=yl), steps, warm=warmup)
     nl = Ll - taps + 1
+    if dump:
+        dump_rows(torch, yl[: nl // 4096 * 4096].view(-1, 4096), dump)
     out["value"] = round(nl / t / 1e9, 2)
     out["unit"] = "G output samples/s"
     out["long_signal"] = f"2^{FIR['long_log2']} samples, {taps} taps"
@@ -726,11 +756,13 @@ def single_process_main(args):
     torch.cuda.set_device(devs[0])
     per_dev_ms = [a.elapsed_time(b) / args.steps for a, b in ev]
     tps = P * batch * args.steps / el
+    if args.dump_outputs:
+        dump_rows(torch, ys[0], os.path.join(args.dump_outputs, "spectrum.npy"))
     # parity of the first and the last part against the reference, inputs rebuilt on the host from their GLOBAL indices
-    parity = None
+    parity = None if args.full else "unchecked: plain run (--full checks against the reference)"
     try:
         from oracle import ref as oref
-        if oref.available():
+        if args.full and oref.available():
             rs = oref.get().setup(cfg["N"], cfg["tr"], dt)
             worst, cnt = 0.0, 0
             for p in sorted({0, P - 1}):
@@ -777,7 +809,11 @@ def main():
     ap.add_argument("--batch-log2", type=int, default=None, help="override: transforms per GPU = 2^this (weak)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-extras", action="store_true", help="headline line only: skip the other configs / side rates")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the other configs / side rates")
+    ap.add_argument("--full", action="store_true",
+                    help="also the parity check against the reference, side rates, other configs, batch sweep, sizes table, CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output as DIR/<name>.npy (a fixed sample when larger than 32 MiB)")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl", help=argparse.SUPPRESS)
     ap.add_argument("--selftest-cpu", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--single-process", action="store_true",
@@ -786,6 +822,8 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
     if args.single_process:
         return single_process_main(args)
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -822,10 +860,10 @@ def main():
             dist.init_process_group(backend=args.backend, rank=rank, world_size=world)
     from pffft_amd.sharding import combine_stats, shard_range
     timer = Timer(torch)
-    cpu_s = 0.0 if args.no_cpu_baseline else args.cpu_seconds
+    cpu_s = 0.0 if (args.no_cpu_baseline or not args.full) else args.cpu_seconds
     SEEDS = {"c2": 2, "c3": 3, "c5": 5}
 
-    def run_fft(key, scaling, steps, warmup, batch_log2=None):
+    def run_fft(key, scaling, steps, warmup, batch_log2=None, check=True, dump=None):
         cfg = CONFIGS[key]
         if scaling == "strong":
             total = 1 << cfg["total_log2"]
@@ -836,7 +874,7 @@ def main():
             first = rank * batch                # weak scaling: rank r holds global vectors [r * batch, (r + 1) * batch)
             in_place = False
         el, ks, kname, parity, first_ms = fft_config_run(torch, pa, dev, cfg, batch, first, steps, warmup, in_place, dist, rank,
-                                                         SEEDS[key])
+                                                         SEEDS[key], check, dump)
         st = combine_stats(el, float(batch), dist, dev)
         el, tot = st["elapsed_max"], st["units"]
         tps = tot * steps / el
@@ -859,17 +897,20 @@ def main():
     if args.config == "c4":
         if world > 1:
             raise SystemExit("bench.py: c4 (one 8 MiB signal) does not shard: replicas only (DESIGN.md §5)")
-        res, add_cpu = fir_config(torch, pa, dev, timer, args.warmup)
-        add_cpu(cpu_s)
+        res, add_cpu = fir_config(torch, pa, dev, timer, args.warmup, args.steps, args.full,
+                                  os.path.join(args.dump_outputs, "fir_output.npy") if args.dump_outputs else None)
+        if args.full:
+            add_cpu(cpu_s)
         line = {"metric": "G output samples/s, pffastconv overlap-save FIR, 4096 taps", "value": res["value"],
-                "unit": res["unit"], "n_gpus": 1, "steps": 40, "warmup": args.warmup,
+                "unit": res["unit"], "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
                 "ms_per_step": res["roofline"]["kernel_ms"], "higher_is_better": True, "scaling": "weak",
                 "vs_baseline": None, "dtype": "f32", "data": "synthetic", "config": {"workload": res.pop("workload")}}
         line.update(res)
         print(json.dumps(line), flush=True)
         return
 
-    head = run_fft(args.config, args.scaling, args.steps, args.warmup, args.batch_log2)
+    head = run_fft(args.config, args.scaling, args.steps, args.warmup, args.batch_log2, check=args.full,
+                   dump=os.path.join(args.dump_outputs, "spectrum.npy") if args.dump_outputs and rank == 0 else None)
     cfg = CONFIGS[args.config]
     out = None
     if rank == 0:
@@ -892,7 +933,7 @@ def main():
                 out[k] = head[k]
     extras, configs = {}, {}
     cpu_jobs = []        # CPU baselines run AFTER all GPU work: an idle GPU between configs drops its clocks
-    if not args.no_extras and args.config == "c2" and args.scaling == "weak":
+    if args.full and not args.no_extras and args.config == "c2" and args.scaling == "weak":
         if world == 1:
             # side rates of the headline kernel family + every other BASELINE config at its stated size
             setup = pa.Setup(1024, COMPLEX, np.float32)

@@ -1,14 +1,15 @@
 # Builds the REFERENCE's own test / validation / example programs, from their sources where they lie under
 # $(REF), against OUR library (pffft_amd/libpffft_hip.so) instead of the reference's PFFFT/PFFASTCONV
 # libraries: the drop-in claim of SURVEY.md row f-1.  Nothing of the reference is copied; only the
-# executables land in tests/_refbin/ (git-ignored, shipped to the GPU box by gpurun).
+# executables land in oracle/_ref/bin/ (git-ignored; built next to the reference objects, they travel with them
+# to the GPU box).  Run from oracle/:  make -C oracle -f refprogs.mk REF=<reference tree>
 # The reference's headers (include/pffft/*.h, pffft.hpp) are used verbatim — they ARE the interface.
 REF ?= /root/reference
-ROOT := $(abspath ../..)
-OUT := $(ROOT)/tests/_refbin
+ROOT := $(abspath ..)
+OUT := $(ROOT)/oracle/_ref/bin
 LIBDIR := $(ROOT)/pffft_amd
 INC := -I$(REF)/include -I$(REF)/include/pffft -I$(REF)/src
-LINK := -L$(LIBDIR) -lpffft_hip -Wl,-rpath,'$$ORIGIN/../../pffft_amd' -Wl,-rpath,/opt/rocm/lib -lm
+LINK := -L$(LIBDIR) -lpffft_hip -Wl,-rpath,'$$ORIGIN/../../../pffft_amd' -Wl,-rpath,/opt/rocm/lib -lm
 CFLAGS := -std=c99 -O2 -D_USE_MATH_DEFINES $(INC)
 CXXFLAGS := -O2 -D_USE_MATH_DEFINES $(INC)
 
@@ -50,7 +51,7 @@ $(OUT)/example_cpp11_%: $(REF)/examples/example_cpp11_%.cpp | $(OUT)
 
 # the reference's only program over the PFDSP mixers (row f-4), against libpfdsp_hip.so instead of libpfdsp
 $(OUT)/bench_mixers: $(REF)/benchmarks/bench_mixers.cpp | $(OUT)
-	g++ -std=c++11 $(CXXFLAGS) -I$(REF)/benchmarks -o $@ $< -L$(LIBDIR) -lpfdsp_hip -Wl,-rpath,'$$ORIGIN/../../pffft_amd' -Wl,-rpath,/opt/rocm/lib -lm
+	g++ -std=c++11 $(CXXFLAGS) -I$(REF)/benchmarks -o $@ $< -L$(LIBDIR) -lpfdsp_hip -Wl,-rpath,'$$ORIGIN/../../../pffft_amd' -Wl,-rpath,/opt/rocm/lib -lm
 
 clean:
 	rm -rf $(OUT)

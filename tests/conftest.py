@@ -14,7 +14,7 @@ def pytest_configure(config):
 
 
 def missing_checker(what: str):
-    """The checker artefacts (oracle/_ref/*.so, tests/_refbin/*) are git-ignored and travel to the GPU box prebuilt.
+    """The checker artefacts (oracle/_ref/*.so, oracle/_ref/bin/*) are git-ignored and travel to the GPU box prebuilt.
     On a box with a GPU their absence must FAIL the run — ~150 parity tests silently skipping would leave it green with
     nothing checked; without a GPU (a CPU-only checkout without /root/reference) the tests that need them skip."""
     gpu = False

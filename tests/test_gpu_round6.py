@@ -426,13 +426,42 @@ def test_bench_single_process_path(cfg):
         if share:
             env["PFFFT_BENCH_SHARE_GPU"] = "1"
         p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--single-process", "--config", cfg,
-                            "--steps", "3", "--warmup", "1", "--batch-log2", "12"], capture_output=True, text=True, timeout=600, env=env)
+                            "--steps", "3", "--warmup", "1", "--batch-log2", "12", "--full"], capture_output=True, text=True, timeout=600, env=env)
         assert p.returncode == 0, p.stderr[-2000:]
         line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
         assert line["n_gpus"] == gpus and line["single_process"] and line["steps"] == 3
         assert line["devices_seen"] == (min(gpus, nd) if not share else min(2, nd))
         assert line["parity_vs_reference"]["max_rel_err"] <= (1e-5 if cfg == "c2" else 1e-12)
         assert line["value"] > 0 and line["roofline"]["frac"] > 0
+
+
+@pytest.mark.parametrize("cfg,batch_log2", [("c2", 13), ("c5", 11)])
+def test_bench_plain_line_and_dumped_outputs(ref, cfg, batch_log2, tmp_path):
+    """bench.py without --full: the headline line only (no side configs, no CPU baseline, no parity check), `steps` = --steps; and
+    --dump-outputs DIR writes the last step's spectrum - every row when they fit in 32 MiB (c5, 2^11 rows), otherwise the rows numpy
+    default_rng(0) draws (c2, 2^13 rows) - equal to the reference's transform of the same global inputs (pffft_amd/sharding.py)."""
+    import json, os, subprocess, sys
+    from conftest import ROOT
+    from pffft_amd.sharding import global_uniform_np
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", cfg, "--steps", "5", "--warmup", "2",
+                        "--batch-log2", str(batch_log2), "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+    dt, tag, seed, tol = (np.float32, "f32", 2, 1e-5) if cfg == "c2" else (np.float64, "f64", 5, 1e-12)
+    assert line["steps"] == 5 and line["warmup"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["higher_is_better"] is True and line["dtype"] == tag
+    assert "cpu_baseline" not in line and "configs_summary" not in line["roofline"]
+    assert line["parity_vs_reference"].startswith("unchecked")
+    rows = 1 << batch_log2
+    y = np.load(os.path.join(str(tmp_path), "spectrum.npy"))
+    keep = min(rows, (32 << 20) // (2048 * np.dtype(dt).itemsize))
+    idx = np.arange(rows) if keep == rows else np.sort(np.random.default_rng(0).choice(rows, keep, replace=False))
+    assert y.dtype == dt and y.shape == (keep, 2048)
+    rs = ref.setup(1024, pa.COMPLEX, dt)
+    pick = [0, 1, keep // 2, keep - 1]
+    xin = np.stack([global_uniform_np(int(idx[k]) * 2048, 2048, seed, dt) for k in pick])
+    assert relerr(y[pick], rs.batch(xin, pa.FORWARD, False)) <= tol
+    rs.close()
 
 
 # ------------------------------------------------------------------ the single-image kernel (fft_one.h): one pass for the vectors that fill LDS once

@@ -1,8 +1,8 @@
 """The reference's OWN test / validation / example programs (tests/test_pffft.c, test_pffft.cpp,
 test_fft_factors.c, test_pffastconv.c, benchmarks/bench_pffft.c --validate, examples/*), compiled from their
-sources against libpffft_hip.so by tests/refprogs/Makefile ("the cheapest, strongest
-proof of drop-in").  The executables are built in the dev container (where /root/reference exists) into
-tests/_refbin/ and travel to the GPU box with the snapshot; the tests skip when they are absent on a CPU-only box and FAIL when they are absent on a GPU box."""
+sources against libpffft_hip.so by oracle/refprogs.mk ("the cheapest, strongest
+proof of drop-in").  The executables are built where the reference sources exist into oracle/_ref/bin/, next to
+the reference objects, and travel to the GPU box with them; the tests skip when they are absent on a CPU-only box and FAIL when they are absent on a GPU box."""
 import os
 import subprocess
 
@@ -10,7 +10,7 @@ import pytest
 
 from conftest import ROOT
 
-BIN = os.path.join(ROOT, "tests", "_refbin")
+BIN = os.path.join(ROOT, "oracle", "_ref", "bin")
 
 
 def _run(name, *args, timeout=900):
