@@ -203,7 +203,8 @@ const char *pffft_hip_kernel_name(const void *setup);
  * beyond LDS, the sweeps over HBM (tile lengths, which pass reads / stores the internal layout).  Decided once, at pffft_new_setup
  * (reference: the ifac[] / twiddle plan of struct PFFFT_Setup, src/pffft_priv_impl.h:1051-1060, is fixed at setup time too).  Writes at
  * most len - 1 characters + a terminating 0 into buf and returns the length of the whole text (snprintf convention), -1 for an
- * invalid handle.  Works for PFFFT_Setup and PFFFTD_Setup handles; no device needed. */
+ * invalid handle.  Works for PFFFT_Setup and PFFFTD_Setup handles; no device needed.  When the calling thread has set a selector
+ * (pffft_hip_set_variant, tests), the lines show the routes the transforms run under that selector instead of the stored ones. */
 int pffft_hip_describe(const void *setup, char *buf, size_t len);
 /* The devices a setup holds tables / counters / scratch on right now: the device it was first used on, then one entry per further
  * device (HIP device indices; values >= 64 belong to the test hook pffft_hip_set_variant(130)).  Fills devices[0 .. max) and returns the

@@ -167,7 +167,8 @@ def kernel_name(setup: "Setup") -> str:
 
 
 def describe(setup: "Setup") -> str:
-    """pffft_hip_describe: the routes the planner chose for this setup, one line per (direction, layout)."""
+    """pffft_hip_describe: the routes the planner chose for this setup, one line per (direction, layout) - under set_variant(v), the
+    routes that selector runs."""
     buf = C.create_string_buffer(4096)
     n = lib().pffft_hip_describe(setup.handle, buf, len(buf))
     if n < 0:

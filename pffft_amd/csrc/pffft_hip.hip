@@ -1295,7 +1295,7 @@ const char* launch_rule_name(LaunchRule r) {
         default: return "in-order";
     }
 }
-static int describe_route(const Setup* s, const Route& r, char* buf, size_t len) {
+static int describe_route(const Setup* s, const Route& r, int dir, int ordered, char* buf, size_t len) {
     switch (r.fam) {
         case FAM_TINY: return snprintf(buf, len, "tiny: one thread per transform, %s", launch_rule_name(r.rule));
         case FAM_C1024:
@@ -1330,7 +1330,9 @@ static int describe_route(const Setup* s, const Route& r, char* buf, size_t len)
                             (int)b.pair_after, b.sweeps);
         }
         case FAM_ONE: {
-            const int pi = (&r == &s->route[1][0] && !s->is_double && s->transform == PFFFT_COMPLEX) ? 2 : (&r == &s->route[1][0] || &r == &s->route[1][1]) ? 1 : 0;
+            // the plan launch_one_t (one_tu.hip) runs: the float complex backward transform from the layout has one of its own
+            const bool bwd = dir == PFFFT_BACKWARD;
+            const int pi = (bwd && !ordered && !s->is_double && s->transform == PFFFT_COMPLEX) ? 2 : bwd ? 1 : 0;
             const StockPlan& sp = s->one[pi];
             char rad[48] = "";
             for (int i = 0; i < sp.ns; ++i) snprintf(rad + strlen(rad), sizeof rad - strlen(rad), i ? " x %d" : "%d", sp.st[i].R);
@@ -1359,10 +1361,13 @@ static int describe_setup(const Setup* s, char* buf, size_t len) {
     out += line;
     static const char* dn[2] = {"forward ", "backward"};
     static const char* on[2] = {"unordered", "ordered  "};
+    // under a selector (pffft_hip_set_variant) the routes that selector runs, planned exactly as transform_batch plans them
+    const AbSel sel = ab();
     for (int d = 0; d < 2; ++d)
         for (int o = 1; o >= 0; --o) {
             char body[400];
-            describe_route(s, s->route[d][o], body, sizeof body);
+            const Route r = !sel.any() ? s->route[d][o] : s->is_double ? plan_route<double>(s, d, o, sel) : plan_route<float>(s, d, o, sel);
+            describe_route(s, r, d, o, body, sizeof body);
             snprintf(line, sizeof line, "  %s %s: %s\n", dn[d], on[o], body);
             out += line;
         }

@@ -380,6 +380,33 @@ def test_describe_matches_the_routing_restated_here():
     s.close()
 
 
+
+def test_describe_prints_the_single_image_plan_each_direction_runs():
+    """The float complex backward transform from the internal layout runs a single-image plan of its own (DESIGN.md §3.5a: Setup::one[2], four
+    stages for n >= 14400 where the forward plans take three): its describe() line shows that plan, the other three lines the shared one - with
+    no selector set and under a selector that leaves these sizes' routes alone (the routes are then planned again for the text)."""
+    def stages(ln):
+        return ln.split("stages ")[1].split(" in place")[0]
+
+    for N in (14400, 18432):
+        s = pa.Setup(N, pa.COMPLEX, np.float32)
+        text = pa.describe(s)
+        lines = text.strip().split("\n")[1:]
+        fo, fu, bo, bu = (stages(ln) for ln in lines)
+        assert fo == fu == bo and bu != fo and len(bu.split(" x ")) == 4 and len(fo.split(" x ")) == 3, (N, text)
+        pa.set_variant(91)                   # (reroutes n = 16 / 32 only)
+        try:
+            assert pa.describe(s).split("\n")[1:] == text.split("\n")[1:], N
+        finally:
+            pa.set_variant(0)
+        s.close()
+    # double and real: one plan per direction, the backward layouts share theirs
+    for tr, dt, N in ((pa.COMPLEX, np.float64, 7776), (pa.REAL, np.float32, 28800)):
+        s = pa.Setup(N, tr, dt)
+        lines = pa.describe(s).strip().split("\n")[1:]
+        assert stages(lines[2]) == stages(lines[3]), (N, lines)
+        s.close()
+
 def test_setup_devices_without_a_device(L):
     """pffft_hip_setup_devices (round 6: one setup, any device - the device state of a setup is kept per device and listed here): no state
     before the first transform, an invalid handle lists nothing, and a legacy call that fails soft for want of a GPU leaves the list empty
