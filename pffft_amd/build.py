@@ -16,11 +16,18 @@ DSP_LIB = os.path.join(HERE, "libpfdsp_hip.so")
 DSP_SRC = os.path.join(CSRC, "pfdsp_hip.hip")
 DSP_DEPS = [DSP_SRC, os.path.join(CSRC, "pfdsp_mix.h"), os.path.join(HERE, "..", "include", "pfdsp_hip.h"),
             os.path.join(CSRC, "exports_dsp.map")]
+# the PFDSP carriers and CIC down-converter (pf_carrier.h, pf_cic.h): a companion library, so that libpfdsp_hip.so keeps the
+# mixers' exported set
+CIC_LIB = os.path.join(HERE, "libpfdsp_cic_hip.so")
+CIC_SRC = os.path.join(CSRC, "pfdsp_cic_hip.hip")
+CIC_DEPS = [CIC_SRC, os.path.join(CSRC, "pfdsp_cic.h"), os.path.join(HERE, "..", "include", "pfdsp_cic_hip.h"),
+            os.path.join(CSRC, "exports_cic.map")]
 
 
 def _deps():
     out = [os.path.join(CSRC, f) for f in os.listdir(CSRC)
-           if f.endswith((".h", ".hip", ".map")) and f not in ("pfdsp_hip.hip", "exports_dsp.map")]
+           if f.endswith((".h", ".hip", ".map")) and f not in ("pfdsp_hip.hip", "exports_dsp.map", "pfdsp_cic_hip.hip", "pfdsp_cic.h",
+                                                               "exports_cic.map")]
     out.append(os.path.join(HERE, "..", "include", "pffft_hip.h"))
     return out
 
@@ -37,12 +44,13 @@ def needs_build() -> bool:
 COMPRESS = [] if os.environ.get("PFFFT_HIP_NO_COMPRESS") == "1" else ["--offload-compress"]
 
 
-def _build_dsp(force: bool, verbose: bool) -> None:
-    if not force and os.path.exists(DSP_LIB) and all(os.path.getmtime(f) <= os.path.getmtime(DSP_LIB) for f in DSP_DEPS):
+def _build_dsp(force: bool, verbose: bool, lib: str = DSP_LIB, src: str = DSP_SRC, deps=DSP_DEPS,
+               exports: str = "exports_dsp.map") -> None:
+    if not force and os.path.exists(lib) and all(os.path.getmtime(f) <= os.path.getmtime(lib) for f in deps):
         return
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-ffp-contract=off"] + COMPRESS + [
-           "-shared", "-Wl,--version-script=" + os.path.join(CSRC, "exports_dsp.map"), "-o", DSP_LIB, DSP_SRC]
+           "-shared", "-Wl,--version-script=" + os.path.join(CSRC, exports), "-o", lib, src]
     if verbose:
         print(" ".join(cmd))
     subprocess.run(cmd, check=True, cwd=CSRC)
@@ -61,6 +69,7 @@ def _obj_stale(obj: str) -> bool:
 
 def build(force: bool = False, verbose: bool = False) -> str:
     _build_dsp(force, verbose)
+    _build_dsp(force, verbose, CIC_LIB, CIC_SRC, CIC_DEPS, "exports_cic.map")
     if not force and not needs_build():
         return LIB
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -1,4 +1,5 @@
-"""ctypes binding of the PFDSP mixer ABI (include/pfdsp_hip.h = the reference's include/pffft/pf_mixer.h:61-280).
+"""ctypes binding of the PFDSP ABI (include/pfdsp_hip.h = the reference's include/pffft/pf_mixer.h:61-280;
+include/pfdsp_cic_hip.h = its pf_carrier.h and pf_cic.h).
 
 `MixerABI(path)` binds every reference-named entry of ANY shared object with that ABI — the product
 (`libpfdsp_hip.so`, via `lib()`) and, in tests only, the compiled reference (oracle/pfdsp_ref.py hands it
@@ -7,6 +8,10 @@ oracle/_ref/libpfdsp_ref.so).  The struct classes below are the ABI's by-value s
 `Mixer` is the small operator-style mirror the tests use:  m = Mixer("addfast", rate); y = m(x)  keeps the
 algorithm's state between calls exactly as a C caller would (returned phase fed back / struct advanced).
 numpy complex64 arrays go in as host pointers; torch CUDA complex64 tensors as device pointers.
+
+The carriers and the CIC down-converter are the companion library libpfdsp_cic_hip.so (include/pfdsp_cic_hip.h, `cic_lib()`):
+`CicDdc(factor)` is one CIC down-converter state (`s16` / `cs16` / `cu8(x, outsize, rate)`), `cicddc_bank` runs many of them
+over one device input (pfdsp_hip_cicddc_device), `generate(name, size)` writes a carrier.
 """
 from __future__ import annotations
 
@@ -108,6 +113,15 @@ REFERENCE_ENTRIES = {
 for _k, _T in _SSE_DATA.items():
     REFERENCE_ENTRIES[f"shift_limited_unroll_{_k}_sse_init"] = (_T, [_F, _F])
     REFERENCE_ENTRIES[f"shift_limited_unroll_{_k}_sse_inp_c"] = (None, [_P, _I, C.POINTER(_T)])
+
+
+# carriers (pf_carrier.h:72-85) and the CIC down-converter (pf_cic.h): libpfdsp_cic_hip.so
+CARRIERS = ("dc_f", "dc_s16", "pos_fs4_f", "pos_fs4_s16", "neg_fs4_f", "neg_fs4_s16", "dc_pos_fs4_s16", "dc_neg_fs4_s16",
+            "pos_neg_fs4_s16", "dc_pos_neg_fs4_s16", "pos_neg_fs2_s16", "dc_pos_neg_fs2_s16")
+CIC_FORMATS = {"s16": 0, "cs16": 1, "cu8": 2}    # PFDSP_HIP_CIC_S16 / _CS16 / _CU8
+CIC_ENTRIES = {"cicddc_init": (_P, [_I]), "cicddc_free": (None, [_P])}
+CIC_ENTRIES.update({f"cicddc_{f}_c": (None, [_P, _P, _P, _I, _F]) for f in CIC_FORMATS})
+CIC_ENTRIES.update({f"generate_{n}": (None, [_P, _I]) for n in CARRIERS})
 
 
 class MixerABI:
@@ -273,3 +287,128 @@ class Mixer:
         po, n = _ptr(out)
         self.L.gen_recursive_osc_c(po, n, C.byref(self.conf), C.byref(self.data))
         return out
+
+
+# ------------------------------------------------------------------ carriers and CIC down-converter
+class _CicABI:
+    """the entries of libpfdsp_cic_hip.so, typed"""
+
+    def __init__(self, path: str):
+        if not os.path.exists(path):
+            raise RuntimeError(f"{path} is missing — build it with `python -m pffft_amd.build`.  There is no CPU fallback.")
+        self.path = path
+        self.dll = C.CDLL(path, mode=getattr(os, "RTLD_LOCAL", 0))
+        for name, (res, args) in CIC_ENTRIES.items():
+            fn = getattr(self.dll, name)
+            fn.restype, fn.argtypes = res, args
+            setattr(self, name, fn)
+        self.dll.pfdsp_hip_cicddc_device.restype = C.c_int
+        self.dll.pfdsp_hip_cicddc_device.argtypes = [_P, _P, _I, _I, _P, C.c_size_t, _P, C.c_size_t, _P]
+        self.dll.pfdsp_hip_cic_last_error.restype = C.c_char_p
+        self.dll.pfdsp_hip_cic_error_count.restype = C.c_uint
+
+
+_CIC_LIB = None
+
+
+def cic_lib_path() -> str:
+    return os.path.join(_HERE, "libpfdsp_cic_hip.so")
+
+
+def cic_lib() -> _CicABI:
+    """The carriers / CIC library (HIP); torch first, as for lib()."""
+    global _CIC_LIB
+    if _CIC_LIB is None:
+        try:
+            import torch  # noqa: F401
+        except Exception:
+            pass
+        _CIC_LIB = _CicABI(cic_lib_path())
+    return _CIC_LIB
+
+
+def _buf(x) -> int:
+    """address of a contiguous numpy array (host pointer) or torch CUDA tensor (device pointer)"""
+    if _is_torch(x):
+        assert x.is_cuda and x.is_contiguous()
+        return x.data_ptr()
+    assert isinstance(x, np.ndarray) and x.flags.c_contiguous
+    return x.ctypes.data
+
+
+def generate(name: str, size: int, out=None):
+    """generate_<name> (pf_carrier.h): writes `size` complex samples = 2*size scalars (float32 for *_f, int16 otherwise)
+    into `out` (numpy: written on the host; torch CUDA tensor: fill kernel), by default a new numpy array"""
+    assert name in CARRIERS, name
+    if out is None:
+        out = np.zeros(2 * max(int(size), 0), np.float32 if name.endswith("_f") else np.int16)
+    getattr(cic_lib(), f"generate_{name}")(_buf(out), int(size))
+    return out
+
+
+class CicDdc:
+    """One CIC down-converter state (cicddc_init(factor)).  s16 / cs16 / cu8(x, outsize, rate) run one call of the
+    reference's entry of that format on x (numpy int16 / uint8: host pointers; torch CUDA tensors: device pointers) and
+    return the outsize complex64 outputs (numpy or torch like x); calls chain through the state as in C."""
+
+    _DT = {"s16": "int16", "cs16": "int16", "cu8": "uint8"}
+
+    def __init__(self, factor: int):
+        self.L = cic_lib()
+        self.factor = int(factor)
+        self.handle = self.L.cicddc_init(self.factor)
+        if not self.handle:
+            raise ValueError(f"cicddc_init({factor}) returned NULL: the factor must be >= 1")
+
+    def close(self):
+        if self.handle:
+            self.L.cicddc_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _run(self, fmt: str, x, outsize: int, rate: float):
+        need = outsize * self.factor * (1 if fmt == "s16" else 2)
+        if _is_torch(x):
+            import torch
+            assert x.dtype == getattr(torch, self._DT[fmt]) and x.numel() >= need
+            out = torch.empty(max(outsize, 0), dtype=torch.complex64, device=x.device)
+        else:
+            assert x.dtype == np.dtype(self._DT[fmt]) and x.size >= need
+            out = np.empty(max(outsize, 0), np.complex64)
+        getattr(self.L, f"cicddc_{fmt}_c")(self.handle, _buf(x), _buf(out), int(outsize), float(rate))
+        return out
+
+    def s16(self, x, outsize: int, rate: float):
+        return self._run("s16", x, outsize, rate)
+
+    def cs16(self, x, outsize: int, rate: float):
+        return self._run("cs16", x, outsize, rate)
+
+    def cu8(self, x, outsize: int, rate: float):
+        return self._run("cu8", x, outsize, rate)
+
+
+def cicddc_bank(states, rates, fmt: str, x, outsize: int, out=None):
+    """pfdsp_hip_cicddc_device on the current torch stream: every CicDdc of `states` (one factor) over the one device
+    input x with its own rate.  Returns `out`, by default a new (nch, outsize) complex64 tensor; a given `out` is 2-D
+    with unit column stride and row stride >= outsize (the channels' out_stride).  outsize 0 binds the states."""
+    import torch
+    L = cic_lib()
+    nch = len(states)
+    if out is None:
+        out = torch.empty((nch, max(outsize, 0)), dtype=torch.complex64, device=x.device if x is not None else "cuda")
+    assert out.dtype == torch.complex64 and out.is_cuda and out.dim() == 2 and out.shape[0] == nch
+    assert out.shape[1] == 0 or out.stride(1) == 1
+    hs = (C.c_void_p * nch)(*[s.handle for s in states])
+    rs = (C.c_float * nch)(*[float(r) for r in rates])
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    rc = L.dll.pfdsp_hip_cicddc_device(hs, rs, nch, CIC_FORMATS[fmt], x.data_ptr() if x is not None else None,
+                                       int(outsize), out.data_ptr(), max(out.stride(0), int(outsize)), st)
+    if rc:
+        raise RuntimeError(f"pfdsp_hip_cicddc_device failed ({rc}): {L.dll.pfdsp_hip_cic_last_error().decode()}")
+    return out
