@@ -181,6 +181,59 @@ int pffftd_hip_convolve_batch(PFFFTD_Setup *, const double *in, const double *H,
 int pffft_hip_shift_transform_batch(PFFFT_Setup *, const float *in, float *out, size_t batch, int ordered,
                                     double rate, double phase_rad, void *stream);
 
+/* Windowed overlapping-frame transforms: short-time analysis and overlap-add synthesis in one call each.
+ * A SAMPLE is one scalar for a real setup and one interleaved complex pair for a complex one (spp = 1 / 2 scalars); `hop` and the
+ * frame positions are in samples, every stride is in scalars of the setup's type.  All pointers are device pointers, the calls are
+ * asynchronous on `stream`; 0, else a hipError_t with its text in pffft_hip_last_error().
+ *
+ * pffft_hip_frames_transform_batch.  Frame f of signal i is x[j] = signal[i*signal_stride + (f*hop + j)*spp ..] * window[j], j < N
+ * (window: N real scalars; NULL = no multiplication at all); the product is ONE rounding in the setup's type.  Frame
+ * v = i*nframes + f is forward-transformed exactly as pffft_hip_transform_batch transforms vector v - the result equals
+ * transform_batch of the materialised frames bit for bit - and written at out + v*out_stride:
+ *   PFFFT_HIP_FRAMES_INTERNAL / _ORDERED  the layouts of ordered = 0 / 1 (N scalars per frame for a real, 2N for a complex setup);
+ *   PFFFT_HIP_FRAMES_POWER                re^2 + im^2 per bin: N/2 + 1 scalars per frame for a real setup (bins 0 ... N/2, DC and
+ *                                         Nyquist unpacked), N for a complex one.
+ * out_stride = 0: dense rows.  No centring and no padding: every signal holds (nframes-1)*hop + N samples (checked against
+ * signal_stride when nsignals > 1; signal_stride is not read when nsignals == 1).  Any hop >= 1, also hop > N.  signal and out must
+ * not overlap.  Real float setups of N = 1024 / 2048 / 4096 run as ONE kernel - the register-tiled transform with a framed,
+ * windowing loader: (hop + N) scalars of HBM traffic per frame, |X|^2 taken from the registers - when hop, signal_stride and (for the
+ * spectrum outputs) out_stride are multiples of 4 and signal, window and out are 16-byte aligned.  Every other legal size, hop,
+ * alignment and precision is composed: a framing kernel into a per-stream frame matrix, pffft_hip_transform_batch, and a row kernel
+ * where `out` is pitched or a power spectrum.  The frame matrix holds at most 256 MiB; longer batches go through it in chunks on
+ * `stream`.  It follows the rules of the other per-stream scratch: it grows outside HIP graph capture only - a call that would have to
+ * grow it while `stream` is capturing fails with hipErrorStreamCaptureUnsupported and launches nothing: run the call once on that
+ * stream before capturing.
+ *
+ * pffft_hip_frames_overlap_add_batch.  Spectrum v = i*nframes + f (layout by `ordered`, at spectra + v*spectra_stride, 0 = dense) is
+ * backward-transformed as pffft_hip_transform_batch(..., PFFFT_BACKWARD, ordered) does (UNSCALED) into y_f, and sample s of signal i,
+ * for every s < (nframes-1)*hop + N, is WRITTEN (not accumulated) as
+ *     signal[s] = scaling * ( sum_f window[s - f*hop] * y_f[s - f*hop] )    over the frames with 0 <= s - f*hop < N, f ascending,
+ * each product and each addition rounded once, the sum started from its first term (window == NULL: the terms are y_f itself): a
+ * gather in a fixed order, no atomics, so the result is deterministic.  Samples no frame covers (hop > N) are written as 0.
+ * NORMALISING BY THE WINDOW'S OVERLAP SUM IS THE CALLER'S BUSINESS (`scaling`): the transforms are unscaled, so for a periodic Hann
+ * window on both sides at hop = N/4 it is 1/(1.5*N).  Composed: backward transforms into the frame matrix, then the gather (beyond
+ * the 256 MiB cap signal by signal in runs of frames).  spectra and signal must not overlap.
+ *
+ * Validation happens before any device is touched: a NULL or foreign setup, hop == 0, an unknown `output`, a stride smaller than the
+ * row it has to hold, a signal_stride smaller than one signal's samples when nsignals > 1, a NULL signal / spectra / out -> non-zero,
+ * nothing launched.  nsignals == 0 or nframes == 0 -> 0, nothing launched. */
+enum { PFFFT_HIP_FRAMES_INTERNAL = 0, PFFFT_HIP_FRAMES_ORDERED = 1, PFFFT_HIP_FRAMES_POWER = 2 };
+int pffft_hip_frames_transform_batch(PFFFT_Setup *, const float *signal, size_t signal_stride, size_t nsignals, size_t nframes,
+                                     size_t hop, const float *window, float *out, size_t out_stride, int output, void *stream);
+int pffftd_hip_frames_transform_batch(PFFFTD_Setup *, const double *signal, size_t signal_stride, size_t nsignals, size_t nframes,
+                                      size_t hop, const double *window, double *out, size_t out_stride, int output, void *stream);
+int pffft_hip_frames_overlap_add_batch(PFFFT_Setup *, const float *spectra, size_t spectra_stride, size_t nsignals, size_t nframes,
+                                       size_t hop, const float *window, float scaling, float *signal, size_t signal_stride,
+                                       int ordered, void *stream);
+int pffftd_hip_frames_overlap_add_batch(PFFFTD_Setup *, const double *spectra, size_t spectra_stride, size_t nsignals, size_t nframes,
+                                        size_t hop, const double *window, double scaling, double *signal, size_t signal_stride,
+                                        int ordered, void *stream);
+/* The route pffft_hip_frames_transform_batch takes for these arguments under the calling thread's selector (pffft_hip_set_variant:
+ * 124 = always composed, 125 = fused wherever it is legal): "fused" or "composed"; "" for an invalid handle, hop == 0 or an unknown
+ * output.  Pointer alignment is checked at the call: the query assumes 16-byte aligned pointers.  signal_stride = 0: one signal.
+ * Host arithmetic only; PFFFT_Setup and PFFFTD_Setup handles. */
+const char *pffft_hip_frames_route(const void *setup, size_t hop, size_t signal_stride, size_t out_stride, int output);
+
 /* Overlap-save FIR on device-resident signal/output (same block schedule as pffastconv_apply,
  * src/pffastconv.c:204-261): returns the number of output samples written, or -1 on error. */
 int pffastconv_hip_apply_device(PFFASTCONV_Setup *, const float *d_input, int inputLen, float *d_output,

@@ -77,6 +77,12 @@ def lib():
         g("hip_convolve_batch").restype = C.c_int
         g("hip_convolve_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, ct, C.c_size_t,
                                             C.c_int, C.c_int, C.c_void_p]
+        g("hip_frames_transform_batch").restype = C.c_int
+        g("hip_frames_transform_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
+                                                    C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+        g("hip_frames_overlap_add_batch").restype = C.c_int
+        g("hip_frames_overlap_add_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
+                                                      C.c_void_p, ct, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
         getattr(L, f"validate_{pfx}_simd").restype = C.c_int
         getattr(L, f"validate_{pfx}_simd_ex").restype = C.c_int
         getattr(L, f"validate_{pfx}_simd_ex").argtypes = [C.c_void_p]
@@ -95,6 +101,8 @@ def lib():
     L.pffft_hip_shift_transform_batch.restype = C.c_int
     L.pffft_hip_shift_transform_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_double,
                                                   C.c_double, C.c_void_p]
+    L.pffft_hip_frames_route.restype = C.c_char_p
+    L.pffft_hip_frames_route.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int]
     L.pffft_hip_kernel_name.restype = C.c_char_p; L.pffft_hip_kernel_name.argtypes = [C.c_void_p]
     L.pffft_hip_describe.restype = C.c_int; L.pffft_hip_describe.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.pffft_hip_setup_devices.restype = C.c_int; L.pffft_hip_setup_devices.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_int]
@@ -181,6 +189,16 @@ def setup_devices(setup: "Setup"):
     buf = (C.c_int * 80)()
     n = lib().pffft_hip_setup_devices(setup.handle, buf, 80)
     return [buf[i] for i in range(min(n, 80))]
+
+
+FRAMES_OUTPUTS = {"internal": 0, "ordered": 1, "power": 2}
+
+
+def frames_route(setup: "Setup", hop, signal_stride=0, out_stride=0, output="ordered") -> str:
+    """pffft_hip_frames_route: "fused" / "composed" for an analysis call with 16-byte aligned pointers, under the calling
+    thread's selector.  Host arithmetic only."""
+    return lib().pffft_hip_frames_route(setup.handle, int(hop), int(signal_stride), int(out_stride),
+                                        FRAMES_OUTPUTS[output]).decode()
 
 
 def _is_torch(x) -> bool:
@@ -301,6 +319,71 @@ class Setup:
         fn = getattr(self._L, f"{self._pfx}_hip_convolve_batch")
         _check(fn(self.handle, x.data_ptr(), H.data_ptr(), out.data_ptr(), scaling, batch, int(bool(accumulate)), int(bc),
                   self._stream()), "hip_convolve_batch")
+        return out
+
+    def _frames_rows(self, t, what):
+        """(nsignals, row stride in scalars, scalars per row) of a 1-D signal / 2-D [nsignals, scalars] tensor."""
+        import torch
+        want = torch.float64 if self.dtype == np.float64 else torch.float32
+        assert t.is_cuda and t.dtype == want and t.dim() in (1, 2) and t.stride(-1) == 1, \
+            f"{what}: 1-D or 2-D CUDA tensor of the setup dtype with unit stride along the samples"
+        if t.dim() == 1:
+            return 1, 0, t.shape[0]
+        return t.shape[0], (t.stride(0) if t.shape[0] > 1 else 0), t.shape[1]
+
+    def frames_out_row(self, output="internal") -> int:
+        """Scalars per output row of frames_transform_batch."""
+        if output == "power":
+            return self.N // 2 + 1 if self.transform_type == REAL else self.N
+        return self.vec_scalars
+
+    def frames_transform_batch(self, signal, hop, nframes=None, window=None, out=None, output="internal"):
+        """pffft_hip_frames_transform_batch: frames of N samples every `hop` samples of `signal` (1-D, or 2-D [nsignals, scalars] with
+        the row stride taken from the tensor; complex setups: interleaved pairs), times `window` (N scalars, None = none), forward
+        transformed.  Returns [nsignals,] nframes, row]; `out` may have padded rows (its stride(-2) is the row pitch)."""
+        import torch
+        spp = 2 if self.transform_type == COMPLEX else 1
+        nsig, sstride, scalars = self._frames_rows(signal, "signal")
+        samples = scalars // spp
+        if nframes is None:
+            assert samples >= self.N, "the signal holds no frame"
+            nframes = (samples - self.N) // hop + 1
+        assert nframes == 0 or (nframes - 1) * hop + self.N <= samples, "the signal is shorter than its frames"
+        row = self.frames_out_row(output)
+        if out is None:
+            out = torch.empty((nsig, nframes, row) if signal.dim() == 2 else (nframes, row), dtype=signal.dtype, device=signal.device)
+        assert out.dtype == signal.dtype and out.is_cuda and out.stride(-1) == 1 and out.shape[-1] == row and out.shape[-2] == nframes
+        assert out.dim() == 2 or (out.dim() == 3 and out.shape[0] == nsig)
+        pitch = out.stride(-2) if nframes > 1 else (out.stride(0) if out.dim() == 3 and nsig > 1 else row)
+        assert out.dim() == 2 or nsig == 1 or out.stride(0) == nframes * pitch, "frame v = i nframes + f is written at v * pitch"
+        if window is not None:
+            assert window.is_cuda and window.dtype == signal.dtype and window.is_contiguous() and window.numel() == self.N
+        fn = getattr(self._L, f"{self._pfx}_hip_frames_transform_batch")
+        _check(fn(self.handle, signal.data_ptr(), sstride, nsig, nframes, hop, window.data_ptr() if window is not None else None,
+                  out.data_ptr(), pitch, FRAMES_OUTPUTS[output], self._stream()), "hip_frames_transform_batch")
+        return out
+
+    def frames_overlap_add_batch(self, spectra, hop, window=None, scaling=1.0, out=None, ordered=False):
+        """pffft_hip_frames_overlap_add_batch: spectra [nsignals,] nframes, N or 2N scalars] (stride(-2) = row pitch) are backward
+        transformed (unscaled) and overlap-added every `hop` samples: out[s] = scaling * sum_f window[s - f hop] y_f[s - f hop].
+        Returns [nsignals,] (nframes - 1) hop + N samples]; normalising by the window's overlap sum is the caller's `scaling`."""
+        import torch
+        spp = 2 if self.transform_type == COMPLEX else 1
+        assert spectra.is_cuda and spectra.dim() in (2, 3) and spectra.stride(-1) == 1 and spectra.shape[-1] == self.vec_scalars
+        nframes = spectra.shape[-2]
+        nsig = spectra.shape[0] if spectra.dim() == 3 else 1
+        pitch = spectra.stride(-2) if nframes > 1 else (spectra.stride(0) if spectra.dim() == 3 and nsig > 1 else self.vec_scalars)
+        assert spectra.dim() == 2 or nsig == 1 or spectra.stride(0) == nframes * pitch
+        scalars = ((nframes - 1) * hop + self.N) * spp if nframes else 0
+        if out is None:
+            out = torch.empty((nsig, scalars) if spectra.dim() == 3 else (scalars,), dtype=spectra.dtype, device=spectra.device)
+        osig, ostride, oscalars = self._frames_rows(out, "out")
+        assert osig == nsig and oscalars >= scalars
+        if window is not None:
+            assert window.is_cuda and window.dtype == spectra.dtype and window.is_contiguous() and window.numel() == self.N
+        fn = getattr(self._L, f"{self._pfx}_hip_frames_overlap_add_batch")
+        _check(fn(self.handle, spectra.data_ptr(), pitch, nsig, nframes, hop, window.data_ptr() if window is not None else None,
+                  float(scaling), out.data_ptr(), ostride, int(bool(ordered)), self._stream()), "hip_frames_overlap_add_batch")
         return out
 
     # ---------------- host (numpy): the legacy single-vector entries ----------------

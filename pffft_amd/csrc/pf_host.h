@@ -105,6 +105,10 @@ struct Setup {
     std::mutex conv_mu;
     std::map<hipStream_t, Scratch> conv_scratch;
     unsigned long long conv_clock = 0;
+    // frame matrix of the composed pffft_hip_frames_* routes (frames_tu.hip): one per stream, frames_mu held while a call enqueues
+    std::mutex frames_mu;
+    std::map<hipStream_t, Scratch> frames_scratch;
+    unsigned long long frames_clock = 0;
     void* d_stage[3] = {nullptr, nullptr, nullptr};  // staging for host-pointer legacy calls
     size_t stage_bytes[3] = {0, 0, 0};
     void* h_stage[4] = {nullptr, nullptr, nullptr, nullptr};  // pinned host images the kernels read / write directly (small vectors)
@@ -127,6 +131,14 @@ unsigned* take_counters(Setup* s, hipStream_t st, unsigned pairs = 1);
 Setup* for_device(Setup* s);
 // devices `s` holds state on right now (its own binding first): fills out[0 .. max), returns the count (pffft_hip_setup_devices)
 int setup_devices(Setup* s, int* out, int max);
+
+// pffft_hip.hip: the per-stream scratch of a setup (held under the lock of the table it lives in) - the entry of `st`, created on first use
+// (the stream that used the setup longest ago makes room), and buffer i of it grown to `bytes` (outside graph capture only)
+int stream_scratch(std::map<hipStream_t, Setup::Scratch>& tab, unsigned long long& clock, hipStream_t st, Setup::Scratch** out);
+int scratch_grow(Setup* s, Setup::Scratch& sc, int i, size_t bytes);
+// pffft_hip.hip, for frames_tu.hip: pffft(d)_hip_transform_batch on a checked setup, and the lazy device initialisation of a resolved one
+int transform_batch_any(Setup* s, const void* in, void* out, size_t batch, int dir, int ordered, hipStream_t st);
+int ensure_device_any(Setup* s);
 
 struct FcBatch { int nsig; size_t xstride, ystride; };   // signals of one pffastconv call (1 for the reference entries)
 

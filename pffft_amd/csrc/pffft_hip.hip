@@ -322,6 +322,7 @@ static void destroy_setup(Setup* s) {
     for (void* p : s->d_bigtw) if (p) (void)hipFree(p);
     for (auto& kv : s->big_scratch) for (void* p : kv.second.buf) if (p) (void)hipFree(p);
     for (auto& kv : s->conv_scratch) for (void* p : kv.second.buf) if (p) (void)hipFree(p);
+    for (auto& kv : s->frames_scratch) for (void* p : kv.second.buf) if (p) (void)hipFree(p);
     for (void* p : s->retired) if (p) (void)hipFree(p);
     for (void* p : s->d_stage) if (p) (void)hipFree(p);
     for (void* p : s->h_stage) if (p) (void)hipHostFree(p);
@@ -969,7 +970,7 @@ static int launch_block(Setup* s, int mode, const T* in, T* out, size_t batch, h
 // free and re-allocate every stream's buffers on every call.  An entry a HIP graph has recorded (Scratch::captured) is never the victim,
 // and a buffer it outgrows is retired instead of freed: a replay dereferences the pointers it froze at capture time.
 constexpr size_t SCRATCH_STREAMS = 8;
-static int stream_scratch(std::map<hipStream_t, Setup::Scratch>& tab, unsigned long long& clock, hipStream_t st, Setup::Scratch** out) {
+int stream_scratch(std::map<hipStream_t, Setup::Scratch>& tab, unsigned long long& clock, hipStream_t st, Setup::Scratch** out) {
     if (tab.size() >= SCRATCH_STREAMS && !tab.count(st)) {
         auto victim = tab.end();
         for (auto it = tab.begin(); it != tab.end(); ++it)
@@ -985,7 +986,7 @@ static int stream_scratch(std::map<hipStream_t, Setup::Scratch>& tab, unsigned l
     *out = &sc;
     return 0;
 }
-static int scratch_grow(Setup* s, Setup::Scratch& sc, int i, size_t bytes) {
+int scratch_grow(Setup* s, Setup::Scratch& sc, int i, size_t bytes) {
     if (sc.bytes[i] >= bytes) return 0;
     // (hipFree waits for the device: kernels of this stream still using the old buffer finish first)
     if (sc.buf[i]) {
@@ -1273,6 +1274,13 @@ static int transform_batch(Setup* s, const T* in, T* out, size_t batch, int dir,
     g_last_error = "pffft_hip: no kernel for this size";
     return (int)hipErrorInvalidValue;
 }
+
+// frames_tu.hip: the batched transform and the lazy device state behind type-erased pointers
+int transform_batch_any(Setup* s, const void* in, void* out, size_t batch, int dir, int ordered, hipStream_t st) {
+    if (s->is_double) return transform_batch<double>(s, (const double*)in, (double*)out, batch, dir, ordered, st);
+    return transform_batch<float>(s, (const float*)in, (float*)out, batch, dir, ordered, st);
+}
+int ensure_device_any(Setup* s) { return s->is_double ? ensure_device<double>(s) : ensure_device<float>(s); }
 
 // ------------------------------------------------------------------------------------------------
 // pffft_hip_describe: the routes of a setup as text
