@@ -22,7 +22,7 @@ static int conv_launch(Setup* s, const T* in, const T* H, T* out, size_t batch, 
     if (grid > groups) grid = groups;
     unsigned* ctr = groups <= grid ? nullptr : take_counters(s, st);
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(C::WG_THREADS), C::LDS_BYTES, st, in, H, out, (unsigned)batch, scaling, accumulate,
-                       (const cx<T>*)s->d_tw, (const cx<T>*)s->d_twr, ctr);
+                       s->d_tw.as<cx<T>>(), s->d_twr.as<cx<T>>(), ctr);
     PF_CHECK(hipGetLastError());
     return 0;
 }

@@ -6,10 +6,9 @@
 #include "fft_dma.h"
 #include "fft_split.h"
 #include "fft_fir32.h"
-#include <cmath>
+#include <utility>
 
 namespace pf {
-
 
 template <class C>
 static int fir_dma_cfg(Setup* ps, const float* d_Hc, const float* d_x, float* d_y, int nblk, int step, int inputLen,
@@ -24,14 +23,13 @@ static int fir_dma_cfg(Setup* ps, const float* d_Hc, const float* d_x, float* d_
     if (grid > groups) grid = groups;
     unsigned* ctr = groups <= grid ? nullptr : take_counters(ps, st);
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(C::WG_THREADS), G::LDS_BYTES, st, d_x, d_y, (const cx<float>*)d_Hc,
-                       nblk, step, inputLen, lastOut, (const cx<float>*)ps->d_tw, (const cx<float>*)ps->d_twr, ctr,
+                       nblk, step, inputLen, lastOut, ps->d_tw.as<cx<float>>(), ps->d_twr.as<cx<float>>(), ctr,
                        fb.nsig, fb.xstride, fb.ystride);
     PF_CHECK(hipGetLastError());
     return 0;
 }
 
-// W_m^j (m = 1024, 512) for the wave-local sub-transforms of the split kernels: one table per device and length, generated in
-// extended precision
+// W_m^j (m = 1024, 512) for the wave-local sub-transforms of the split kernels: one table per device and length
 static int split_sub_table(const cx<float>** out, int m = 1024) {
     static std::mutex mu;
     static std::map<long long, cx<float>*> tabs;
@@ -41,12 +39,8 @@ static int split_sub_table(const cx<float>** out, int m = 1024) {
     const long long key = (long long)dev * 65536 + m;
     auto it = tabs.find(key);
     if (it == tabs.end()) {
-        std::vector<cx<float>> tw(m);
-        for (int j = 0; j < m; ++j) {
-            const long double a = -2.0L * 3.14159265358979323846264338327950288L * (long double)j / (long double)m;
-            tw[j].x = (float)cosl(a); tw[j].y = (float)sinl(a);
-        }
-        cx<float>* d = nullptr;
+        const std::vector<cx<float>> tw = unit_roots<float>(m, m);
+        cx<float>* d = nullptr;   // (cached for the life of the process, never freed: no owner with static storage, pf_devmem.h)
         PF_CHECK(hipMalloc((void**)&d, sizeof(cx<float>) * m));
         PF_CHECK(hipMemcpy(d, tw.data(), sizeof(cx<float>) * m, hipMemcpyHostToDevice));
         it = tabs.emplace(key, d).first;
@@ -57,24 +51,24 @@ static int split_sub_table(const cx<float>** out, int m = 1024) {
 
 template <int W>
 static int fir_split1(Setup* ps, const float* d_Hc, const float* d_x, float* d_y, int nblk, int step, int inputLen, int lastOut,
-                      hipStream_t st, const FcBatch& fb, void** ab_cache) {
+                      hipStream_t st, const FcBatch& fb, DevBuf& ab_cache) {
     typedef SplitOneT<W> S;
     ps = for_device(ps);
     auto k = fastconv_split1_kernel<W>;
     int rc = allow_big_lds(k, S::LDS_BYTES);
     if (rc) return rc;
-    if (!*ab_cache) {
+    if (!ab_cache) {
         // the folded coefficients of this filter: built ONCE and COMPLETE before the pointer is published - null stream + synchronisation,
         // like every other lazily built table (fc_ensure_big, split_sub_table).  Built on the caller's stream (round 4) a second call on
         // another non-blocking stream saw the pointer set and could read a half-written table: the setup's mutex orders hosts, not streams.
-        void* ab = nullptr;
-        PF_CHECK(hipMalloc(&ab, sizeof(float) * 4 * (size_t)S::n));
-        hipLaunchKernelGGL(fastconv_split1_coef_kernel<W>, dim3(1), dim3(S::WG), 0, nullptr, (const cx<float>*)d_Hc, (const cx<float>*)ps->d_twr,
-                           (vec4<float>*)ab);
+        DevBuf ab;
+        if ((rc = ab.grow(sizeof(float) * 4 * (size_t)S::n))) return rc;
+        hipLaunchKernelGGL(fastconv_split1_coef_kernel<W>, dim3(1), dim3(S::WG), 0, nullptr, (const cx<float>*)d_Hc, ps->d_twr.as<cx<float>>(),
+                           ab.as<vec4<float>>());
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-        if (e != hipSuccess) { (void)hipFree(ab); return fail(e, "fastconv_split1_coef_kernel"); }
-        *ab_cache = ab;
+        if (e != hipSuccess) return fail(e, "fastconv_split1_coef_kernel");
+        ab_cache = std::move(ab);
     }
     const cx<float>* tw512 = nullptr;
     if ((rc = split_sub_table(&tw512, S::M))) return rc;
@@ -83,8 +77,8 @@ static int fir_split1(Setup* ps, const float* d_Hc, const float* d_x, float* d_y
     const size_t groups = (size_t)nblk * fb.nsig;
     size_t grid = (size_t)num_cus() * per_cu;
     if (grid > groups) grid = groups;
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(S::WG), S::LDS_BYTES, st, d_x, d_y, (const vec4<float>*)*ab_cache, nblk, step, inputLen,
-                       lastOut, (const cx<float>*)ps->d_tw, tw512, fb.nsig, fb.xstride, fb.ystride, env().fir_xcd);
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(S::WG), S::LDS_BYTES, st, d_x, d_y, ab_cache.as<vec4<float>>(), nblk, step, inputLen,
+                       lastOut, ps->d_tw.as<cx<float>>(), tw512, fb.nsig, fb.xstride, fb.ystride, env().fir_xcd);
     PF_CHECK(hipGetLastError());
     return 0;
 }
@@ -92,7 +86,7 @@ static int fir_split1(Setup* ps, const float* d_Hc, const float* d_x, float* d_y
 // calls with few blocks on reference-sized blocks of 2 ps->n samples: W wavefronts x 512-point wave-local transforms (fft_split.h);
 // -1: no such kernel for this length
 int launch_fir_split1(Setup* ps, const float* d_Hc, const float* d_x, float* d_y, int nblk, int step, int inputLen, int lastOut,
-                      hipStream_t st, const FcBatch& fb, void** ab_cache) {
+                      hipStream_t st, const FcBatch& fb, DevBuf& ab_cache) {
     switch (ps->n) {
         case 4096: return fir_split1<8>(ps, d_Hc, d_x, d_y, nblk, step, inputLen, lastOut, st, fb, ab_cache);
         case 2048: return fir_split1<4>(ps, d_Hc, d_x, d_y, nblk, step, inputLen, lastOut, st, fb, ab_cache);
@@ -119,30 +113,29 @@ static int fir_split(Setup* ps, const float* d_Hc, const float* d_x, float* d_y,
     const int xmode = (env().fir_xcd && grid >= 8 && groups < 0xfffffff0ull) ? 1 : 0;
     unsigned* ctr = groups <= grid ? nullptr : take_counters(ps, st, xmode ? 5 : 1);   // (per-XCD counters: nine words)
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(S::WG), S::LDS_BYTES, st, d_x, d_y, (const cx<float>*)d_Hc,
-                       nblk, step, inputLen, lastOut, (const cx<float>*)ps->d_tw, tw1024, (const cx<float>*)ps->d_twr, ctr,
+                       nblk, step, inputLen, lastOut, ps->d_tw.as<cx<float>>(), tw1024, ps->d_twr.as<cx<float>>(), ctr,
                        fb.nsig, fb.xstride, fb.ystride, xmode);
     PF_CHECK(hipGetLastError());
     return 0;
 }
 
 // 16384-sample blocks on 256 threads, 32 points per thread (fft_fir32.h).  hp_cache: the thread-major copy of the filter spectrum, built
-// once per filter - on the null stream and COMPLETE before the pointer is published, like every lazily built table - and owned by
-// the caller's pffastconv setup (hipFree)
+// once per filter - on the null stream and COMPLETE before it is moved into the caller's pffastconv setup, like every lazily built table
 template <int PREF>
 static int fir32(Setup* ps, const float* d_Hc, const float* d_x, float* d_y, int nblk, int step, int inputLen, int lastOut,
-                 hipStream_t st, const FcBatch& fb, void** hp_cache) {
+                 hipStream_t st, const FcBatch& fb, DevBuf& hp_cache) {
     ps = for_device(ps);
     auto k = fastconv_fused32_kernel<PREF>;
     int rc = allow_big_lds(k, Fir32::LDS_BYTES);
     if (rc) return rc;
-    if (!*hp_cache) {
-        void* hp = nullptr;
-        PF_CHECK(hipMalloc(&hp, sizeof(float) * 4 * (size_t)Fir32::n));
-        hipLaunchKernelGGL(fir32_coef_kernel, dim3(1), dim3(Fir32::WG), 0, nullptr, (const cx<float>*)d_Hc, (const cx<float>*)ps->d_twr, (vec4<float>*)hp);
+    if (!hp_cache) {
+        DevBuf hp;
+        if ((rc = hp.grow(sizeof(float) * 4 * (size_t)Fir32::n))) return rc;
+        hipLaunchKernelGGL(fir32_coef_kernel, dim3(1), dim3(Fir32::WG), 0, nullptr, (const cx<float>*)d_Hc, ps->d_twr.as<cx<float>>(), hp.as<vec4<float>>());
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-        if (e != hipSuccess) { (void)hipFree(hp); return fail(e, "fir32_coef_kernel"); }
-        *hp_cache = hp;
+        if (e != hipSuccess) return fail(e, "fir32_coef_kernel");
+        hp_cache = std::move(hp);
     }
     int per_cu = 0;
     if ((rc = cached_occupancy(reinterpret_cast<const void*>(k), Fir32::WG, Fir32::LDS_BYTES, &per_cu))) return rc;
@@ -152,14 +145,14 @@ static int fir32(Setup* ps, const float* d_Hc, const float* d_x, float* d_y, int
     // (the per-XCD ranges need every XCD to have a workgroup: ADVICE r05)
     const int xmode = (env().fir_xcd && grid >= 8 && groups < 0xfffffff0ull) ? 1 : 0;
     unsigned* ctr = groups <= grid ? nullptr : take_counters(ps, st, xmode ? 5 : 1);
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(Fir32::WG), Fir32::LDS_BYTES, st, d_x, d_y, (const vec4<float>*)*hp_cache,
-                       nblk, step, inputLen, lastOut, (const cx<float>*)ps->d_tw, (const cx<float>*)ps->d_twr, ctr,
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(Fir32::WG), Fir32::LDS_BYTES, st, d_x, d_y, hp_cache.as<vec4<float>>(),
+                       nblk, step, inputLen, lastOut, ps->d_tw.as<cx<float>>(), ps->d_twr.as<cx<float>>(), ctr,
                        fb.nsig, fb.xstride, fb.ystride, xmode);
     PF_CHECK(hipGetLastError());
     return 0;
 }
 int launch_fir32(Setup* ps, const float* d_Hc, const float* d_x, float* d_y, int nblk, int step, int inputLen, int lastOut,
-                 hipStream_t st, const FcBatch& fb, void** hp_cache, int pref) {
+                 hipStream_t st, const FcBatch& fb, DevBuf& hp_cache, int pref) {
     if (ps->n != Fir32::n) return -1;
     if (pref == 2) return fir32<2>(ps, d_Hc, d_x, d_y, nblk, step, inputLen, lastOut, st, fb, hp_cache);
 #ifdef PFFFT_HIP_VARIANTS

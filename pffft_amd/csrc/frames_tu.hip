@@ -94,7 +94,7 @@ static int launch_frames_fused(Setup* s, const FramesSel& e, const float* signal
     if (grid > groups) grid = groups;
     unsigned* ctr = groups <= grid ? nullptr : take_counters(s, st);
     hipLaunchKernelGGL(e.fn, dim3((unsigned)grid), dim3(e.wg), e.lds, st, signal, signal_stride, (unsigned)nframes, hop, window, out,
-                       out_stride, (unsigned)batch, (const cx<float>*)s->d_tw, (const cx<float>*)s->d_twr, ctr);
+                       out_stride, (unsigned)batch, s->d_tw.as<cx<float>>(), s->d_twr.as<cx<float>>(), ctr);
     PF_CHECK(hipGetLastError());
     return 0;
 }
@@ -104,16 +104,14 @@ static unsigned stream_grid(size_t items) {
     return (unsigned)std::max<size_t>(1, std::min<size_t>((items + 255) / 256, (size_t)num_cus() * 16));
 }
 
-// the frame matrix of `st` (frames_mu held by the caller), grown to `bytes`: outside graph capture only
+// the frame matrix of `st` (frames.mu held by the caller), grown to `bytes`: outside graph capture only
 static int frames_buffer(Setup* s, hipStream_t st, size_t bytes, void** buf) {
-    Setup::Scratch* sc = nullptr;
-    int rc = stream_scratch(s->frames_scratch, s->frames_clock, st, &sc);
-    if (rc) return rc;
-    if (sc->bytes[0] < bytes && stream_capturing(st))
+    StreamScratch::Entry& sc = s->frames.acquire(st);
+    if (sc.buf[0].bytes() < bytes && stream_capturing(st))
         return bad("the frame matrix of this stream would have to grow during graph capture: run the call once on this stream before capturing",
                    hipErrorStreamCaptureUnsupported);
-    if ((rc = scratch_grow(s, *sc, 0, bytes))) return rc;
-    *buf = sc->buf[0];
+    if (int rc = s->frames.grow(sc, 0, bytes)) return rc;
+    *buf = sc.buf[0].get();
     return 0;
 }
 
@@ -182,7 +180,7 @@ static int frames_transform_batch(Setup* s, const T* signal, size_t signal_strid
     // the dense spectrum
     const size_t chunk = std::max<size_t>(1, std::min(batch, FRAMES_CAP_BYTES / (row * sizeof(T))));
     const bool direct = output != FR_POWER && out_stride == row;
-    std::lock_guard<std::mutex> lk(s->frames_mu);
+    std::lock_guard<std::mutex> lk(s->frames.mu);
     void* buf = nullptr;
     if ((rc = frames_buffer(s, st, chunk * row * sizeof(T), &buf))) return rc;
     T* X = (T*)buf;
@@ -249,7 +247,7 @@ static int frames_overlap_add_batch(Setup* s, const T* spectra, size_t spectra_s
     s = for_device(s);
     if ((rc = ensure_device_any(s))) return rc;
     const size_t batch = nsignals * nframes, cap_rows = std::max<size_t>(1, FRAMES_CAP_BYTES / (row * sizeof(T)));
-    std::lock_guard<std::mutex> lk(s->frames_mu);
+    std::lock_guard<std::mutex> lk(s->frames.mu);
     void* buf = nullptr;
     if (batch <= cap_rows) {   // every frame at once, one gather
         if ((rc = frames_buffer(s, st, batch * row * sizeof(T), &buf))) return rc;

@@ -130,8 +130,8 @@ static int launch_one_t(Setup* s, const T* in, T* out, size_t batch, int dir, in
     if (grid > batch) grid = batch;
     // in order from the counter (one grab per 80-144 KiB vector); a launch that the resident workgroups cover in one go needs none
     unsigned* ctr = (batch > grid && batch < 0xfffffff0ull) ? take_counters(s, st, 1) : nullptr;
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(ONE_WG), lds, st, in, out, batch, p, (const cx<T>*)(pi == 2 ? s->d_one_tw2 : s->d_twc[pi]),
-                       (const cx<T>*)s->d_twr, ctr);
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(ONE_WG), lds, st, in, out, batch, p, (pi == 2 ? s->d_one_tw2 : s->d_twc[pi]).as<cx<T>>(),
+                       s->d_twr.as<cx<T>>(), ctr);
     PF_CHECK(hipGetLastError());
     return 0;
 }

@@ -18,6 +18,7 @@
 #include "fft_big.h"
 #include "stock_plan.h"
 #include "pf_route.h"
+#include "pf_devmem.h"
 
 namespace pf {
 
@@ -69,7 +70,7 @@ struct Setup {
     // single-image plan (fft_one.h, round 6): the sizes that fill LDS once but not twice - [0] forward, [1] backward
     StockPlan one[3];          // [2]: the float complex backward transform from the internal layout (fft_one.h NARROW: no two-trip middle stages)
     bool one_ok = false;
-    void* d_one_tw2 = nullptr; // compact twiddles of one[2]
+    DevBuf d_one_tw2;          // compact twiddles of one[2]
     // device state (lazy: creating a setup never touches the GPU)
     std::mutex mu;        // guards the lazy device initialisation
     std::mutex stage_mu;  // guards the staging buffers of the legacy host-pointer entries
@@ -80,39 +81,26 @@ struct Setup {
     std::atomic<int> device{-1};
     std::map<int, Setup*> replicas;   // (under mu) device key -> replica; owned, destroyed with the setup
     bool is_replica = false;
-    void* d_tw = nullptr;   // W_n^j, j < n
-    void* d_twr = nullptr;  // W_N^k, k <= n/2 (real only)
-    void* d_twc[2] = {nullptr, nullptr};  // compact per-stage base twiddles of the Stockham plans (forward / backward order)
-    unsigned* d_ctr = nullptr;             // ring of {next, done} work counters for the dynamic kernels (+ the captured region behind it)
+    // (every table, scratch and staging buffer below is a DevBuf / PinnedBuf / StreamScratch of pf_devmem.h: freed with the object)
+    DevBuf d_tw;      // W_n^j, j < n
+    DevBuf d_twr;     // W_N^k, k <= n/2 (real only)
+    DevBuf d_twc[2];  // compact per-stage base twiddles of the Stockham plans (forward / backward order)
+    DevBuf d_ctr;     // ring of {next, done} work counters for the dynamic kernels (+ the captured region behind it)
     std::atomic<unsigned> ctr_slot{0}, cap_slot{0};
     // sizes beyond LDS with a small factor (fft_big.h, three streaming passes): n = bigR x sub->n
     int bigR = 0;
     Setup* sub = nullptr;
     // sizes beyond LDS (K_BIG): n = bigN[0] x bigN[1], one strided plan + twiddle table per factor
     StridedPlan bigp[2];
-    void* d_bigtw[2] = {nullptr, nullptr};
-    // HBM work buffers of the beyond-LDS path: one pair PER STREAM (kernels of one stream serialise; two streams running
-    // the same setup concurrently must not share scratch).  big_mu is held while a call enqueues its passes (launch_big).
-    // captured: a launch using these buffers was recorded into a HIP graph - a replay dereferences the pointers it froze, so such an
-    // entry is never evicted and a buffer it outgrows is retired (freed with the setup) instead of freed
-    struct Scratch { void* buf[2] = {nullptr, nullptr}; size_t bytes[2] = {0, 0}; unsigned long long last_use = 0; bool captured = false; };
-    std::mutex retired_mu;
-    std::vector<void*> retired;
-    unsigned long long scratch_clock = 0;      // (under big_mu) orders the streams' last uses: the idlest one is evicted first
-    std::mutex big_mu;
-    std::map<hipStream_t, Scratch> big_scratch;
-    // spectrum image of the composed pffft_hip_convolve_batch route: one per stream, conv_mu held while a call enqueues
-    std::mutex conv_mu;
-    std::map<hipStream_t, Scratch> conv_scratch;
-    unsigned long long conv_clock = 0;
-    // frame matrix of the composed pffft_hip_frames_* routes (frames_tu.hip): one per stream, frames_mu held while a call enqueues
-    std::mutex frames_mu;
-    std::map<hipStream_t, Scratch> frames_scratch;
-    unsigned long long frames_clock = 0;
-    void* d_stage[3] = {nullptr, nullptr, nullptr};  // staging for host-pointer legacy calls
-    size_t stage_bytes[3] = {0, 0, 0};
-    void* h_stage[4] = {nullptr, nullptr, nullptr, nullptr};  // pinned host images the kernels read / write directly (small vectors)
-    size_t hstage_bytes[4] = {0, 0, 0, 0};
+    DevBuf d_bigtw[2];
+    // HBM work buffers of the beyond-LDS path: one pair per stream, big.mu held while a call enqueues its passes (launch_big)
+    StreamScratch big;
+    // spectrum image of the composed pffft_hip_convolve_batch route: one per stream, conv.mu held while a call enqueues
+    StreamScratch conv;
+    // frame matrix of the composed pffft_hip_frames_* routes (frames_tu.hip): one per stream, frames.mu held while a call enqueues
+    StreamScratch frames;
+    DevBuf d_stage[3];     // staging for host-pointer legacy calls
+    PinnedBuf h_stage[4];  // pinned host images the kernels read / write directly (small vectors)
 };
 constexpr uint32_t MAGIC = 0x50464654u;  // "PFFT"
 
@@ -132,10 +120,6 @@ Setup* for_device(Setup* s);
 // devices `s` holds state on right now (its own binding first): fills out[0 .. max), returns the count (pffft_hip_setup_devices)
 int setup_devices(Setup* s, int* out, int max);
 
-// pffft_hip.hip: the per-stream scratch of a setup (held under the lock of the table it lives in) - the entry of `st`, created on first use
-// (the stream that used the setup longest ago makes room), and buffer i of it grown to `bytes` (outside graph capture only)
-int stream_scratch(std::map<hipStream_t, Setup::Scratch>& tab, unsigned long long& clock, hipStream_t st, Setup::Scratch** out);
-int scratch_grow(Setup* s, Setup::Scratch& sc, int i, size_t bytes);
 // pffft_hip.hip, for frames_tu.hip: pffft(d)_hip_transform_batch on a checked setup, and the lazy device initialisation of a resolved one
 int transform_batch_any(Setup* s, const void* in, void* out, size_t batch, int dir, int ordered, hipStream_t st);
 int ensure_device_any(Setup* s);
@@ -148,7 +132,7 @@ int launch_fir_dma(Setup* ps, const float* d_Hc, const float* d_x, float* d_y, i
 
 // dma_tu.hip: 16384-sample FIR blocks on 256 threads with 32 points per thread (fft_fir32.h); -1: not this block length
 int launch_fir32(Setup* ps, const float* d_Hc, const float* d_x, float* d_y, int nblk, int step, int inputLen, int lastOut,
-                 hipStream_t st, const FcBatch& fb, void** hp_cache, int pref);
+                 hipStream_t st, const FcBatch& fb, DevBuf& hp_cache, int pref);
 
 // tile_real_tu.hip: REAL transforms beyond LDS in two sweeps (fft_tile.h RMODE): N real points -> canonical half spectrum through a
 // work buffer of tile_rfft_work_elems(N) complex elements per vector; -1: no plan for this length / direction
@@ -166,9 +150,9 @@ const void* one_kernel_ptr(bool is_double, int flags);
 int launch_conv_fused(Setup* s, const void* in, const void* H, void* out, size_t batch, double scaling, int accumulate, hipStream_t st);
 
 // dma_tu.hip: few-block calls on reference-sized blocks (fft_split.h fastconv_split1_kernel); -1: no such kernel for this length
-// (ab_cache: the filter's folded coefficient table, built on first use and owned by the caller's pffastconv setup: hipFree)
+// (ab_cache: the filter's folded coefficient table, built on first use into the caller's pffastconv setup)
 int launch_fir_split1(Setup* ps, const float* d_Hc, const float* d_x, float* d_y, int nblk, int step, int inputLen, int lastOut,
-                      hipStream_t st, const FcBatch& fb, void** ab_cache);
+                      hipStream_t st, const FcBatch& fb, DevBuf& ab_cache);
 
 // tile_tu.hip: power-of-two sizes beyond LDS in two / three passes (fft_tile.h); canonical complex, in -> out through `work`
 // (same size, distinct from both; in may equal out).  -1 when the size has no tile plan.  layout 3 (round 6, forward only, the complex core

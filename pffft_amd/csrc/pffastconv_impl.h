@@ -22,26 +22,21 @@ struct FastConv {
     std::mutex mu;
     bool ready = false;     // set only after EVERY step of fc_ensure_device succeeded
     int device = -1;
-    float* d_Hf = nullptr;
-    float* d_Hc = nullptr;  // canonical-order filter spectrum * 1/Nfft for the fused kernel
+    // (device tables, work images and staging: DevBuf / PinnedBuf / StreamScratch of pf_devmem.h, freed with the setup)
+    DevBuf d_Hf;
+    DevBuf d_Hc;  // canonical-order filter spectrum * 1/Nfft for the fused kernel
     // throughput regime (many blocks): the same outputs through LARGER internal blocks (better overlap-save efficiency)
-    PFFFT_Setup* st_big = nullptr; float* d_Hc_big = nullptr; int Nfft_big = 0;
+    PFFFT_Setup* st_big = nullptr; DevBuf d_Hc_big; int Nfft_big = 0;
     // partitioned path (fft_fir.h fastconv_part_kernel): P spectra of 1024-tap partitions on 2048-sample blocks
-    PFFFT_Setup* st_part = nullptr; float* d_Hp = nullptr; int part_P = 0;
+    PFFFT_Setup* st_part = nullptr; DevBuf d_Hp; int part_P = 0;
     std::vector<float> h_td;  // y[m] = sum_i h_td[i] x[m + i]: the filter as the time-domain kernel applies it (zero padded to 8)
-    float* d_td = nullptr;
-    void* d_fir32_hp = nullptr;    // thread-major filter spectrum of the 32-points-per-thread block kernel (fft_fir32.h), of d_Hc_big
-    void* d_fir32_hp_ref = nullptr;   // ... of d_Hc (filters whose reference block length is 16384 samples itself)
-    void* d_split1_ab = nullptr;   // folded per-bin coefficients of the few-block split kernel (fft_split.h), built on first use
-    // work image of the composed path: one per stream (two streams running one setup must not share scratch)
-    struct Work { float* p = nullptr; size_t floats = 0; unsigned long long last_use = 0; bool captured = false; };   // captured: pf_host.h Scratch
-    std::vector<float*> retired;
-    unsigned long long work_clock = 0;
-    std::map<hipStream_t, Work> work;
-    float* d_x = nullptr; size_t x_floats = 0;   // staging of pffastconv_apply's host pointers (large signals)
-    float* d_y = nullptr; size_t y_floats = 0;
-    float* h_x = nullptr; size_t hx_floats = 0;  // pinned host images the kernels read / write directly (zero copy)
-    float* h_y = nullptr; size_t hy_floats = 0;
+    DevBuf d_td;
+    DevBuf d_fir32_hp;       // thread-major filter spectrum of the 32-points-per-thread block kernel (fft_fir32.h), of d_Hc_big
+    DevBuf d_fir32_hp_ref;   // ... of d_Hc (filters whose reference block length is 16384 samples itself)
+    DevBuf d_split1_ab;      // folded per-bin coefficients of the few-block split kernel (fft_split.h), built on first use
+    StreamScratch work;      // work image of the composed path (buf[0]): one per stream; FastConv::mu is the lock its callers hold
+    DevBuf d_x, d_y;         // staging of pffastconv_apply's host pointers (large signals)
+    PinnedBuf h_x, h_y;      // pinned host images the kernels read / write directly (zero copy)
 };
 constexpr uint32_t FC_MAGIC = 0x46434e56u;
 
@@ -139,43 +134,29 @@ fastconv_td_kernel(const float* __restrict__ x, float* __restrict__ y, const flo
     }
 }
 
-static int fc_grow(float** p, size_t* have, size_t want) {
-    if (*have >= want) return 0;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr; *have = 0;
-    PF_CHECK(hipMalloc((void**)p, want * sizeof(float)));
-    *have = want;
-    return 0;
-}
-
-static void fc_free_device(FastConv* s) {
-    for (float** p : {&s->d_Hf, &s->d_Hc}) if (*p) { (void)hipFree(*p); *p = nullptr; }
-}
-
 // everything this setup holds on its device: the filter tables of every route, per-stream work images, staging (not the pinned host
 // images, not the inner pffft setups - those keep state per device themselves, for_device)
 static void fc_release_device(FastConv* s) {
-    fc_free_device(s);
-    for (float** p : {&s->d_Hc_big, &s->d_Hp, &s->d_td, &s->d_x, &s->d_y}) if (*p) { (void)hipFree(*p); *p = nullptr; }
-    for (void** p : {&s->d_split1_ab, &s->d_fir32_hp, &s->d_fir32_hp_ref}) if (*p) { (void)hipFree(*p); *p = nullptr; }
-    for (auto& kv : s->work) if (kv.second.p) (void)hipFree(kv.second.p);
+    for (DevBuf* b : {&s->d_Hf, &s->d_Hc, &s->d_Hc_big, &s->d_Hp, &s->d_td, &s->d_split1_ab, &s->d_fir32_hp, &s->d_fir32_hp_ref, &s->d_x, &s->d_y})
+        b->reset();
     s->work.clear();
-    for (float* p : s->retired) if (p) (void)hipFree(p);
-    s->retired.clear();
-    s->Nfft_big = 0; s->part_P = 0; s->x_floats = 0; s->y_floats = 0;
+    s->Nfft_big = 0; s->part_P = 0;
     s->ready = false;
 }
 
 static int fc_init_device(FastConv* s) {
-    PF_CHECK(hipMalloc((void**)&s->d_Hf, sizeof(float) * s->Nfft));
-    PF_CHECK(hipMemcpy(s->d_Hf, s->h_filter_image.data(), sizeof(float) * s->Nfft, hipMemcpyHostToDevice));
-    int rc = transform_batch<float>(s->st, s->d_Hf, s->d_Hf, 1, PFFFT_FORWARD, 0, nullptr);  // :108
+    int rc = s->d_Hf.grow(sizeof(float) * s->Nfft);
+    if (rc) return rc;
+    float* const Hf = s->d_Hf.as<float>();
+    PF_CHECK(hipMemcpy(Hf, s->h_filter_image.data(), sizeof(float) * s->Nfft, hipMemcpyHostToDevice));
+    rc = transform_batch<float>(s->st, Hf, Hf, 1, PFFFT_FORWARD, 0, nullptr);  // :108
     if (rc) return rc;
     // fused path: canonical order (pffft_zreorder) and the 1/Nfft scale folded into the table
-    PF_CHECK(hipMalloc((void**)&s->d_Hc, sizeof(float) * s->Nfft));
-    rc = zreorder_batch<float>(s->st, s->d_Hf, s->d_Hc, 1, PFFFT_FORWARD, nullptr);
+    if ((rc = s->d_Hc.grow(sizeof(float) * s->Nfft))) return rc;
+    float* const Hc = s->d_Hc.as<float>();
+    rc = zreorder_batch<float>(s->st, Hf, Hc, 1, PFFFT_FORWARD, nullptr);
     if (rc) return rc;
-    hipLaunchKernelGGL(fastconv_scale_kernel, dim3(64), dim3(256), 0, nullptr, s->d_Hc, s->d_Hc, s->Nfft, s->scale);
+    hipLaunchKernelGGL(fastconv_scale_kernel, dim3(64), dim3(256), 0, nullptr, Hc, Hc, s->Nfft, s->scale);
     PF_CHECK(hipGetLastError());
     PF_CHECK(hipStreamSynchronize(nullptr));
     return 0;
@@ -194,7 +175,7 @@ static int fc_ensure_device(FastConv* s) {
         fc_release_device(s);
     }
     rc = fc_init_device(s);
-    if (rc) { fc_free_device(s); return rc; }   // a later call starts over instead of launching on half-built tables
+    if (rc) { s->d_Hf.reset(); s->d_Hc.reset(); return rc; }   // a later call (on whatever device) starts over instead of launching on half-built tables
     s->device = dev;
     s->ready = true;
     return 0;
@@ -212,10 +193,10 @@ static int fc_launch_fused(FastConv* s, const float* d_x, float* d_y, int nblk, 
     size_t grid = (size_t)num_cus() * per_cu;
     if (grid > groups) grid = groups;
     Setup* ps = for_device(pst ? pst : s->st);
-    if (!d_Hc) d_Hc = s->d_Hc;
+    if (!d_Hc) d_Hc = s->d_Hc.as<float>();
     unsigned* ctr = groups <= grid ? nullptr : take_counters(ps, st);
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(C::WG_THREADS), C::LDS_BYTES, st, d_x, d_y, (const cx<float>*)d_Hc,
-                       nblk, step, inputLen, lastOut, (const cx<float>*)ps->d_tw, (const cx<float>*)ps->d_twr, ctr,
+                       nblk, step, inputLen, lastOut, ps->d_tw.as<cx<float>>(), ps->d_twr.as<cx<float>>(), ctr,
                        fb.nsig, fb.xstride, fb.ystride);
     PF_CHECK(hipGetLastError());
     return 0;
@@ -254,25 +235,27 @@ static int fc_big_nfft(const FastConv* s, long produced, int nsig) {
 static int fc_ensure_big(FastConv* s, int Nfft_big) {
     if (s->Nfft_big == Nfft_big) return 0;
     if (s->st_big) { pffft_destroy_setup(s->st_big); s->st_big = nullptr; }
-    if (s->d_Hc_big) { (void)hipFree(s->d_Hc_big); s->d_Hc_big = nullptr; }
-    if (s->d_fir32_hp) { (void)hipFree(s->d_fir32_hp); s->d_fir32_hp = nullptr; }
+    s->d_Hc_big.reset();
+    s->d_fir32_hp.reset();
     s->Nfft_big = 0;
     s->st_big = pffft_new_setup(Nfft_big, PFFFT_REAL);
     if (!s->st_big) { g_last_error = "pffastconv: internal setup failed"; return (int)hipErrorInvalidValue; }
     std::vector<float> img((size_t)Nfft_big, 0.f);
     const int flen = s->filterLen;
     for (int i = 0; i < flen; ++i) img[(Nfft_big - i) & (Nfft_big - 1)] = s->h_td[i];   // :100-106 with the longer block
-    float* d_tmp = nullptr;
-    PF_CHECK(hipMalloc((void**)&d_tmp, sizeof(float) * Nfft_big));
-    PF_CHECK(hipMalloc((void**)&s->d_Hc_big, sizeof(float) * Nfft_big));
+    DevBuf tmp;
+    int rc = tmp.grow(sizeof(float) * Nfft_big);
+    if (!rc) rc = s->d_Hc_big.grow(sizeof(float) * Nfft_big);
+    if (rc) return rc;
+    float* const d_tmp = tmp.as<float>();
+    float* const Hc = s->d_Hc_big.as<float>();
     PF_CHECK(hipMemcpy(d_tmp, img.data(), sizeof(float) * Nfft_big, hipMemcpyHostToDevice));
-    int rc = transform_batch<float>(s->st_big, d_tmp, d_tmp, 1, PFFFT_FORWARD, 0, nullptr);
-    if (!rc) rc = zreorder_batch<float>(s->st_big, d_tmp, s->d_Hc_big, 1, PFFFT_FORWARD, nullptr);
+    rc = transform_batch<float>(s->st_big, d_tmp, d_tmp, 1, PFFFT_FORWARD, 0, nullptr);
+    if (!rc) rc = zreorder_batch<float>(s->st_big, d_tmp, Hc, 1, PFFFT_FORWARD, nullptr);
     if (!rc) {
-        hipLaunchKernelGGL(fastconv_scale_kernel, dim3(64), dim3(256), 0, nullptr, s->d_Hc_big, s->d_Hc_big, Nfft_big, 1.0f / (float)Nfft_big);
+        hipLaunchKernelGGL(fastconv_scale_kernel, dim3(64), dim3(256), 0, nullptr, Hc, Hc, Nfft_big, 1.0f / (float)Nfft_big);
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) rc = (int)hipErrorUnknown;
     }
-    (void)hipFree(d_tmp);
     if (rc) return rc;
     s->Nfft_big = Nfft_big;
     return 0;
@@ -289,19 +272,21 @@ static int fc_ensure_part(FastConv* s) {
     // correlation image of partition p (src/pffastconv.c:100-106 with the partition's taps): g[(Nfft - i) mod Nfft] = c[pB + i]
     std::vector<float> img((size_t)P * Nfft, 0.f);
     for (int i = 0; i < s->filterLen; ++i) img[(size_t)(i / PART_B) * Nfft + ((Nfft - i % PART_B) & (Nfft - 1))] = s->h_td[i];
-    float* d_tmp = nullptr;
-    if (s->d_Hp) { (void)hipFree(s->d_Hp); s->d_Hp = nullptr; s->part_P = 0; }
-    PF_CHECK(hipMalloc((void**)&d_tmp, sizeof(float) * P * Nfft));
-    PF_CHECK(hipMalloc((void**)&s->d_Hp, sizeof(float) * P * Nfft));
+    s->d_Hp.reset(); s->part_P = 0;
+    DevBuf tmp;
+    int rc = tmp.grow(sizeof(float) * P * Nfft);
+    if (!rc) rc = s->d_Hp.grow(sizeof(float) * P * Nfft);
+    if (rc) return rc;
+    float* const d_tmp = tmp.as<float>();
+    float* const Hp = s->d_Hp.as<float>();
     PF_CHECK(hipMemcpy(d_tmp, img.data(), sizeof(float) * P * Nfft, hipMemcpyHostToDevice));
-    int rc = transform_batch<float>(s->st_part, d_tmp, d_tmp, P, PFFFT_FORWARD, 0, nullptr);
-    if (!rc) rc = zreorder_batch<float>(s->st_part, d_tmp, s->d_Hp, P, PFFFT_FORWARD, nullptr);
+    rc = transform_batch<float>(s->st_part, d_tmp, d_tmp, P, PFFFT_FORWARD, 0, nullptr);
+    if (!rc) rc = zreorder_batch<float>(s->st_part, d_tmp, Hp, P, PFFFT_FORWARD, nullptr);
     if (!rc) {
-        hipLaunchKernelGGL(fastconv_scale_kernel, dim3(64), dim3(256), 0, nullptr, s->d_Hp, s->d_Hp, P * Nfft, 1.0f / (float)Nfft);
+        hipLaunchKernelGGL(fastconv_scale_kernel, dim3(64), dim3(256), 0, nullptr, Hp, Hp, P * Nfft, 1.0f / (float)Nfft);
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) rc = (int)hipErrorUnknown;
     }
-    (void)hipFree(d_tmp);
-    if (rc) { (void)hipFree(s->d_Hp); s->d_Hp = nullptr; return rc; }
+    if (rc) { s->d_Hp.reset(); return rc; }
     s->part_P = P;
     return 0;
 }
@@ -332,8 +317,8 @@ static int fc_launch_part(FastConv* s, const float* d_x, float* d_y, long produc
     long grid = (ntask + C::T_PER_WG - 1) / C::T_PER_WG;
     if (grid > (long)num_cus() * per_cu) grid = (long)num_cus() * per_cu;
     Setup* ps = for_device(s->st_part);
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(C::WG_THREADS), lds, st, d_x, d_y, (const cx<float>*)s->d_Hp, nblk, inputLen,
-                       lastOut, (int)kchunk, (const cx<float>*)ps->d_tw, (const cx<float>*)ps->d_twr, fb.nsig, fb.xstride, fb.ystride);
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(C::WG_THREADS), lds, st, d_x, d_y, s->d_Hp.as<cx<float>>(), nblk, inputLen,
+                       lastOut, (int)kchunk, ps->d_tw.as<cx<float>>(), ps->d_twr.as<cx<float>>(), fb.nsig, fb.xstride, fb.ystride);
     PF_CHECK(hipGetLastError());
     return 0;
 }
@@ -359,8 +344,8 @@ static int fc_launch_wave(FastConv* s, const float* d_x, float* d_y, long produc
     long grid = (ntask + C::T_PER_WG - 1) / C::T_PER_WG;
     if (grid > (long)num_cus() * per_cu) grid = (long)num_cus() * per_cu;
     Setup* ps = for_device(s->st_part);
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(C::WG_THREADS), lds, st, d_x, d_y, (const cx<float>*)s->d_Hp, nblk, step, inputLen,
-                       lastOut, (int)kchunk, (const cx<float>*)ps->d_tw, (const cx<float>*)ps->d_twr, fb.nsig, fb.xstride, fb.ystride);
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(C::WG_THREADS), lds, st, d_x, d_y, s->d_Hp.as<cx<float>>(), nblk, step, inputLen,
+                       lastOut, (int)kchunk, ps->d_tw.as<cx<float>>(), ps->d_twr.as<cx<float>>(), fb.nsig, fb.xstride, fb.ystride);
     PF_CHECK(hipGetLastError());
     return 0;
 }
@@ -457,19 +442,19 @@ static int fc_apply_device(FastConv* s, const float* d_x, int cplxInputLen, floa
             // 16384-sample blocks: 256 threads, 32 points per thread, four exchanges per block (fft_fir32.h, round 6); AB_FIR_SPLIT: the split
             // kernel it replaced (fft_split.h: the second route of tests/test_gpu_round6.py), development build: AB_FIR_LOCKSTEP / AB_FIR_SPLIT_PLAIN
             if (nbig == 16384 && !sel.is(AB_FIR_SPLIT) && !sel.is(AB_FIR_LOCKSTEP) && !sel.is(AB_FIR_SPLIT_PLAIN)) {
-                rc = launch_fir32(s->st_big, s->d_Hc_big, d_x, d_y, bblk, bstep, inputLen, blast, st, fb, &s->d_fir32_hp,
+                rc = launch_fir32(s->st_big, s->d_Hc_big.as<float>(), d_x, d_y, bblk, bstep, inputLen, blast, st, fb, s->d_fir32_hp,
                                   sel.is(AB_FIR_FUSED32_PF1) ? 1 : sel.is(AB_FIR_FUSED32_NOPF) ? 0 : 2);
                 if (rc != -1) return rc;
             }
             if (nbig == 16384) {
-                rc = launch_fir_dma(s->st_big, s->d_Hc_big, d_x, d_y, bblk, bstep, inputLen, blast, st, fb);
+                rc = launch_fir_dma(s->st_big, s->d_Hc_big.as<float>(), d_x, d_y, bblk, bstep, inputLen, blast, st, fb);
                 if (rc != -1) return rc;
             }
             switch (nbig / 2) {
-                case 1024: return fc_launch_fused<FirCfg::C1024>(s, d_x, d_y, bblk, bstep, inputLen, blast, st, fb, s->st_big, s->d_Hc_big);
-                case 2048: return fc_launch_fused<FirCfg::C2048>(s, d_x, d_y, bblk, bstep, inputLen, blast, st, fb, s->st_big, s->d_Hc_big);
-                case 4096: return fc_launch_fused<FirCfg::C4096>(s, d_x, d_y, bblk, bstep, inputLen, blast, st, fb, s->st_big, s->d_Hc_big);
-                case 8192: return fc_launch_fused<FirCfg::C8192>(s, d_x, d_y, bblk, bstep, inputLen, blast, st, fb, s->st_big, s->d_Hc_big);
+                case 1024: return fc_launch_fused<FirCfg::C1024>(s, d_x, d_y, bblk, bstep, inputLen, blast, st, fb, s->st_big, s->d_Hc_big.as<float>());
+                case 2048: return fc_launch_fused<FirCfg::C2048>(s, d_x, d_y, bblk, bstep, inputLen, blast, st, fb, s->st_big, s->d_Hc_big.as<float>());
+                case 4096: return fc_launch_fused<FirCfg::C4096>(s, d_x, d_y, bblk, bstep, inputLen, blast, st, fb, s->st_big, s->d_Hc_big.as<float>());
+                case 8192: return fc_launch_fused<FirCfg::C8192>(s, d_x, d_y, bblk, bstep, inputLen, blast, st, fb, s->st_big, s->d_Hc_big.as<float>());
                 default: break;
             }
         }
@@ -478,8 +463,8 @@ static int fc_apply_device(FastConv* s, const float* d_x, int cplxInputLen, floa
     if (taps <= TD_MAX_TAPS) {
         // short real filter: time domain; the complex modes are the stride-2 sum over the float stream
         if (!s->d_td) {
-            PF_CHECK(hipMalloc((void**)&s->d_td, sizeof(float) * s->h_td.size()));
-            PF_CHECK(hipMemcpy(s->d_td, s->h_td.data(), sizeof(float) * s->h_td.size(), hipMemcpyHostToDevice));
+            if ((rc = s->d_td.grow(sizeof(float) * s->h_td.size()))) return rc;
+            PF_CHECK(hipMemcpy(s->d_td.get(), s->h_td.data(), sizeof(float) * s->h_td.size(), hipMemcpyHostToDevice));
         }
         const int flen8 = (int)s->h_td.size();
         const bool cplx = mode == 1 || s->cplxFactor == 2;
@@ -491,25 +476,25 @@ static int fc_apply_device(FastConv* s, const float* d_x, int cplxInputLen, floa
             const dim3 grid((unsigned)((out_f + TD_TILE - 1) / TD_TILE), (unsigned)ns);
             const float* xs = d_x + (size_t)s0 * fb.xstride;
             float* ys = d_y + (size_t)s0 * fb.ystride;
-            if (cplx) hipLaunchKernelGGL(fastconv_td_kernel<2>, grid, dim3(TD_THREADS), lds, st, xs, ys, (const float*)s->d_td, flen8, out_f, in_f, fb.xstride, fb.ystride);
-            else hipLaunchKernelGGL(fastconv_td_kernel<1>, grid, dim3(TD_THREADS), lds, st, xs, ys, (const float*)s->d_td, flen8, out_f, in_f, fb.xstride, fb.ystride);
+            if (cplx) hipLaunchKernelGGL(fastconv_td_kernel<2>, grid, dim3(TD_THREADS), lds, st, xs, ys, s->d_td.as<float>(), flen8, out_f, in_f, fb.xstride, fb.ystride);
+            else hipLaunchKernelGGL(fastconv_td_kernel<1>, grid, dim3(TD_THREADS), lds, st, xs, ys, s->d_td.as<float>(), flen8, out_f, in_f, fb.xstride, fb.ystride);
         }
         PF_CHECK(hipGetLastError());
         return 0;
     }
     if (mode == 0 && Nfft == 16384 && (long)nblk * fb.nsig >= 2L * num_cus()) {
         if (!sel.is(AB_FIR_SPLIT) && !sel.is(AB_FIR_LOCKSTEP) && !sel.is(AB_FIR_SPLIT_PLAIN)) {
-            rc = launch_fir32(s->st, s->d_Hc, d_x, d_y, nblk, step, inputLen, lastOut, st, fb, &s->d_fir32_hp_ref, 2);
+            rc = launch_fir32(s->st, s->d_Hc.as<float>(), d_x, d_y, nblk, step, inputLen, lastOut, st, fb, s->d_fir32_hp_ref, 2);
             if (rc != -1) return rc;
         }
-        rc = launch_fir_dma(s->st, s->d_Hc, d_x, d_y, nblk, step, inputLen, lastOut, st, fb);   // many reference-sized blocks
+        rc = launch_fir_dma(s->st, s->d_Hc.as<float>(), d_x, d_y, nblk, step, inputLen, lastOut, st, fb);   // many reference-sized blocks
         if (rc != -1) return rc;
     }
     if (mode == 0 && !sel.is(AB_FIR_FEW_16PT) && !sel.is(AB_FIR_FEW_LOCKSTEP) && (Nfft == 8192 || Nfft == 4096)) {
         // few blocks of 8192 / 4096 samples: cross-wave radix 8 / 4 + wave-local 512-point transforms (fft_split.h
         // fastconv_split1_kernel, round 4); AB_FIR_FEW_LOCKSTEP = the lock-step kernel on 512 / 256 threads (the second route of
         // tests/test_gpu_round4.py), AB_FIR_FEW_16PT (development build) = on 256 / 128
-        rc = launch_fir_split1(s->st, s->d_Hc, d_x, d_y, nblk, step, inputLen, lastOut, st, fb, &s->d_split1_ab);
+        rc = launch_fir_split1(s->st, s->d_Hc.as<float>(), d_x, d_y, nblk, step, inputLen, lastOut, st, fb, s->d_split1_ab);
         if (rc != -1) return rc;
     }
     if (mode == 0) {  // one real stream: the fused one-kernel path when Nfft/2 has a tiled kernel
@@ -533,22 +518,9 @@ static int fc_apply_device(FastConv* s, const float* d_x, int cplxInputLen, floa
         }
     }
     // composed path (complex-I/O modes with long filters): signal by signal on the same stream through one work image
-    if (s->work.size() >= 8 && !s->work.count(st)) {   // the stream that used this setup longest ago gives up its image (hipFree waits for its kernels)
-        auto victim = s->work.end();                   // (never an image a HIP graph has recorded: a replay dereferences the frozen pointer)
-        for (auto it = s->work.begin(); it != s->work.end(); ++it)
-            if (!it->second.captured && (victim == s->work.end() || it->second.last_use < victim->second.last_use)) victim = it;
-        if (victim != s->work.end()) {
-            if (victim->second.p) (void)hipFree(victim->second.p);
-            s->work.erase(victim);
-        }
-    }
-    FastConv::Work& wk = s->work[st];
-    wk.last_use = ++s->work_clock;
-    if (stream_capturing(st)) wk.captured = true;
-    if (wk.captured && wk.p && wk.floats < (size_t)nblk * Nfft) { s->retired.push_back(wk.p); wk.p = nullptr; wk.floats = 0; }   // outgrown: retired, not freed
-    rc = fc_grow(&wk.p, &wk.floats, (size_t)nblk * Nfft);
-    if (rc) return rc;
-    float* const d_work = wk.p;
+    StreamScratch::Entry& wk = s->work.acquire(st);
+    if ((rc = s->work.grow(wk, 0, sizeof(float) * (size_t)nblk * Nfft))) return rc;
+    float* const d_work = wk.buf[0].as<float>();
     const unsigned grid = (unsigned)std::min<size_t>(((size_t)nblk * Nfft + 255) / 256, (size_t)num_cus() * 16);
     for (int sig = 0; sig < fb.nsig; ++sig) {
         const float* xs = d_x + (size_t)sig * fb.xstride;
@@ -558,7 +530,7 @@ static int fc_apply_device(FastConv* s, const float* d_x, int cplxInputLen, floa
         PF_CHECK(hipGetLastError());
         rc = transform_batch<float>(s->st, d_work, d_work, nblk, PFFFT_FORWARD, 0, st);            // :235
         if (rc) return rc;
-        rc = zconvolve_batch<float>(s->st, d_work, s->d_Hf, d_work, s->scale, nblk, 0, 1, st);     // :238
+        rc = zconvolve_batch<float>(s->st, d_work, s->d_Hf.as<float>(), d_work, s->scale, nblk, 0, 1, st);     // :238
         if (rc) return rc;
         rc = transform_batch<float>(s->st, d_work, d_work, nblk, PFFFT_BACKWARD, 0, st);           // :254
         if (rc) return rc;
@@ -607,14 +579,7 @@ PF_EXPORT void pffastconv_destroy_setup(PFFASTCONV_Setup* s) {
     if (!s) return;
     pffft_destroy_setup(s->st);
     if (s->st_big) pffft_destroy_setup(s->st_big);
-    for (float* p : {s->d_Hf, s->d_Hc, s->d_Hc_big, s->d_Hp, s->d_td, s->d_x, s->d_y}) if (p) (void)hipFree(p);
     if (s->st_part) pffft_destroy_setup(s->st_part);
-    for (auto& kv : s->work) if (kv.second.p) (void)hipFree(kv.second.p);
-    for (float* p : s->retired) if (p) (void)hipFree(p);
-    if (s->d_split1_ab) (void)hipFree(s->d_split1_ab);
-    if (s->d_fir32_hp) (void)hipFree(s->d_fir32_hp);
-    if (s->d_fir32_hp_ref) (void)hipFree(s->d_fir32_hp_ref);
-    for (float* p : {s->h_x, s->h_y}) if (p) (void)hipHostFree(p);
     s->magic = 0;
     delete s;
 }
@@ -649,17 +614,6 @@ PF_EXPORT int pffastconv_hip_apply_batch(PFFASTCONV_Setup* s, const float* d_inp
     return rc ? -1 : produced;
 }
 
-namespace pf {
-static int fc_pinned(float** p, size_t* have, size_t want) {
-    if (*have >= want) return 0;
-    if (*p) (void)hipHostFree(*p);
-    *p = nullptr; *have = 0;
-    PF_CHECK(hipHostMalloc((void**)p, want * sizeof(float), hipHostMallocDefault));
-    *have = want;
-    return 0;
-}
-}  // namespace pf
-
 // Host pointers (the reference's calling convention): up to FC_ZC_LIMIT bytes per signal there is no DMA copy — the signal
 // is copied by the CPU into a pinned host image that the kernel reads over PCIe directly, the kernel writes its outputs
 // into another pinned image, one stream synchronisation, CPU copy out (the same scheme as the transform entries,
@@ -676,26 +630,27 @@ PF_EXPORT int pffastconv_apply(PFFASTCONV_Setup* s, const float* input, int cplx
     const bool in_dev = is_device_ptr(input), out_dev = is_device_ptr(output);
     const int cpl = (s->flags & PFFASTCONV_HIP_CPLX_INP_OUT) ? 2 : 1;
     const size_t in_floats = (size_t)cplxInputLen * cpl;
+    const size_t stage_bytes = (in_floats ? in_floats : 1) * sizeof(float);
     const float* d_in = input; float* d_out = output;
     int rc = 0, produced = 0;
     const bool zc = zero_copy_enabled() && in_floats * sizeof(float) <= FC_ZC_LIMIT;
     bool out_pinned = false;
     do {
         if (!in_dev) {
-            if (zc && fc_pinned(&s->h_x, &s->hx_floats, in_floats ? in_floats : 1) == 0) {
-                if (in_floats) memcpy(s->h_x, input, in_floats * sizeof(float));
-                d_in = s->h_x;
+            if (zc && s->h_x.grow(stage_bytes) == 0) {
+                if (in_floats) memcpy(s->h_x.get(), input, in_floats * sizeof(float));
+                d_in = s->h_x.as<float>();
             } else {
-                if ((rc = fc_grow(&s->d_x, &s->x_floats, in_floats ? in_floats : 1))) break;
-                if (in_floats && hipMemcpy(s->d_x, input, in_floats * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { rc = -1; break; }
-                d_in = s->d_x;
+                if ((rc = s->d_x.grow(stage_bytes))) break;
+                if (in_floats && hipMemcpy(s->d_x.get(), input, in_floats * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { rc = -1; break; }
+                d_in = s->d_x.as<float>();
             }
         }
         if (!out_dev) {
-            if (zc && fc_pinned(&s->h_y, &s->hy_floats, in_floats ? in_floats : 1) == 0) { d_out = s->h_y; out_pinned = true; }
+            if (zc && s->h_y.grow(stage_bytes) == 0) { d_out = s->h_y.as<float>(); out_pinned = true; }
             else {
-                if ((rc = fc_grow(&s->d_y, &s->y_floats, in_floats ? in_floats : 1))) break;
-                d_out = s->d_y;
+                if ((rc = s->d_y.grow(stage_bytes))) break;
+                d_out = s->d_y.as<float>();
             }
         }
         if ((rc = fc_apply_device(s, d_in, cplxInputLen, d_out, applyFlush, nullptr, &produced))) break;

@@ -310,24 +310,10 @@ static Setup* new_setup(int N, int transform, int is_double) {
 
 static void destroy_setup(Setup* s) {
     if (!s) return;
-    for (auto& kv : s->replicas) destroy_setup(kv.second);   // (hipFree takes a pointer of any device, whatever the current one is)
-    if (s->dev_ready) {
-        if (s->d_tw) (void)hipFree(s->d_tw);
-        if (s->d_twr) (void)hipFree(s->d_twr);
-        for (void* q : s->d_twc) if (q) (void)hipFree(q);
-        if (s->d_one_tw2) (void)hipFree(s->d_one_tw2);
-    }
-    if (s->d_ctr) (void)hipFree(s->d_ctr);
+    for (auto& kv : s->replicas) destroy_setup(kv.second);
     if (s->sub) destroy_setup(s->sub);
-    for (void* p : s->d_bigtw) if (p) (void)hipFree(p);
-    for (auto& kv : s->big_scratch) for (void* p : kv.second.buf) if (p) (void)hipFree(p);
-    for (auto& kv : s->conv_scratch) for (void* p : kv.second.buf) if (p) (void)hipFree(p);
-    for (auto& kv : s->frames_scratch) for (void* p : kv.second.buf) if (p) (void)hipFree(p);
-    for (void* p : s->retired) if (p) (void)hipFree(p);
-    for (void* p : s->d_stage) if (p) (void)hipFree(p);
-    for (void* p : s->h_stage) if (p) (void)hipHostFree(p);
     s->magic = 0;
-    delete s;
+    delete s;   // (the tables, scratch and staging buffers go with their owners: pf_devmem.h)
 }
 
 // The key a thread's current device goes by: the HIP device index; AB_FAKE_DEVICE moves the calling thread to a key of its own (the
@@ -398,8 +384,10 @@ static int alloc_counter_ring(Setup* s) {
     if (s->d_ctr) return 0;
     // (+ 16 after each region: a launch may take several consecutive pairs from the last slot)
     constexpr size_t words = 2 * (size_t)CTR_RING + 16 + 2 * (size_t)CTR_CAPTURED + 16;
-    PF_CHECK(hipMalloc((void**)&s->d_ctr, sizeof(unsigned) * words));
-    PF_CHECK(hipMemset(s->d_ctr, 0, sizeof(unsigned) * words));
+    int rc = s->d_ctr.grow(sizeof(unsigned) * words);
+    if (rc) return rc;
+    hipError_t e = hipMemset(s->d_ctr.get(), 0, sizeof(unsigned) * words);
+    if (e != hipSuccess) { s->d_ctr.reset(); return fail(e, "hipMemset of the counter ring"); }   // (never a ring that was not cleared)
     return 0;
 }
 
@@ -410,8 +398,9 @@ bool stream_capturing(hipStream_t st) {
 }
 
 unsigned* take_counters(Setup* s, hipStream_t st, unsigned pairs) {
-    if (stream_capturing(st)) return s->d_ctr + 2 * (size_t)CTR_RING + 16 + 2 * (s->cap_slot.fetch_add(pairs) % CTR_CAPTURED);
-    return s->d_ctr + 2 * (s->ctr_slot.fetch_add(pairs) % CTR_RING);
+    unsigned* ring = s->d_ctr.as<unsigned>();
+    if (stream_capturing(st)) return ring + 2 * (size_t)CTR_RING + 16 + 2 * (s->cap_slot.fetch_add(pairs) % CTR_CAPTURED);
+    return ring + 2 * (s->ctr_slot.fetch_add(pairs) % CTR_RING);
 }
 
 template <typename T>
@@ -428,75 +417,22 @@ static int ensure_device(Setup* s) {
                 g_last_error = "pffft_hip: N too large even for the four-step path in this precision";
                 return (int)hipErrorInvalidValue;
             }
-            std::vector<cx<T>> tw(m);
-            for (int j = 0; j < m; ++j) {
-                long double a = -2.0L * 3.14159265358979323846264338327950288L * (long double)j / (long double)m;
-                tw[j].x = (T)cosl(a); tw[j].y = (T)sinl(a);
-            }
-            PF_CHECK(hipMalloc(&s->d_bigtw[i], sizeof(cx<T>) * m));
-            PF_CHECK(hipMemcpy(s->d_bigtw[i], tw.data(), sizeof(cx<T>) * m, hipMemcpyHostToDevice));
+            if ((rc = upload_roots<T>(s->d_bigtw[i], m, m))) return rc;
         }
         if (s->one_ok) {   // single-image kernel: compact base twiddles per direction, W_N^k of the pair pass
-            const long double PI2 = 2.0L * 3.14159265358979323846264338327950288L;
-            for (int d = 0; d < 3; ++d) {
-                const StockPlan& sp = s->one[d];
-                std::vector<cx<T>> tc(sp.ctab + 1);
-                for (int st = 1; st < sp.ns; ++st) {
-                    const StockStage& g = sp.st[st];
-                    for (int jm = 0; jm < g.Ns; ++jm) {   // W_{Ns R}^jm
-                        const long double a = -PI2 * (long double)jm / (long double)(g.Ns * g.R);
-                        tc[g.tw_off + jm].x = (T)cosl(a); tc[g.tw_off + jm].y = (T)sinl(a);
-                    }
-                }
-                void** dst = d < 2 ? &s->d_twc[d] : &s->d_one_tw2;
-                PF_CHECK(hipMalloc(dst, sizeof(cx<T>) * tc.size()));
-                PF_CHECK(hipMemcpy(*dst, tc.data(), sizeof(cx<T>) * tc.size(), hipMemcpyHostToDevice));
-            }
-            if (s->transform == PFFFT_REAL) {
-                const int m = s->n / 2 + 1;
-                std::vector<cx<T>> twr(m);
-                for (int k = 0; k < m; ++k) {
-                    const long double a = -PI2 * (long double)k / (long double)(2 * s->n);
-                    twr[k].x = (T)cosl(a); twr[k].y = (T)sinl(a);
-                }
-                PF_CHECK(hipMalloc(&s->d_twr, sizeof(cx<T>) * m));
-                PF_CHECK(hipMemcpy(s->d_twr, twr.data(), sizeof(cx<T>) * m, hipMemcpyHostToDevice));
-            }
+            for (int d = 0; d < 3; ++d)
+                if ((rc = upload_stock_table<T>(d < 2 ? s->d_twc[d] : s->d_one_tw2, s->one[d]))) return rc;
+            if (s->transform == PFFFT_REAL && (rc = upload_roots<T>(s->d_twr, s->n / 2 + 1, 2LL * s->n))) return rc;
         }
         s->dev_ready = true;
         return 0;
     }
     const int n = s->n;
-    std::vector<cx<T>> tw(n);
-    for (int j = 0; j < n; ++j) {  // tables are generated in extended precision and rounded once
-        long double a = -2.0L * 3.14159265358979323846264338327950288L * (long double)j / (long double)n;
-        tw[j].x = (T)cosl(a); tw[j].y = (T)sinl(a);
-    }
-    PF_CHECK(hipMalloc(&s->d_tw, sizeof(cx<T>) * n));
-    PF_CHECK(hipMemcpy(s->d_tw, tw.data(), sizeof(cx<T>) * n, hipMemcpyHostToDevice));
-    if (s->transform == PFFFT_REAL) {
-        const int m = n / 2 + 1;
-        std::vector<cx<T>> twr(m);
-        for (int k = 0; k < m; ++k) {
-            long double a = -2.0L * 3.14159265358979323846264338327950288L * (long double)k / (long double)(2 * n);
-            twr[k].x = (T)cosl(a); twr[k].y = (T)sinl(a);
-        }
-        PF_CHECK(hipMalloc(&s->d_twr, sizeof(cx<T>) * m));
-        PF_CHECK(hipMemcpy(s->d_twr, twr.data(), sizeof(cx<T>) * m, hipMemcpyHostToDevice));
-    }
+    if ((rc = upload_roots<T>(s->d_tw, n, n))) return rc;
+    if (s->transform == PFFFT_REAL && (rc = upload_roots<T>(s->d_twr, n / 2 + 1, 2LL * n))) return rc;
     for (int d = 0; d < 2; ++d) {
         const StockPlan* sp = (s->sk_ok && s->sk[d].twmode == 2) ? &s->sk[d] : (s->skw_ok && s->skw[d].twmode == 2) ? &s->skw[d] : nullptr;
-        if (!sp) continue;
-        std::vector<cx<T>> tc(sp->ctab + 1);
-        for (int st = 1; st < sp->ns; ++st) {
-            const StockStage& g = sp->st[st];
-            for (int jm = 0; jm < g.Ns; ++jm) {   // W_{Ns R}^jm
-                long double a = -2.0L * 3.14159265358979323846264338327950288L * (long double)jm / (long double)(g.Ns * g.R);
-                tc[g.tw_off + jm].x = (T)cosl(a); tc[g.tw_off + jm].y = (T)sinl(a);
-            }
-        }
-        PF_CHECK(hipMalloc(&s->d_twc[d], sizeof(cx<T>) * tc.size()));
-        PF_CHECK(hipMemcpy(s->d_twc[d], tc.data(), sizeof(cx<T>) * tc.size(), hipMemcpyHostToDevice));
+        if (sp && (rc = upload_stock_table<T>(s->d_twc[d], *sp))) return rc;
     }
     s->dev_ready = true;
     return 0;
@@ -562,7 +498,7 @@ template <int W>
 static int launch_c1024_once(Setup* s, const float* in, float* out, size_t batch, int dir, int ordered, hipStream_t st) {
     const unsigned grid = (unsigned)((batch + W - 1) / W);
     const size_t lds = (size_t)W * C1024_WAVE_BYTES;
-    const cx<float>* tw = (const cx<float>*)s->d_tw;
+    const cx<float>* tw = s->d_tw.as<cx<float>>();
 #define PF_LAUNCH_C1024_ONCE(D, I, O)                                                                 \
     do {                                                                                              \
         auto k = fft_c1024_f32_once_kernel<D, I, O, W>;                                               \
@@ -595,7 +531,7 @@ static int launch_c1024(Setup* s, const Route& r, const float* in, float* out, s
     if (grid > wgs_needed) grid = wgs_needed;
     const dim3 blk(C1024_WAVES * 64);
     const size_t lds = C1024_LDS_BYTES;
-    const cx<float>* tw = (const cx<float>*)s->d_tw;
+    const cx<float>* tw = s->d_tw.as<cx<float>>();
     const unsigned b = (unsigned)batch;
     unsigned* ctr = take_counters(s, st);
 #define PF_LAUNCH_C1024(D, I, O)                                                                      \
@@ -623,7 +559,7 @@ static int launch_c1024_mix(Setup* s, const float* in, float* out, size_t batch,
     if (grid > wgs_needed) grid = wgs_needed;
     const dim3 blk(C1024_WAVES * 64);
     const size_t lds = C1024_LDS_BYTES;
-    const cx<float>* tw = (const cx<float>*)s->d_tw;
+    const cx<float>* tw = s->d_tw.as<cx<float>>();
     const unsigned b = (unsigned)batch;
     unsigned* ctr = take_counters(s, st);
     C1024Mix mix;
@@ -750,7 +686,7 @@ static int launch_tiled(Setup* s, const Route& r, const T* in, T* out, size_t ba
     const int flags = (((dir == PFFFT_BACKWARD) && !ordered) ? 1 : 0) | (((dir == PFFFT_FORWARD) && !ordered) ? 2 : 0);
     unsigned* ctr = groups <= grid ? nullptr : take_counters(s, st);
     hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(e.wg), e.lds, st, in, out, (unsigned)batch, flags,
-                       (const cx<T>*)s->d_tw, (const cx<T>*)s->d_twr, ctr);
+                       s->d_tw.as<cx<T>>(), s->d_twr.as<cx<T>>(), ctr);
     PF_CHECK(hipGetLastError());
     return 0;
 }
@@ -805,7 +741,7 @@ static int launch_stock(Setup* s, const Route& r, const T* in, T* out, size_t ba
     const StockSel& k = r.stock;
     const bool bwd = dir == PFFFT_BACKWARD;
     const StockPlan& sp = k.wl ? s->skw[bwd ? 1 : 0] : s->sk[bwd ? 1 : 0];
-    const cx<T>* twp = (const cx<T>*)(sp.twmode == 2 ? s->d_twc[bwd ? 1 : 0] : s->d_tw);
+    const cx<T>* twp = (sp.twmode == 2 ? s->d_twc[bwd ? 1 : 0] : s->d_tw).as<cx<T>>();
     const size_t groups = (batch + sp.G - 1) / sp.G;
     const bool dyn = r.rule == LR_INORDER;
     // in-order groups are pulled in chunks of ONE group from 44 KiB per group on (double n = 3072 .. 4000 0.71-0.75 -> 0.78-0.82 against two),
@@ -841,7 +777,7 @@ static int launch_stock(Setup* s, const Route& r, const T* in, T* out, size_t ba
         if (grid > groups) grid = groups;
         if (grid > 0x7fffffffu) grid = 0x7fffffffu;
         unsigned* ctr = (groups <= grid || !dyn) ? nullptr : take_counters(s, st);
-        hipLaunchKernelGGL(cf, dim3((unsigned)grid), dim3(k.threads), k.lds, st, in, out, batch, twp, (const cx<T>*)s->d_twr, ctr, chunk_for(grid));
+        hipLaunchKernelGGL(cf, dim3((unsigned)grid), dim3(k.threads), k.lds, st, in, out, batch, twp, s->d_twr.as<cx<T>>(), ctr, chunk_for(grid));
         PF_CHECK(hipGetLastError());
         return 0;
     }
@@ -856,7 +792,7 @@ static int launch_stock(Setup* s, const Route& r, const T* in, T* out, size_t ba
     size_t grid = (size_t)num_cus() * per_cu;
     if (grid > groups) grid = groups;
     unsigned* ctr = (groups <= grid || !dyn) ? nullptr : take_counters(s, st);
-    hipLaunchKernelGGL(kf, dim3((unsigned)grid), dim3(k.threads), k.lds, st, in, out, batch, sp, k.flags, twp, (const cx<T>*)s->d_twr, ctr, chunk_for(grid));
+    hipLaunchKernelGGL(kf, dim3((unsigned)grid), dim3(k.threads), k.lds, st, in, out, batch, sp, k.flags, twp, s->d_twr.as<cx<T>>(), ctr, chunk_for(grid));
     PF_CHECK(hipGetLastError());
     return 0;
 #else
@@ -882,7 +818,7 @@ static int launch_strided(Setup* s, int which, const cx<T>* in, cx<T>* out, size
     int rc = allow_big_lds(dir == PFFFT_FORWARD ? kf : kb, lds);
     if (rc) return rc;
     hipLaunchKernelGGL(dir == PFFFT_FORWARD ? kf : kb, dim3((unsigned)grid), dim3(th), lds, st, in, out, (long long)batch, sp,
-                       (const cx<T>*)s->d_bigtw[which]);
+                       s->d_bigtw[which].as<cx<T>>());
     PF_CHECK(hipGetLastError());
     return 0;
 }
@@ -965,40 +901,6 @@ static int launch_block(Setup* s, int mode, const T* in, T* out, size_t batch, h
     return 0;
 }
 
-// Per-stream scratch of a setup (held under the setup's scratch lock).  More than SCRATCH_STREAMS streams: ONE entry goes - the stream that
-// used this setup longest ago (hipFree waits for its kernels) - not the whole map: a caller cycling through nine streams would otherwise
-// free and re-allocate every stream's buffers on every call.  An entry a HIP graph has recorded (Scratch::captured) is never the victim,
-// and a buffer it outgrows is retired instead of freed: a replay dereferences the pointers it froze at capture time.
-constexpr size_t SCRATCH_STREAMS = 8;
-int stream_scratch(std::map<hipStream_t, Setup::Scratch>& tab, unsigned long long& clock, hipStream_t st, Setup::Scratch** out) {
-    if (tab.size() >= SCRATCH_STREAMS && !tab.count(st)) {
-        auto victim = tab.end();
-        for (auto it = tab.begin(); it != tab.end(); ++it)
-            if (!it->second.captured && (victim == tab.end() || it->second.last_use < victim->second.last_use)) victim = it;
-        if (victim != tab.end()) {
-            for (void* p : victim->second.buf) if (p) (void)hipFree(p);
-            tab.erase(victim);
-        }
-    }
-    Setup::Scratch& sc = tab[st];
-    sc.last_use = ++clock;
-    if (stream_capturing(st)) sc.captured = true;
-    *out = &sc;
-    return 0;
-}
-int scratch_grow(Setup* s, Setup::Scratch& sc, int i, size_t bytes) {
-    if (sc.bytes[i] >= bytes) return 0;
-    // (hipFree waits for the device: kernels of this stream still using the old buffer finish first)
-    if (sc.buf[i]) {
-        if (sc.captured) { std::lock_guard<std::mutex> lk(s->retired_mu); s->retired.push_back(sc.buf[i]); }
-        else (void)hipFree(sc.buf[i]);
-    }
-    sc.buf[i] = nullptr; sc.bytes[i] = 0;
-    PF_CHECK(hipMalloc(&sc.buf[i], bytes));   // (while the stream is capturing this fails: warm the setup up with the largest batch first)
-    sc.bytes[i] = bytes;
-    return 0;
-}
-
 // ------------------------------------------------------------------------------------------------
 // n beyond LDS: the sweeps over HBM of a (direction, layout), planned once (BigPlan), executed by launch_big
 // ------------------------------------------------------------------------------------------------
@@ -1073,17 +975,13 @@ static int launch_big(Setup* s, const Route& r, const T* in, T* out, size_t batc
     // (the work rows of the real two-sweep route - k1 <= N1/2, whole row tiles - need a little more than n)
     if (b.core == BIG_RFFT2) bytes = std::max(bytes, batch * tile_rfft_work_elems(2LL * s->n, s->is_double != 0) * sizeof(cx<T>));
     cx<T>*bufA, *bufB;
-    // big_mu is held until EVERY pass of this call is enqueued: it guards host-side enqueue only, and a second thread growing the same
-    // stream's scratch (hipFree synchronises with the device) can then never free buffers whose kernels are not yet in the stream
-    std::lock_guard<std::mutex> lk(s->big_mu);
+    std::lock_guard<std::mutex> lk(s->big.mu);   // held until EVERY pass of this call is enqueued (StreamScratch)
     {
-        Setup::Scratch* scp = nullptr;
-        int rcs = stream_scratch(s->big_scratch, s->scratch_clock, st, &scp);
-        if (rcs) return rcs;
+        StreamScratch::Entry& sc = s->big.acquire(st);
         for (int i = 0; i < 2; ++i)
-            if ((rcs = scratch_grow(s, *scp, i, bytes))) return rcs;
-        bufA = (cx<T>*)scp->buf[0];
-        bufB = (cx<T>*)scp->buf[1];
+            if (int rcs = s->big.grow(sc, i, bytes)) return rcs;
+        bufA = sc.buf[0].as<cx<T>>();
+        bufB = sc.buf[1].as<cx<T>>();
     }
     const bool real = s->transform == PFFFT_REAL, fwd = dir == PFFFT_FORWARD;
     int rc;
@@ -1151,7 +1049,7 @@ static int launch_tiny(Setup* s, const T* in, T* out, size_t batch, int dir, int
     // (one group of 64 vectors per wavefront in hardware dispatch order: plan_route has the measurement)
     (void)cap;
     const bool real = s->transform == PFFFT_REAL, fwd = dir == PFFFT_FORWARD;
-    const cx<T>* twr = (const cx<T>*)s->d_twr;
+    const cx<T>* twr = s->d_twr.as<cx<T>>();
 #define PF_TINY(D, R, I, O)                                                                                        \
     do {                                                                                                           \
         auto k = fft_tiny_kernel<T, n, D, R, I, O>;                                                                \
@@ -1583,12 +1481,10 @@ static int convolve_batch(Setup* s, const T* in, const T* H, T* out, T scaling, 
         if (rc != -1) return rc;
     }
     const size_t bytes = batch * s->vec_scalars * sizeof(T);
-    std::lock_guard<std::mutex> lk(s->conv_mu);
-    Setup::Scratch* scp = nullptr;
-    if ((rc = stream_scratch(s->conv_scratch, s->conv_clock, st, &scp))) return rc;
-    Setup::Scratch& sc = *scp;
-    if ((rc = scratch_grow(s, sc, 0, bytes))) return rc;
-    T* X = (T*)sc.buf[0];
+    std::lock_guard<std::mutex> lk(s->conv.mu);
+    StreamScratch::Entry& sc = s->conv.acquire(st);
+    if ((rc = s->conv.grow(sc, 0, bytes))) return rc;
+    T* X = sc.buf[0].as<T>();
     if ((rc = transform_batch<T>(s, in, X, batch, PFFFT_FORWARD, 0, st))) return rc;
     if ((rc = zconvolve_batch<T>(s, X, H, X, scaling, batch, 0, h_broadcast, st))) return rc;
     if (!accumulate) return transform_batch<T>(s, X, out, batch, PFFFT_BACKWARD, 0, st);
@@ -1608,28 +1504,6 @@ static bool is_device_ptr(const void* p) {
     hipError_t e = hipPointerGetAttributes(&attr, p);
     if (e != hipSuccess) { (void)hipGetLastError(); return false; }
     return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
-}
-
-static int stage_buf(Setup* s, int slot, size_t bytes, void** out) {
-    if (s->stage_bytes[slot] < bytes) {
-        if (s->d_stage[slot]) (void)hipFree(s->d_stage[slot]);
-        s->d_stage[slot] = nullptr; s->stage_bytes[slot] = 0;
-        PF_CHECK(hipMalloc(&s->d_stage[slot], bytes));
-        s->stage_bytes[slot] = bytes;
-    }
-    *out = s->d_stage[slot];
-    return 0;
-}
-
-static int pinned_buf(Setup* s, int slot, size_t bytes, void** out) {
-    if (s->hstage_bytes[slot] < bytes) {
-        if (s->h_stage[slot]) (void)hipHostFree(s->h_stage[slot]);
-        s->h_stage[slot] = nullptr; s->hstage_bytes[slot] = 0;
-        PF_CHECK(hipHostMalloc(&s->h_stage[slot], bytes, hipHostMallocDefault));
-        s->hstage_bytes[slot] = bytes;
-    }
-    *out = s->h_stage[slot];
-    return 0;
 }
 
 // Host-pointer calls on small vectors: no DMA copies at all.  The vector is copied (CPU memcpy, < 1 us) into a pinned host
@@ -1656,13 +1530,11 @@ static int legacy_run(Setup* s, const T* const* ins, int nin, T* out, bool out_i
         bool any_dev = is_device_ptr(out);
         for (int i = 0; i < nin && !any_dev; ++i) any_dev = is_device_ptr(ins[i]);
         // the pinned images are allocated up front; if the host cannot pin memory the device staging below still works
-        void* pins[4] = {nullptr, nullptr, nullptr, nullptr};
         bool pinned_ok = !any_dev;
-        for (int k = 0; k <= nin && pinned_ok; ++k) pinned_ok = pinned_buf(s, k, bytes, &pins[k]) == 0;
+        for (int k = 0; k <= nin && pinned_ok; ++k) pinned_ok = s->h_stage[k].grow(bytes) == 0;
         if (!any_dev && pinned_ok) {
             const T* h_in[3] = {nullptr, nullptr, nullptr};
-            void* po; int rc = pinned_buf(s, 0, bytes, &po); if (rc) return rc;
-            T* h_out = (T*)po;
+            T* h_out = s->h_stage[0].as<T>();
             bool out_loaded = false;
             if (out_is_inout) { memcpy(h_out, out, bytes); out_loaded = true; }
             int slot = 1;
@@ -1671,11 +1543,11 @@ static int legacy_run(Setup* s, const T* const* ins, int nin, T* out, bool out_i
                 bool dup = false;
                 for (int j = 0; j < i; ++j) if (ins[j] == ins[i]) { h_in[i] = h_in[j]; dup = true; break; }
                 if (dup) continue;
-                void* p; rc = pinned_buf(s, slot++, bytes, &p); if (rc) return rc;
+                void* p = s->h_stage[slot++].get();
                 memcpy(p, ins[i], bytes);
                 h_in[i] = (const T*)p;
             }
-            rc = fn(h_in, h_out);
+            int rc = fn(h_in, h_out);
             if (rc) return rc;
             PF_CHECK(hipStreamSynchronize(nullptr));
             memcpy(out, h_out, bytes);
@@ -1688,8 +1560,8 @@ static int legacy_run(Setup* s, const T* const* ins, int nin, T* out, bool out_i
     int slot = 0;
     if (out_dev) d_out = out;
     else {
-        void* p; int rc = stage_buf(s, slot++, bytes, &p); if (rc) return rc;
-        d_out = (T*)p;
+        int rc = s->d_stage[slot].grow(bytes); if (rc) return rc;
+        d_out = s->d_stage[slot++].as<T>();
         if (out_is_inout) PF_CHECK(hipMemcpy(d_out, out, bytes, hipMemcpyHostToDevice));
     }
     for (int i = 0; i < nin; ++i) {
@@ -1699,7 +1571,8 @@ static int legacy_run(Setup* s, const T* const* ins, int nin, T* out, bool out_i
         if (dup) continue;
         if (is_device_ptr(ins[i])) d_in[i] = ins[i];
         else {
-            void* p; int rc = stage_buf(s, slot++, bytes, &p); if (rc) return rc;
+            int rc = s->d_stage[slot].grow(bytes); if (rc) return rc;
+            void* p = s->d_stage[slot++].get();
             PF_CHECK(hipMemcpy(p, ins[i], bytes, hipMemcpyHostToDevice));
             d_in[i] = (const T*)p;
         }
