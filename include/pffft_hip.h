@@ -234,6 +234,42 @@ int pffftd_hip_frames_overlap_add_batch(PFFFTD_Setup *, const double *spectra, s
  * Host arithmetic only; PFFFT_Setup and PFFFTD_Setup handles. */
 const char *pffft_hip_frames_route(const void *setup, size_t hop, size_t signal_stride, size_t out_stride, int output);
 
+/* Polyphase filter-bank analysis (weighted overlap-add channelizer): the framing of pffft_hip_frames_transform_batch with a prototype
+ * filter of taps*N real coefficients that is folded onto N points before the transform.  For frame f of signal i
+ *     u_f[j] = sum over p = 0 ... taps-1 of  prototype[p*N + j] * x_i[f*hop + p*N + j],   j < N
+ * (x: real samples, or complex samples times the real coefficient), and out_f is the forward transform of u_f exactly as
+ * pffft_hip_transform_batch transforms a vector.  ROUNDING IS PART OF THE CONTRACT: every product is rounded once, every addition is
+ * rounded once, p ascending, the sum started from its first term (no FMA) - so the result equals transform_batch of the materialised
+ * folded frames bit for bit on every route, and taps = 1 is pffft_hip_frames_transform_batch with the prototype as its window, bit for bit.
+ * Every signal holds (nframes-1)*hop + taps*N samples.  There is NO circular shift and NO per-frame phase rotation: out_f[k] is the
+ * length-taps*N windowed DFT of the segment that starts at sample f*hop, sampled at every taps-th bin (bin taps*k), phase-referenced
+ * to the frame's FIRST sample - as the output of the frame entry is.  A caller who wants channel phases that are continuous from frame
+ * to frame at a hop that is no multiple of N rotates bin k of frame f by exp(-2 pi i k f hop / N) (or circularly shifts u_f) itself.
+ * Arguments, strides, `output` (PFFFT_HIP_FRAMES_INTERNAL / _ORDERED / _POWER), row sizes, out_stride = 0, the frame numbering
+ * v = i*nframes + f, the 256 MiB cap of the frame matrix with chunking and its rule during HIP graph capture are those of
+ * pffft_hip_frames_transform_batch.  signal, prototype and out must not overlap.
+ * Complex float setups of N = 1024 run as ONE kernel for the spectrum outputs - the N = 1024 transform with a folding loader and the
+ * prototype in LDS: taps*N/hop reads of a sample served by the caches, one write of the spectrum - when hop is even, signal_stride and
+ * out_stride are multiples of 4 scalars, signal and out are 16-byte and prototype 8-byte aligned and
+ * taps <= PFFFT_HIP_PFB_FUSED_MAX_TAPS, in the (taps, hop) cells where that kernel measured faster.  Everything else
+ * - every other size, precision and transform, |X|^2, odd hops - is composed: a folding kernel into the per-stream frame matrix,
+ * pffft_hip_transform_batch, and a row kernel where `out` is pitched or a power spectrum.
+ * Validation happens before any device is touched: a NULL or foreign setup, hop == 0, taps == 0, prototype == NULL, an unknown `output`,
+ * an out_stride smaller than a row, a signal_stride smaller than ((nframes-1)*hop + taps*N) samples when nsignals > 1, a NULL signal /
+ * out -> non-zero, nothing launched.  nsignals == 0 or nframes == 0 -> 0, nothing launched. */
+#define PFFFT_HIP_PFB_FUSED_MAX_TAPS 16
+int pffft_hip_pfb_transform_batch(PFFFT_Setup *, const float *signal, size_t signal_stride, size_t nsignals, size_t nframes,
+                                  size_t hop, const float *prototype, size_t taps, float *out, size_t out_stride, int output,
+                                  void *stream);
+int pffftd_hip_pfb_transform_batch(PFFFTD_Setup *, const double *signal, size_t signal_stride, size_t nsignals, size_t nframes,
+                                   size_t hop, const double *prototype, size_t taps, double *out, size_t out_stride, int output,
+                                   void *stream);
+/* The route pffft_hip_pfb_transform_batch takes for these arguments under the calling thread's selector (pffft_hip_set_variant:
+ * 126 = always composed, 127 = fused wherever it is legal): "fused" or "composed"; "" for an invalid handle, hop == 0, taps == 0 or an
+ * unknown output.  Pointer alignment is checked at the call: the query assumes aligned pointers.  signal_stride = 0: one signal.
+ * Host arithmetic only; PFFFT_Setup and PFFFTD_Setup handles. */
+const char *pffft_hip_pfb_route(const void *setup, size_t hop, size_t taps, size_t signal_stride, size_t out_stride, int output);
+
 /* Overlap-save FIR on device-resident signal/output (same block schedule as pffastconv_apply,
  * src/pffastconv.c:204-261): returns the number of output samples written, or -1 on error. */
 int pffastconv_hip_apply_device(PFFASTCONV_Setup *, const float *d_input, int inputLen, float *d_output,

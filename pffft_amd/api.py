@@ -80,6 +80,9 @@ def lib():
         g("hip_frames_transform_batch").restype = C.c_int
         g("hip_frames_transform_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
                                                     C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+        g("hip_pfb_transform_batch").restype = C.c_int
+        g("hip_pfb_transform_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
+                                                 C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
         g("hip_frames_overlap_add_batch").restype = C.c_int
         g("hip_frames_overlap_add_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
                                                       C.c_void_p, ct, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
@@ -103,6 +106,8 @@ def lib():
                                                   C.c_double, C.c_void_p]
     L.pffft_hip_frames_route.restype = C.c_char_p
     L.pffft_hip_frames_route.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int]
+    L.pffft_hip_pfb_route.restype = C.c_char_p
+    L.pffft_hip_pfb_route.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int]
     L.pffft_hip_kernel_name.restype = C.c_char_p; L.pffft_hip_kernel_name.argtypes = [C.c_void_p]
     L.pffft_hip_describe.restype = C.c_int; L.pffft_hip_describe.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.pffft_hip_setup_devices.restype = C.c_int; L.pffft_hip_setup_devices.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_int]
@@ -199,6 +204,16 @@ def frames_route(setup: "Setup", hop, signal_stride=0, out_stride=0, output="ord
     thread's selector.  Host arithmetic only."""
     return lib().pffft_hip_frames_route(setup.handle, int(hop), int(signal_stride), int(out_stride),
                                         FRAMES_OUTPUTS[output]).decode()
+
+
+PFB_FUSED_MAX_TAPS = 16   # PFFFT_HIP_PFB_FUSED_MAX_TAPS of include/pffft_hip.h
+
+
+def pfb_route(setup: "Setup", hop, taps, signal_stride=0, out_stride=0, output="ordered") -> str:
+    """pffft_hip_pfb_route: "fused" / "composed" for a filter-bank call with aligned pointers, under the calling thread's
+    selector.  Host arithmetic only."""
+    return lib().pffft_hip_pfb_route(setup.handle, int(hop), int(taps), int(signal_stride), int(out_stride),
+                                     FRAMES_OUTPUTS[output]).decode()
 
 
 def _is_torch(x) -> bool:
@@ -361,6 +376,34 @@ class Setup:
         fn = getattr(self._L, f"{self._pfx}_hip_frames_transform_batch")
         _check(fn(self.handle, signal.data_ptr(), sstride, nsig, nframes, hop, window.data_ptr() if window is not None else None,
                   out.data_ptr(), pitch, FRAMES_OUTPUTS[output], self._stream()), "hip_frames_transform_batch")
+        return out
+
+    def pfb_transform_batch(self, signal, hop, prototype, nframes=None, out=None, output="internal"):
+        """pffft_hip_pfb_transform_batch: polyphase filter-bank analysis.  `prototype` holds taps * N coefficients; frame f folds the
+        taps * N samples from f * hop on onto N points (u[j] = sum_p prototype[p N + j] x[f hop + p N + j]) and forward-transforms them.
+        Tensor conventions of frames_transform_batch: returns [nsignals,] nframes, row]; `out` may have padded rows."""
+        import torch
+        spp = 2 if self.transform_type == COMPLEX else 1
+        nsig, sstride, scalars = self._frames_rows(signal, "signal")
+        samples = scalars // spp
+        assert prototype.is_cuda and prototype.dtype == signal.dtype and prototype.is_contiguous() and prototype.dim() == 1
+        taps = prototype.numel() // self.N
+        assert taps >= 1 and taps * self.N == prototype.numel(), "the prototype holds taps * N coefficients"
+        span = taps * self.N
+        if nframes is None:
+            assert samples >= span, "the signal holds no frame"
+            nframes = (samples - span) // hop + 1
+        assert nframes == 0 or (nframes - 1) * hop + span <= samples, "the signal is shorter than its frames"
+        row = self.frames_out_row(output)
+        if out is None:
+            out = torch.empty((nsig, nframes, row) if signal.dim() == 2 else (nframes, row), dtype=signal.dtype, device=signal.device)
+        assert out.dtype == signal.dtype and out.is_cuda and out.stride(-1) == 1 and out.shape[-1] == row and out.shape[-2] == nframes
+        assert out.dim() == 2 or (out.dim() == 3 and out.shape[0] == nsig)
+        pitch = out.stride(-2) if nframes > 1 else (out.stride(0) if out.dim() == 3 and nsig > 1 else row)
+        assert out.dim() == 2 or nsig == 1 or out.stride(0) == nframes * pitch, "frame v = i nframes + f is written at v * pitch"
+        fn = getattr(self._L, f"{self._pfx}_hip_pfb_transform_batch")
+        _check(fn(self.handle, signal.data_ptr(), sstride, nsig, nframes, hop, prototype.data_ptr(), taps, out.data_ptr(), pitch,
+                  FRAMES_OUTPUTS[output], self._stream()), "hip_pfb_transform_batch")
         return out
 
     def frames_overlap_add_batch(self, spectra, hop, window=None, scaling=1.0, out=None, ordered=False):

@@ -68,7 +68,9 @@ enum AbValue : int {
     AB_NO_ONE_IMAGE = 123,      // the sizes of the single-image kernel (fft_one.h) on the tile / streaming passes they ran on before round 6
     AB_FRAMES_COMPOSED = 124,   // pffft_hip_frames_transform_batch: framing kernel + transform_batch through the frame matrix
     AB_FRAMES_FUSED = 125,      // ... the framed register-tiled kernel wherever it is legal, whatever the measured default of the cell is
-    AB_FAKE_DEVICE = 130,       // the calling thread counts as being on ANOTHER device than its current one (key + 64): exercises the per-device
+    AB_PFB_COMPOSED = 126,      // pffft_hip_pfb_transform_batch: folding kernel + transform_batch through the frame matrix
+    AB_PFB_FUSED = 127,         // ... the folding complex N = 1024 kernel wherever it is legal, whatever the measured default of the cell is
+    AB_FAKE_DEVICE = 130,      // the calling thread counts as being on ANOTHER device than its current one (key + 64): exercises the per-device
                                 // replicas of a shared setup on a box with one GPU (tests/test_gpu_round6.py)
 };
 struct AbSel {
