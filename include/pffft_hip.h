@@ -270,6 +270,49 @@ int pffftd_hip_pfb_transform_batch(PFFFTD_Setup *, const double *signal, size_t 
  * Host arithmetic only; PFFFT_Setup and PFFFTD_Setup handles. */
 const char *pffft_hip_pfb_route(const void *setup, size_t hop, size_t taps, size_t signal_stride, size_t out_stride, int output);
 
+/* Polyphase filter-bank synthesis (weighted overlap-add of PERIODICALLY EXTENDED backward transforms): the way back from the spectra of
+ * pffft_hip_pfb_transform_batch, and pffft_hip_frames_overlap_add_batch with a prototype of taps*N real coefficients instead of a window
+ * of N.  Spectrum v = i*nframes + f (layout by `ordered`, at spectra + v*spectra_stride, 0 = dense) is backward-transformed exactly as
+ * pffft_hip_transform_batch(..., PFFFT_BACKWARD, ordered) does (UNSCALED) into y_f[0..N), and sample s of signal i, for every
+ * s < (nframes-1)*hop + taps*N, is WRITTEN (not accumulated) as
+ *     signal[s] = scaling * ( sum_f prototype[s - f*hop] * y_f[(s - f*hop) mod N] )
+ *                 over the frames with 0 <= s - f*hop < taps*N, f ascending
+ * (complex setups: a sample is an interleaved pair, both scalars take the same real coefficient).  ROUNDING IS PART OF THE CONTRACT:
+ * every product is rounded once, every addition is rounded once, f ascending, the sum started from its first term (no FMA), and the result
+ * is multiplied once by `scaling`.  Samples no frame covers (hop > taps*N) are written as 0.  A gather in a fixed order, no atomics: the
+ * result is deterministic.  Every signal holds (nframes-1)*hop + taps*N samples (checked against signal_stride when nsignals > 1;
+ * signal_stride is not read when nsignals == 1).  It follows that
+ *   (1) taps = 1 with the same coefficients as window is pffft_hip_frames_overlap_add_batch, bit for bit;
+ *   (2) the result equals the sum above evaluated in the setup's type on pffft_hip_transform_batch(BACKWARD)'s own rows, bit for bit, for
+ *       every hop, alignment and kernel form;
+ *   (3) in exact arithmetic the synthesis of pffft_hip_pfb_transform_batch's output (analysis prototype h) is
+ *           out[s] = scaling * N * sum_r x[s + r*N] * sum_f prototype[m] * h[m + r*N],   m = s - f*hop,
+ *       so perfect reconstruction needs sum_f prototype[m]*h[m] = 1/(scaling*N) and sum_f prototype[m]*h[m + r*N] = 0 for r != 0 (a two-tap
+ *       paraunitary prototype at hop = N/2 with scaling = 1/N satisfies both on the interior
+ *       taps*N - hop <= s < (nframes-1)*hop + hop).
+ * There is NO circular shift and NO per-frame phase rotation: y_f is taken phase-referenced to the frame's FIRST sample - as the output
+ * of the analysis entry is.  A caller who rotated bin k of frame f by exp(-2 pi i k f hop / N) (or circularly shifted u_f) for channel
+ * phases that are continuous from frame to frame undoes that itself before this call.
+ * Arguments and strides are those of pffft_hip_frames_overlap_add_batch; all pointers are device pointers, the call is asynchronous on
+ * `stream`; 0, else a hipError_t with its text in pffft_hip_last_error().  spectra, prototype and signal must not overlap.
+ * Composed, for every setup (real and complex, float and double, every size): backward transforms into the per-stream frame matrix
+ * (pitched spectra through a row kernel first), then an output-stationary gather kernel - 16 bytes of the output per thread where hop*spp,
+ * signal_stride and the row are multiples of 16 bytes and signal and prototype are aligned (16 bytes; the prototype of a complex setup: 8),
+ * one scalar per thread otherwise, the same arithmetic in both.  The frame matrix, its 256 MiB cap, the mutex and the rule during HIP
+ * graph capture (growth -> hipErrorStreamCaptureUnsupported, nothing launched) are those of the frame entries.  Beyond the cap the call
+ * goes signal by signal in runs of frames; a run re-transforms the ceil(taps*N/hop) - 1 earlier frames that reach into its samples and is
+ * never shorter than that, so where that many frames + 1 do not fit under the cap THE MATRIX IS AS LARGE AS THEY NEED (at most twice that
+ * many rows).
+ * Validation happens before any device is touched: a NULL or foreign setup or the other precision's handle, hop == 0, taps == 0,
+ * prototype == NULL, a spectra_stride smaller than a row, a signal_stride smaller than one signal's scalars when nsignals > 1, a NULL
+ * spectra / signal -> non-zero, nothing launched.  nsignals == 0 or nframes == 0 -> 0, nothing launched. */
+int pffft_hip_pfb_synthesis_batch(PFFFT_Setup *, const float *spectra, size_t spectra_stride, size_t nsignals, size_t nframes,
+                                  size_t hop, const float *prototype, size_t taps, float scaling,
+                                  float *signal, size_t signal_stride, int ordered, void *stream);
+int pffftd_hip_pfb_synthesis_batch(PFFFTD_Setup *, const double *spectra, size_t spectra_stride, size_t nsignals, size_t nframes,
+                                   size_t hop, const double *prototype, size_t taps, double scaling,
+                                   double *signal, size_t signal_stride, int ordered, void *stream);
+
 /* Overlap-save FIR on device-resident signal/output (same block schedule as pffastconv_apply,
  * src/pffastconv.c:204-261): returns the number of output samples written, or -1 on error. */
 int pffastconv_hip_apply_device(PFFASTCONV_Setup *, const float *d_input, int inputLen, float *d_output,

@@ -86,6 +86,9 @@ def lib():
         g("hip_frames_overlap_add_batch").restype = C.c_int
         g("hip_frames_overlap_add_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
                                                       C.c_void_p, ct, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+        g("hip_pfb_synthesis_batch").restype = C.c_int
+        g("hip_pfb_synthesis_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
+                                                 C.c_void_p, C.c_size_t, ct, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
         getattr(L, f"validate_{pfx}_simd").restype = C.c_int
         getattr(L, f"validate_{pfx}_simd_ex").restype = C.c_int
         getattr(L, f"validate_{pfx}_simd_ex").argtypes = [C.c_void_p]
@@ -427,6 +430,31 @@ class Setup:
         fn = getattr(self._L, f"{self._pfx}_hip_frames_overlap_add_batch")
         _check(fn(self.handle, spectra.data_ptr(), pitch, nsig, nframes, hop, window.data_ptr() if window is not None else None,
                   float(scaling), out.data_ptr(), ostride, int(bool(ordered)), self._stream()), "hip_frames_overlap_add_batch")
+        return out
+
+    def pfb_synthesis_batch(self, spectra, hop, prototype, scaling=1.0, out=None, ordered=False):
+        """pffft_hip_pfb_synthesis_batch: polyphase filter-bank synthesis.  spectra [nsignals,] nframes, N or 2N scalars] (stride(-2) = row
+        pitch) are backward transformed (unscaled), periodically extended over the taps * N coefficients of `prototype` and overlap-added
+        every `hop` samples: out[s] = scaling * sum_f prototype[s - f hop] y_f[(s - f hop) mod N].  Tensor conventions of
+        frames_overlap_add_batch: returns [nsignals,] ((nframes - 1) hop + taps N) spp scalars]; `out` may have a padded row stride."""
+        import torch
+        spp = 2 if self.transform_type == COMPLEX else 1
+        assert spectra.is_cuda and spectra.dim() in (2, 3) and spectra.stride(-1) == 1 and spectra.shape[-1] == self.vec_scalars
+        assert prototype.is_cuda and prototype.dtype == spectra.dtype and prototype.is_contiguous() and prototype.dim() == 1
+        taps = prototype.numel() // self.N
+        assert taps >= 1 and taps * self.N == prototype.numel(), "the prototype holds taps * N coefficients"
+        nframes = spectra.shape[-2]
+        nsig = spectra.shape[0] if spectra.dim() == 3 else 1
+        pitch = spectra.stride(-2) if nframes > 1 else (spectra.stride(0) if spectra.dim() == 3 and nsig > 1 else self.vec_scalars)
+        assert spectra.dim() == 2 or nsig == 1 or spectra.stride(0) == nframes * pitch
+        scalars = ((nframes - 1) * hop + taps * self.N) * spp if nframes else 0
+        if out is None:
+            out = torch.empty((nsig, scalars) if spectra.dim() == 3 else (scalars,), dtype=spectra.dtype, device=spectra.device)
+        osig, ostride, oscalars = self._frames_rows(out, "out")
+        assert osig == nsig and oscalars >= scalars
+        fn = getattr(self._L, f"{self._pfx}_hip_pfb_synthesis_batch")
+        _check(fn(self.handle, spectra.data_ptr(), pitch, nsig, nframes, hop, prototype.data_ptr(), taps, float(scaling), out.data_ptr(),
+                  ostride, int(bool(ordered)), self._stream()), "hip_pfb_synthesis_batch")
         return out
 
     # ---------------- host (numpy): the legacy single-vector entries ----------------

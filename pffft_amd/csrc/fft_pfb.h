@@ -1,5 +1,6 @@
-// Polyphase filter-bank analysis (pffft_hip_pfb_transform_batch): the kernels.
+// Polyphase filter bank (pffft_hip_pfb_transform_batch, pffft_hip_pfb_synthesis_batch): the kernels.
 //
+// ANALYSIS
 //   u_f[j] = sum over p < taps, p ascending, of  h[p N + j] * x[f hop + p N + j]     (every product and every addition rounded once,
 //                                                                                     the sum started from its first term)
 //   out_f  = forward transform of u_f
@@ -17,9 +18,20 @@
 //                          the first PFB_SLOTS taps of the NEXT frame, which are in flight while part B finishes this one.
 //   pfb_fold_kernel        the streaming kernel of the COMPOSED route: folded frames -> dense rows of the frame matrix.  Rows are
 //                          mapped to groups of threads of a workgroup (one division per row and thread, not per unit), units of U scalars.
+//
+// SYNTHESIS
+//   signal[s] = scaling * ( sum over f ascending, 0 <= s - f hop < taps N, of  g[s - f hop] * y_f[(s - f hop) mod N] )
+//                                                                                    (every product and every addition rounded once,
+//                                                                                     the sum started from its first term; 0 where no
+//                                                                                     frame covers s)
+//   pfb_syn_kernel         the output-stationary gather behind the backward transforms: a thread owns units of U scalars of the output
+//                          and loops over the covering frames.  WIDE form (U = 16 bytes) where every offset allows 16-byte accesses,
+//                          SCALAR form (U = 1) for everything else; the arithmetic of a scalar is the same in both.  XCD = 1 maps every
+//                          eighth of a sweep of the grid's tiles to one XCD (xcd_local of fft_fir.h); XCD = 0 is the plain grid stride.
 #pragma once
 #include "fft_c1024.h"
 #include "fft_frames.h"
+#include "fft_fir.h"
 
 namespace pf {
 
@@ -158,6 +170,97 @@ pfb_fold_kernel(const T* __restrict__ signal, size_t signal_stride, size_t nfram
                 __builtin_memcpy(&c, acc, 16);
                 *reinterpret_cast<vec4<float>*>(d + j) = c;
             }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ synthesis
+// a / b and the remainder: 32-bit division wherever both fit (the common case), 64-bit otherwise
+__device__ __forceinline__ size_t pfb_udiv(size_t a, size_t b, size_t& rem) {
+    if (((a | b) >> 32) == 0) {
+        const unsigned q = (unsigned)a / (unsigned)b;
+        rem = (unsigned)a - q * (unsigned)b;
+        return q;
+    }
+    const size_t q = a / b;
+    rem = a - q * b;
+    return q;
+}
+
+// U consecutive scalars as ONE access (16 bytes: U = 4 floats / 2 doubles; 8 bytes: 2 floats), or one scalar
+template <typename T, int U>
+__device__ __forceinline__ void pfb_load(T (&a)[U], const T* p) {
+    if constexpr (U == 1) a[0] = p[0];
+    else if constexpr (sizeof(T) * U == 16) {
+        const vec4<float> c = *reinterpret_cast<const vec4<float>*>(p);
+        __builtin_memcpy(a, &c, 16);
+    } else {
+        static_assert(sizeof(T) * U == 8, "8- and 16-byte units only");
+        const vec2<float> c = *reinterpret_cast<const vec2<float>*>(p);
+        __builtin_memcpy(a, &c, 8);
+    }
+}
+
+// Scalars s0 spp ... s1 spp - 1 of every signal, as units of U scalars (the wide form's conditions are the host's: hop spp, signal_stride
+// and row are multiples of U and every pointer is aligned, so that the scalars of a unit share their frames and neither a frame's edge nor
+// the wrap at N falls inside a unit).  `y` holds the backward-transformed frames fbase ... of every signal as dense rows (`fpitch` rows per
+// signal); frames f < nframes exist.  span = taps N samples, hop_mod = (hop spp) mod (N spp).  Per unit: the divisions that split the unit
+// index and find the first and the last covering frame; inside the f loop the position in the prototype falls by hop and the position in
+// the row is carried modulo N with one compare - no division.
+template <typename T, int U, int SPP, int XCD>
+__global__ void __launch_bounds__(256)
+pfb_syn_kernel(const T* __restrict__ y, size_t fbase, size_t fpitch, size_t nframes, size_t hop, unsigned N, size_t span, unsigned hop_mod,
+               const T* __restrict__ g, T scaling, T* __restrict__ signal, size_t signal_stride, size_t nsignals, size_t s0, size_t s1) {
+    constexpr int GU = U >= SPP ? U / SPP : 1;    // prototype values per unit
+    const unsigned row = N * SPP;
+    const size_t hop_s = hop * SPP;
+    const size_t ups = (s1 - s0) * SPP / U, units = nsignals * ups;
+    const size_t tiles = (units + 255) / 256;
+    const unsigned pos = XCD ? xcd_local(blockIdx.x, gridDim.x) : blockIdx.x;
+    for (size_t t0 = 0; t0 < tiles; t0 += gridDim.x) {
+        const size_t x = (t0 + pos) * 256 + threadIdx.x;
+        if (x >= units) continue;
+        size_t u;
+        const size_t i = pfb_udiv(x, ups, u);
+        const size_t e = s0 * SPP + u * U, s = e / SPP;
+        size_t r;
+        size_t fhi = pfb_udiv(s, hop, r);
+        if (fhi > nframes - 1) fhi = nframes - 1;
+        const size_t flo = s < span ? 0 : pfb_udiv(s - span, hop, r) + 1;
+        T acc[U];
+#pragma unroll
+        for (int k = 0; k < U; ++k) acc[k] = (T)0;
+        bool first = true;
+        if (flo <= fhi) {
+            size_t m = e - flo * hop_s;     // scalars from the start of frame flo: < span SPP
+            size_t jr;
+            pfb_udiv(m, row, jr);
+            unsigned j = (unsigned)jr;      // ... modulo the row
+            const T* yp = y + (i * fpitch + (flo - fbase)) * row;
+            for (size_t f = flo; f <= fhi; ++f) {
+                T yv[U], gv[GU];
+                pfb_load<T, U>(yv, yp + j);
+                pfb_load<T, GU>(gv, g + m / SPP);
+#pragma unroll
+                for (int k = 0; k < U; ++k) {
+                    const T term = gv[U >= SPP ? k / SPP : 0] * yv[k];
+                    acc[k] = first ? term : acc[k] + term;
+                }
+                first = false;
+                m -= hop_s;
+                j = j >= hop_mod ? j - hop_mod : j + (row - hop_mod);
+                yp += row;
+            }
+        }
+        T o[U];
+#pragma unroll
+        for (int k = 0; k < U; ++k) o[k] = first ? (T)0 : scaling * acc[k];
+        T* dst = signal + i * signal_stride + e;
+        if constexpr (U == 1) __builtin_nontemporal_store(o[0], dst);
+        else {
+            vec4<float> c;
+            __builtin_memcpy(&c, o, 16);
+            __builtin_nontemporal_store(c, reinterpret_cast<vec4<float>*>(dst));
         }
     }
 }

@@ -70,6 +70,9 @@ enum AbValue : int {
     AB_FRAMES_FUSED = 125,      // ... the framed register-tiled kernel wherever it is legal, whatever the measured default of the cell is
     AB_PFB_COMPOSED = 126,      // pffft_hip_pfb_transform_batch: folding kernel + transform_batch through the frame matrix
     AB_PFB_FUSED = 127,         // ... the folding complex N = 1024 kernel wherever it is legal, whatever the measured default of the cell is
+    AB_PFB_SYN_SCALAR = 128,    // pffft_hip_pfb_synthesis_batch: the scalar form of the gather also where the wide one is legal (same arithmetic)
+    AB_PFB_SYN_PLAIN = 129,     // ... the gather's tiles on the plain grid stride, whatever the measured default is (same arithmetic)
+    AB_PFB_SYN_XCD = 131,       // ... the gather's tiles in XCD-contiguous sweeps, whatever the measured default is (same arithmetic)
     AB_FAKE_DEVICE = 130,      // the calling thread counts as being on ANOTHER device than its current one (key + 64): exercises the per-device
                                 // replicas of a shared setup on a box with one GPU (tests/test_gpu_round6.py)
 };

@@ -1,12 +1,13 @@
-// libpffft_hip.so, translation unit of the polyphase filter-bank analysis (include/pffft_hip.h: pffft_hip_pfb_transform_batch,
-// pffft_hip_pfb_route): validation, route decision, the fused complex N = 1024 kernel's launch and the composed route through the
-// per-stream frame matrix (pf::Setup::frames, shared with the frame entries of frames_tu.hip).  Kernels: fft_pfb.h.
+// libpffft_hip.so, translation unit of the polyphase filter bank (include/pffft_hip.h: pffft_hip_pfb_transform_batch,
+// pffft_hip_pfb_route, pffft_hip_pfb_synthesis_batch): validation, route decision, the fused complex N = 1024 kernel's launch and the
+// composed routes through the per-stream frame matrix (pf::Setup::frames and its helpers: frames_host.h, shared with the frame entries of
+// frames_tu.hip).  Kernels: fft_pfb.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "../../include/pffft_hip.h"
-#include "pf_host.h"
+#include "frames_host.h"
 #include "fft_pfb.h"
 
 struct PFFFT_Setup : pf::Setup {};
@@ -17,14 +18,6 @@ struct PFFFTD_Setup : pf::Setup {};
 static_assert(pf::PFB_FUSED_MAX_TAPS == PFFFT_HIP_PFB_FUSED_MAX_TAPS, "the header's constant is the kernel's");
 
 namespace pf {
-
-// the cap of the frame matrix of one composed launch sequence (include/pffft_hip.h; the value of the frame entries)
-constexpr size_t PFB_CAP_BYTES = (size_t)256 << 20;
-
-static int bad(const char* what, hipError_t e = hipErrorInvalidValue) {
-    g_last_error = std::string("pffft_hip: ") + what;
-    return (int)e;
-}
 
 static bool aligned_to(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
@@ -72,28 +65,8 @@ static int launch_pfb_c1024(Setup* s, const float* signal, size_t signal_stride,
     return 0;
 }
 
-// ------------------------------------------------------------------------------------------------ composed pieces
-// the frame matrix of `st` (frames.mu held by the caller), grown to `bytes`: outside graph capture only
-static int pfb_buffer(Setup* s, hipStream_t st, size_t bytes, void** buf) {
-    StreamScratch::Entry& sc = s->frames.acquire(st);
-    if (sc.buf[0].bytes() < bytes && stream_capturing(st))
-        return bad("the frame matrix of this stream would have to grow during graph capture: run the call once on this stream before capturing",
-                   hipErrorStreamCaptureUnsupported);
-    if (int rc = s->frames.grow(sc, 0, bytes)) return rc;
-    *buf = sc.buf[0].get();
-    return 0;
-}
-
-template <typename T, int MODE>
-static int launch_rows(const T* src, size_t src_stride, T* dst, size_t dst_stride, size_t count, size_t row, hipStream_t st) {
-    const size_t per = MODE == 0 ? row : MODE == 1 ? row / 2 + 1 : row / 2;
-    const size_t grid = std::max<size_t>(1, std::min<size_t>((count * per + 255) / 256, (size_t)num_cus() * 16));
-    hipLaunchKernelGGL((frames_rows_kernel<T, MODE>), dim3((unsigned)grid), dim3(256), 0, st, src, src_stride, dst, dst_stride, count,
-                       (unsigned)row);
-    PF_CHECK(hipGetLastError());
-    return 0;
-}
-
+// ------------------------------------------------------------------------------------------------ composed pieces (frames_host.h: the
+// frame matrix, the row kernel's launch)
 template <typename T, int U>
 static int launch_fold(const T* signal, size_t signal_stride, size_t nframes, size_t hop_s, int spp, const T* prototype, size_t taps, T* X,
                        size_t v0, size_t cnt, size_t row, hipStream_t st) {
@@ -156,13 +129,13 @@ static int pfb_transform_batch(Setup* s, const T* signal, size_t signal_stride, 
         }
     }
 
-    // composed: folded frames -> frame matrix (chunks of at most PFB_CAP_BYTES), transform_batch, then rows -> out where `out` is not the
+    // composed: folded frames -> frame matrix (chunks of at most FRAMES_CAP_BYTES), transform_batch, then rows -> out where `out` is not the
     // dense spectrum
-    const size_t chunk = std::max<size_t>(1, std::min(batch, PFB_CAP_BYTES / (row * sizeof(T))));
+    const size_t chunk = std::max<size_t>(1, std::min(batch, FRAMES_CAP_BYTES / (row * sizeof(T))));
     const bool direct = output != FR_POWER && out_stride == row;
     std::lock_guard<std::mutex> lk(s->frames.mu);
     void* buf = nullptr;
-    if ((rc = pfb_buffer(s, st, chunk * row * sizeof(T), &buf))) return rc;
+    if ((rc = frames_buffer(s, st, chunk * row * sizeof(T), &buf))) return rc;
     T* X = (T*)buf;
     constexpr int U = 16 / (int)sizeof(T);
     const bool wide = aligned_to(signal, 16) && signal_stride % U == 0 && hop_s % U == 0 && row % U == 0;
@@ -179,6 +152,95 @@ static int pfb_transform_batch(Setup* s, const T* signal, size_t signal_stride, 
         else rc = launch_rows<T, 2>(X, row, dst, out_stride, cnt, row, st);
         if (rc) return rc;
     }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ synthesis
+// Mapping of the gather's tiles onto workgroups where no selector asks for one: the plain grid stride (false) or XCD-contiguous sweeps
+// (true) - whichever tools/pfb_synth_bench.py measured faster on the MI355X.
+constexpr bool PFB_SYN_XCD_DEFAULT = false;
+
+template <typename T, int U, int SPP>
+static int launch_syn_form(bool xcd, const T* y, size_t fbase, size_t fpitch, size_t nframes, size_t hop, size_t N, size_t span,
+                           const T* g, T scaling, T* signal, size_t signal_stride, size_t nsignals, size_t s0, size_t s1, hipStream_t st) {
+    const size_t units = nsignals * ((s1 - s0) * SPP / U);
+    if (units == 0) return 0;
+    const unsigned hop_mod = (unsigned)((hop * SPP) % (N * SPP));
+    auto k = xcd ? pfb_syn_kernel<T, U, SPP, 1> : pfb_syn_kernel<T, U, SPP, 0>;
+    hipLaunchKernelGGL(k, dim3(stream_grid(units)), dim3(256), 0, st, y, fbase, fpitch, nframes, hop, (unsigned)N, span, hop_mod, g, scaling,
+                       signal, signal_stride, nsignals, s0, s1);
+    PF_CHECK(hipGetLastError());
+    return 0;
+}
+
+struct SynForm { bool wide, xcd; };
+
+template <typename T>
+static int launch_syn(SynForm form, size_t spp, const T* y, size_t fbase, size_t fpitch, size_t nframes, size_t hop, size_t N, size_t span,
+                      const T* g, T scaling, T* signal, size_t signal_stride, size_t nsignals, size_t s0, size_t s1, hipStream_t st) {
+    constexpr int U = 16 / (int)sizeof(T);
+#define PF_SYN(UU, SS) launch_syn_form<T, UU, SS>(form.xcd, y, fbase, fpitch, nframes, hop, N, span, g, scaling, signal, signal_stride, nsignals, s0, s1, st)
+    if (spp == 1) return form.wide ? PF_SYN(U, 1) : PF_SYN(1, 1);
+    return form.wide ? PF_SYN(U, 2) : PF_SYN(1, 2);
+#undef PF_SYN
+}
+
+template <typename T>
+static int pfb_synthesis_batch(Setup* s, const T* spectra, size_t spectra_stride, size_t nsignals, size_t nframes, size_t hop,
+                               const T* prototype, size_t taps, T scaling, T* signal, size_t signal_stride, int ordered, hipStream_t st) {
+    if (!s || s->magic != MAGIC || s->is_double != (sizeof(T) == 8)) {
+        g_last_error = "pffft_hip: bad setup handle";
+        return (int)hipErrorInvalidHandle;
+    }
+    if (hop == 0) return bad("pfb synthesis: hop == 0");
+    if (taps == 0) return bad("pfb synthesis: taps == 0");
+    if (!prototype) return bad("pfb synthesis: NULL prototype");
+    if (nsignals == 0 || nframes == 0) return 0;
+    const bool real = s->transform == PFFFT_REAL;
+    const size_t spp = real ? 1 : 2, N = (size_t)s->N, row = s->vec_scalars, span = taps * N;
+    if (spectra_stride == 0) spectra_stride = row;
+    if (spectra_stride < row) return bad("pfb synthesis: spectra_stride smaller than one spectrum");
+    const size_t samples = (nframes - 1) * hop + span;
+    if (nsignals > 1 && signal_stride < samples * spp) return bad("pfb synthesis: signal_stride smaller than one signal's samples");
+    if (!spectra || !signal) return bad("pfb synthesis: NULL spectra / signal");
+    if (nsignals == 1) signal_stride = 0;   // (one signal: the stride is not read)
+
+    s = for_device(s);
+    int rc = ensure_device_any(s);
+    if (rc) return rc;
+    const AbSel sel = ab();
+    constexpr size_t U = 16 / sizeof(T);
+    SynForm form;
+    // wide: every unit of 16 bytes lies inside one frame's span and one period of it, and every access is aligned (the frame matrix is an
+    // allocation of its own); the prototype is read GU = U / spp values at a time
+    form.wide = !sel.is(AB_PFB_SYN_SCALAR) && (hop * spp) % U == 0 && signal_stride % U == 0 && row % U == 0 && aligned_to(signal, 16) &&
+                aligned_to(prototype, real ? 16 : sizeof(T) * (U / 2));
+    form.xcd = sel.is(AB_PFB_SYN_XCD) || (PFB_SYN_XCD_DEFAULT && !sel.is(AB_PFB_SYN_PLAIN));
+    const size_t batch = nsignals * nframes, cap_rows = std::max<size_t>(1, FRAMES_CAP_BYTES / (row * sizeof(T)));
+    std::lock_guard<std::mutex> lk(s->frames.mu);
+    void* buf = nullptr;
+    if (batch <= cap_rows) {   // every frame at once, one gather
+        if ((rc = frames_buffer(s, st, batch * row * sizeof(T), &buf))) return rc;
+        T* X = (T*)buf;
+        if ((rc = frames_backward<T>(s, spectra, spectra_stride, 0, batch, X, ordered, st))) return rc;
+        return launch_syn<T>(form, spp, X, 0, nframes, nframes, hop, N, span, prototype, scaling, signal, signal_stride, nsignals, 0, samples, st);
+    }
+    // beyond the cap: signal by signal, each in runs of frames.  A run owns the samples from its first frame's start to the next run's
+    // first frame's start (the last run: to the end) and re-transforms the up to `reach` earlier frames that reach into them; a run is at
+    // least `reach` frames long, so that the re-transformed frames never outnumber the new ones - where reach + 1 rows alone do not fit
+    // under the cap the matrix is as large as that takes (at most 2 reach rows).
+    const size_t reach = (span + hop - 1) / hop - 1;
+    const size_t run = std::max<size_t>(std::max<size_t>(cap_rows > reach ? cap_rows - reach : 1, reach), 1);
+    if ((rc = frames_buffer(s, st, std::min(nframes, run + reach) * row * sizeof(T), &buf))) return rc;
+    T* X = (T*)buf;
+    for (size_t i = 0; i < nsignals; ++i)
+        for (size_t fa = 0; fa < nframes; fa += run) {
+            const size_t fb = std::min(nframes, fa + run), f0 = fa > reach ? fa - reach : 0;
+            if ((rc = frames_backward<T>(s, spectra, spectra_stride, i * nframes + f0, fb - f0, X, ordered, st))) return rc;
+            const size_t s0 = fa * hop, s1 = fb == nframes ? samples : fb * hop;
+            if ((rc = launch_syn<T>(form, spp, X, f0, 0, fb, hop, N, span, prototype, scaling, signal + i * signal_stride, 0, 1, s0, s1, st)))
+                return rc;
+        }
     return 0;
 }
 
@@ -203,4 +265,17 @@ PF_EXPORT const char* pffft_hip_pfb_route(const void* setup, size_t hop, size_t 
     const bool real = s->transform == PFFFT_REAL;
     if (out_stride == 0) out_stride = output == pf::FR_POWER ? (real ? (size_t)s->N / 2 + 1 : (size_t)s->N) : s->vec_scalars;
     return pf::pfb_route_fused(s, hop, taps, signal_stride, out_stride, output, pf::ab()) ? "fused" : "composed";
+}
+
+PF_EXPORT int pffft_hip_pfb_synthesis_batch(PFFFT_Setup* s, const float* spectra, size_t spectra_stride, size_t nsignals, size_t nframes,
+                                            size_t hop, const float* prototype, size_t taps, float scaling, float* signal,
+                                            size_t signal_stride, int ordered, void* stream) {
+    return pf::pfb_synthesis_batch<float>(s, spectra, spectra_stride, nsignals, nframes, hop, prototype, taps, scaling, signal, signal_stride,
+                                          ordered, (hipStream_t)stream);
+}
+PF_EXPORT int pffftd_hip_pfb_synthesis_batch(PFFFTD_Setup* s, const double* spectra, size_t spectra_stride, size_t nsignals, size_t nframes,
+                                             size_t hop, const double* prototype, size_t taps, double scaling, double* signal,
+                                             size_t signal_stride, int ordered, void* stream) {
+    return pf::pfb_synthesis_batch<double>(s, spectra, spectra_stride, nsignals, nframes, hop, prototype, taps, scaling, signal, signal_stride,
+                                           ordered, (hipStream_t)stream);
 }
