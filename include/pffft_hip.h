@@ -313,6 +313,54 @@ int pffftd_hip_pfb_synthesis_batch(PFFFTD_Setup *, const double *spectra, size_t
                                    size_t hop, const double *prototype, size_t taps, double scaling,
                                    double *signal, size_t signal_stride, int ordered, void *stream);
 
+/* Complex transforms of ANY length 1 <= N <= 2^25 (Bluestein's algorithm on the library's own convolution).  pffft_new_setup keeps
+ * the reference's rule (N = 2^a 3^b 5^c, a multiple of 16 / 32, else NULL); padding to pffft_nearest_transform_size changes the bin
+ * spacing, so it is no answer to "the DFT of these 1000, 1021 or 10007 samples".  This setup type is:
+ *     out[v][k] = sum_n in[v][n] * exp(-/+ 2 pi j n k / N),   k < N     (forward / backward; UNSCALED: backward(forward(x)) = N x)
+ * Rows are N interleaved complex values, dense; there is no internal layout for this setup type.  PFFFT_COMPLEX only - PFFFT_REAL is
+ * reserved and returns NULL today, like N < 1 and N > 2^25.  Creating a setup touches no device.  in / out are device pointers, 16-byte
+ * (float) / 32-byte (double) aligned like the other batched entries' (rows of odd N are then aligned to one complex value only, which
+ * every kernel here copes with; a base pointer aligned to one complex value is accepted on the fused and composed routes).  in == out is
+ * allowed; otherwise they must not overlap.  The call is asynchronous on `stream`; 0, else a hipError_t with its text in
+ * pffft_hip_last_error().  Validation happens before any device is touched: a NULL or foreign handle or the other precision's, a bad
+ * direction, NULL or misaligned in / out -> non-zero, nothing launched.
+ * Routes, planned once at setup (pffft_hip_any_route names the one a call takes under the calling thread's selector):
+ *   "direct"    N is itself a legal complex size: pffft[d]_hip_transform_batch(..., ordered = 1) on an inner setup, bit for bit.
+ *   "fused"     float and M = the next power of two >= 2N - 1 is 512, 1024, 2048 or 4096 (N = 129 ... 2047): ONE kernel - the fused
+ *               convolution kernel of pffft_hip_convolve_batch with a chirping, zero-padding loader and a chirping, cropping store: N
+ *               samples read and N written per vector.  The default wherever it is legal.
+ *   "composed"  everything else (double, N outside the fused set; selector 132 everywhere): a chirp-and-pad kernel into a per-stream scratch
+ *               image of batch x M, pffft[d]_hip_convolve_batch on an inner setup of length M with one broadcast filter spectrum, a
+ *               chirp-and-crop kernel.  M is pffft_nearest_transform_size(2N - 1, PFFFT_COMPLEX, higher); a setup that can run fused uses its power of two on both routes.
+ * The scratch image follows the rules of the other per-stream scratch: at most 256 MiB (one row where a row is longer), longer batches go
+ * through it in chunks on `stream`; it grows outside HIP graph capture only - a call that would have to grow it while `stream` is
+ * capturing fails with hipErrorStreamCaptureUnsupported and launches nothing.
+ * THE FIRST CALL ON A SETUP BUILDS ITS TABLES (the chirp w[n] = exp(-j pi (n^2 mod 2N) / N) - the reduction in 64-bit integers, the angle
+ * in long double, rounded once - and the filter's spectrum, computed with the double transform also for float setups): it allocates and
+ * synchronises the device, so like the first call on a CIC state it must happen BEFORE a stream capture (during one it fails with
+ * hipErrorStreamCaptureUnsupported).  batch == 0 builds the tables, launches nothing else and returns 0.  The backward direction uses the
+ * same tables (both ends conjugate).  A setup serves ONE device, like PFFASTCONV_Setup: the device that is current at the first call; a
+ * call from a thread whose current device is another one fails with hipErrorInvalidDevice.  Any number of streams and threads of that
+ * device may share it. */
+typedef struct PFFFT_HIP_AnySetup PFFFT_HIP_AnySetup;
+typedef struct PFFFTD_HIP_AnySetup PFFFTD_HIP_AnySetup;
+PFFFT_HIP_AnySetup *pffft_hip_any_new_setup(int N, pffft_transform_t transform);
+PFFFTD_HIP_AnySetup *pffftd_hip_any_new_setup(int N, pffft_transform_t transform);
+void pffft_hip_any_destroy_setup(PFFFT_HIP_AnySetup *);     /* NULL-safe */
+void pffftd_hip_any_destroy_setup(PFFFTD_HIP_AnySetup *);
+int pffft_hip_any_transform_batch(PFFFT_HIP_AnySetup *, const float *in, float *out, size_t batch, pffft_direction_t direction,
+                                  void *stream);
+int pffftd_hip_any_transform_batch(PFFFTD_HIP_AnySetup *, const double *in, double *out, size_t batch, pffft_direction_t direction,
+                                   void *stream);
+/* Host arithmetic only, handles of both precisions.  pffft_hip_any_conv_size: the convolution length M; 0 on the direct route; -1 for an
+ * invalid handle.  pffft_hip_any_route: "direct" / "fused" / "composed" under the calling thread's selector (pffft_hip_set_variant:
+ * 132 = never fused, 133 = fused wherever it is legal); "" for an invalid handle.  pffft_hip_any_chirp: the N chirp values w[n] as
+ * interleaved (re, im) pairs of the setup's type into host_out, as the device table holds them; 0, non-zero for an invalid handle or a
+ * NULL host_out. */
+int pffft_hip_any_conv_size(const void *setup);
+const char *pffft_hip_any_route(const void *setup);
+int pffft_hip_any_chirp(const void *setup, void *host_out);
+
 /* Overlap-save FIR on device-resident signal/output (same block schedule as pffastconv_apply,
  * src/pffastconv.c:204-261): returns the number of output samples written, or -1 on error. */
 int pffastconv_hip_apply_device(PFFASTCONV_Setup *, const float *d_input, int inputLen, float *d_output,

@@ -89,6 +89,10 @@ def lib():
         g("hip_pfb_synthesis_batch").restype = C.c_int
         g("hip_pfb_synthesis_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
                                                  C.c_void_p, C.c_size_t, ct, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+        g("hip_any_new_setup").restype = C.c_void_p; g("hip_any_new_setup").argtypes = [C.c_int, C.c_int]
+        g("hip_any_destroy_setup").restype = None; g("hip_any_destroy_setup").argtypes = [C.c_void_p]
+        g("hip_any_transform_batch").restype = C.c_int
+        g("hip_any_transform_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
         getattr(L, f"validate_{pfx}_simd").restype = C.c_int
         getattr(L, f"validate_{pfx}_simd_ex").restype = C.c_int
         getattr(L, f"validate_{pfx}_simd_ex").argtypes = [C.c_void_p]
@@ -111,6 +115,9 @@ def lib():
     L.pffft_hip_frames_route.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int]
     L.pffft_hip_pfb_route.restype = C.c_char_p
     L.pffft_hip_pfb_route.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int]
+    L.pffft_hip_any_conv_size.restype = C.c_int; L.pffft_hip_any_conv_size.argtypes = [C.c_void_p]
+    L.pffft_hip_any_route.restype = C.c_char_p; L.pffft_hip_any_route.argtypes = [C.c_void_p]
+    L.pffft_hip_any_chirp.restype = C.c_int; L.pffft_hip_any_chirp.argtypes = [C.c_void_p, C.c_void_p]
     L.pffft_hip_kernel_name.restype = C.c_char_p; L.pffft_hip_kernel_name.argtypes = [C.c_void_p]
     L.pffft_hip_describe.restype = C.c_int; L.pffft_hip_describe.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.pffft_hip_setup_devices.restype = C.c_int; L.pffft_hip_setup_devices.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_int]
@@ -217,6 +224,12 @@ def pfb_route(setup: "Setup", hop, taps, signal_stride=0, out_stride=0, output="
     selector.  Host arithmetic only."""
     return lib().pffft_hip_pfb_route(setup.handle, int(hop), int(taps), int(signal_stride), int(out_stride),
                                      FRAMES_OUTPUTS[output]).decode()
+
+
+def any_route(setup: "AnySetup") -> str:
+    """pffft_hip_any_route: "direct" / "fused" / "composed" for an any-length setup under the calling thread's selector.  Host
+    arithmetic only."""
+    return lib().pffft_hip_any_route(setup.handle).decode()
 
 
 def _is_torch(x) -> bool:
@@ -500,6 +513,64 @@ class Setup:
         getattr(self._L, f"{self._pfx}_{name}")(self.handle, pa.ctypes.data, pb.ctypes.data, pab.ctypes.data,
                                                  self.dtype.type(scaling))
         return pab
+
+
+class AnySetup:
+    """PFFFT_HIP_AnySetup / PFFFTD_HIP_AnySetup: complex transforms of any length 1 <= N <= 2^25 (include/pffft_hip.h).  Raises ValueError
+    where pffft_hip_any_new_setup returns NULL.  Rows are N interleaved complex values (2N scalars), dense."""
+
+    def __init__(self, N: int, transform: int = COMPLEX, dtype=np.float32):
+        self.N, self.transform_type, self.dtype = int(N), int(transform), np.dtype(dtype)
+        self._pfx = _pfx(dtype)
+        self._L = lib()
+        self.handle = getattr(self._L, f"{self._pfx}_hip_any_new_setup")(self.N, self.transform_type)
+        if not self.handle:
+            raise ValueError(f"pffft_hip_any_new_setup({N}, {transform}) returned NULL")
+        self.vec_scalars = 2 * self.N
+
+    def close(self):
+        if getattr(self, "handle", None):
+            getattr(self._L, f"{self._pfx}_hip_any_destroy_setup")(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def conv_size(self) -> int:
+        """The convolution length M (0 on the direct route)."""
+        return int(self._L.pffft_hip_any_conv_size(self.handle))
+
+    @property
+    def route(self) -> str:
+        return any_route(self)
+
+    def chirp(self) -> np.ndarray:
+        """pffft_hip_any_chirp: w[n] = exp(-j pi (n^2 mod 2N) / N) as a complex array of the setup's precision (host arithmetic only)."""
+        out = np.empty(2 * self.N, dtype=self.dtype)
+        rc = self._L.pffft_hip_any_chirp(self.handle, out.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"pffft_hip_any_chirp failed ({rc})")
+        return out.view(np.complex128 if self.dtype == np.float64 else np.complex64)
+
+    def transform_batch(self, x, out=None, direction=FORWARD):
+        """x: CUDA tensor of the setup's dtype holding `batch` rows of 2N scalars; only the extent has to be dense (a view that starts
+        anywhere on the grid of complex values is accepted).  out may be x (in place)."""
+        import torch
+        want = torch.float64 if self.dtype == np.float64 else torch.float32
+        assert x.is_cuda and x.dtype == want and x.is_contiguous() and x.numel() % self.vec_scalars == 0, \
+            "need a contiguous CUDA tensor of the setup dtype holding whole rows"
+        batch = x.numel() // self.vec_scalars
+        if out is None:
+            out = torch.empty_like(x)
+        assert out.is_cuda and out.dtype == want and out.is_contiguous() and out.numel() == x.numel()
+        fn = getattr(self._L, f"{self._pfx}_hip_any_transform_batch")
+        _check(fn(self.handle, x.data_ptr(), out.data_ptr(), batch, direction, C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+               "hip_any_transform_batch")
+        return out
 
 
 class FastConv:

@@ -1,0 +1,327 @@
+// libpffft_hip.so, translation unit of the any-length complex transforms (include/pffft_hip.h: pffft[d]_hip_any_*): Bluestein's algorithm
+// on the library's own convolution.  Plan (route, convolution length) at setup, tables on first use, the fused kernel's launch and the
+// composed route through a per-stream scratch image.  Kernels: fft_any.h.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <memory>
+
+#include "../../include/pffft_hip.h"
+#include "pf_host.h"
+#include "fft_any.h"
+
+struct PFFFT_Setup : pf::Setup {};
+struct PFFFTD_Setup : pf::Setup {};
+
+#define PF_EXPORT extern "C" __attribute__((visibility("default")))
+
+namespace pf {
+
+constexpr uint32_t ANY_MAGIC = 0x50464159u;   // "PFAY"
+constexpr int ANY_MAX_N = 1 << 25;             // M <= 2^26, the library's largest setup
+constexpr size_t ANY_CAP_BYTES = (size_t)256 << 20;   // the scratch image of one composed launch sequence; longer batches go in chunks
+
+enum AnyRoute { ANY_DIRECT = 0, ANY_FUSED = 1, ANY_COMPOSED = 2 };
+
+// One setup serves ONE device, like PFFASTCONV_Setup: the tables are built on the device that is current at the first call, and a call
+// from a thread whose current device is another one is refused.
+struct AnySetup {
+    uint32_t magic = ANY_MAGIC;
+    int N = 0, is_double = 0;
+    AnyRoute route = ANY_DIRECT;   // the default route, fixed at setup
+    int M = 0;                     // convolution length; 0 on the direct route
+    Setup* inner = nullptr;        // length N (direct) or M: a PFFFT_Setup / PFFFTD_Setup, owned
+    std::mutex mu;                 // guards the lazy tables
+    bool ready = false;
+    int device = -1;
+    DevBuf d_chirp;                // w[n], n < N (where the fused kernel is legal: M entries, zero from N on)
+    DevBuf d_H;                    // spectrum of the filter b in the inner setup's internal layout
+    StreamScratch pad;             // batch x M image of the composed route: one per stream, pad.mu held while a call enqueues
+};
+
+static int bad(const char* what, hipError_t e = hipErrorInvalidValue) {
+    g_last_error = std::string("pffft_hip: ") + what;
+    return (int)e;
+}
+
+static AnySetup* any_checked(const void* p) {
+    const AnySetup* a = static_cast<const AnySetup*>(p);
+    return a && a->magic == ANY_MAGIC ? const_cast<AnySetup*>(a) : nullptr;
+}
+
+// ------------------------------------------------------------------------------------------------ plan
+// The fused kernel exists for float and these convolution lengths (M2 = next power of two >= 2N - 1), and it is the default in all of
+// them: per vector it moves 2 N 8 bytes in one launch where the composed route moves 2 N 8 + 4 M 8 in three (the pad image written, read
+// and rewritten by the convolution, read by the crop).  tests/test_gpu_any.py holds it faster than selector 132 in every cell on the
+// device; DESIGN.md §3.12 has the figures.
+static bool any_fused_len(int M) { return M == 512 || M == 1024 || M == 2048 || M == 4096; }
+
+// Composed route: the nearest legal size at or above 2N - 1 (M <= 2^26 for N <= 2^25)
+static int any_composed_len(int N) { return pffft_nearest_transform_size(2 * N - 1, PFFFT_COMPLEX, 1); }
+
+static AnySetup* any_new_setup(int N, int transform, int is_double) {
+    if (transform != PFFFT_COMPLEX || N < 1 || N > ANY_MAX_N) return nullptr;
+    std::unique_ptr<AnySetup> a(new AnySetup);
+    a->N = N; a->is_double = is_double;
+    int len = N;
+    if (pffft_is_valid_size(N, PFFFT_COMPLEX)) {
+        a->route = ANY_DIRECT;
+    } else {
+        long long p2 = 16;
+        while (p2 < 2ll * N - 1) p2 *= 2;
+        const bool fused = !is_double && any_fused_len((int)p2);
+        // (a setup that can run fused runs BOTH routes on M2: one filter spectrum, one answer to pffft_hip_any_conv_size)
+        a->M = len = fused ? (int)p2 : any_composed_len(N);
+        a->route = fused ? ANY_FUSED : ANY_COMPOSED;
+    }
+    a->inner = is_double ? static_cast<Setup*>(pffftd_new_setup(len, PFFFT_COMPLEX)) : static_cast<Setup*>(pffft_new_setup(len, PFFFT_COMPLEX));
+    if (!a->inner) return nullptr;
+    return a.release();
+}
+
+static void any_destroy_setup(AnySetup* a) {
+    if (!a || a->magic != ANY_MAGIC) return;
+    a->magic = 0;
+    if (a->inner) {
+        if (a->is_double) pffftd_destroy_setup(static_cast<PFFFTD_Setup*>(a->inner));
+        else pffft_destroy_setup(static_cast<PFFFT_Setup*>(a->inner));
+    }
+    delete a;
+}
+
+// the route of a call under the calling thread's selector
+static AnyRoute any_route_now(const AnySetup* a, const AbSel& sel) {
+    if (a->route == ANY_FUSED && sel.is(AB_ANY_COMPOSED)) return ANY_COMPOSED;
+    return a->route;   // (AB_ANY_FUSED: every legal cell is fused by default today - the selector pins that against a later cell list)
+}
+
+// ------------------------------------------------------------------------------------------------ tables
+// w[n] = exp(-j pi (n^2 mod 2N) / N): the reduction in 64-bit integers (n < 2^25: n^2 < 2^50), the angle in extended precision, rounded once
+template <typename T>
+static cx<T> chirp_value(unsigned long long n, unsigned long long N) {
+    const unsigned long long r = (n * n) % (2 * N);
+    const long double a = -3.14159265358979323846264338327950288L * (long double)r / (long double)N;
+    cx<T> w;
+    w.x = (T)cosl(a); w.y = (T)sinl(a);
+    return w;
+}
+
+template <typename T>
+static int any_build_tables(AnySetup* a) {
+    const size_t N = (size_t)a->N, M = (size_t)a->M;
+    std::vector<cx<T>> w(a->route == ANY_FUSED ? M : N);
+    for (size_t n = 0; n < N; ++n) w[n] = chirp_value<T>(n, N);
+    for (size_t n = N; n < w.size(); ++n) w[n] = mk<T>(0, 0);
+    int rc = upload_table(a->d_chirp, w);
+    if (rc) return rc;
+    // b[m] = conj(w[m]), m < N; b[M - m] = b[m]; zero elsewhere - in double whatever the setup's type
+    std::vector<cx<double>> b(M);
+    for (size_t m = 0; m < M; ++m) b[m] = mk<double>(0, 0);
+    for (size_t m = 0; m < N; ++m) {
+        const cx<double> c = chirp_value<double>(m, N);
+        b[m] = mk<double>(c.x, -c.y);
+        if (m) b[M - m] = b[m];
+    }
+    if ((rc = a->d_H.grow(M * sizeof(cx<T>)))) return rc;
+    if constexpr (sizeof(T) == 8) {
+        PF_CHECK(hipMemcpy(a->d_H.get(), b.data(), M * sizeof(cx<double>), hipMemcpyHostToDevice));
+        if ((rc = pffftd_hip_transform_batch(static_cast<PFFFTD_Setup*>(a->inner), a->d_H.as<double>(), a->d_H.as<double>(), 1, PFFFT_FORWARD, 0, nullptr)))
+            return rc;
+    } else {
+        // float: the filter spectrum from the DOUBLE transform, rounded once (a float transform of b would add its error to every output);
+        // the permutation into the internal layout is exact
+        PFFFTD_Setup* sd = pffftd_new_setup((int)M, PFFFT_COMPLEX);
+        if (!sd) return bad("any: no double setup for the filter spectrum");
+        DevBuf tmp, tmpf;
+        rc = tmp.grow(M * sizeof(cx<double>));
+        if (!rc) rc = tmpf.grow(M * sizeof(cx<float>));
+        hipError_t e = hipSuccess;
+        if (!rc) e = hipMemcpy(tmp.get(), b.data(), M * sizeof(cx<double>), hipMemcpyHostToDevice);
+        if (!rc && e == hipSuccess) rc = pffftd_hip_transform_batch(sd, tmp.as<double>(), tmp.as<double>(), 1, PFFFT_FORWARD, 1, nullptr);
+        if (!rc && e == hipSuccess) e = hipStreamSynchronize(nullptr);
+        if (!rc && e == hipSuccess) e = hipMemcpy(b.data(), tmp.get(), M * sizeof(cx<double>), hipMemcpyDeviceToHost);
+        pffftd_destroy_setup(sd);
+        if (rc) return rc;
+        if (e != hipSuccess) return fail(e, "the filter spectrum of an any-length setup");
+        std::vector<cx<float>> bf(M);
+        for (size_t m = 0; m < M; ++m) bf[m] = mk<float>((float)b[m].x, (float)b[m].y);
+        PF_CHECK(hipMemcpy(tmpf.get(), bf.data(), M * sizeof(cx<float>), hipMemcpyHostToDevice));
+        rc = pffft_hip_zreorder_batch(static_cast<PFFFT_Setup*>(a->inner), tmpf.as<float>(), a->d_H.as<float>(), 1, PFFFT_BACKWARD, nullptr);
+        e = hipStreamSynchronize(nullptr);   // (the permutation reads tmpf: it has finished before the temporaries go)
+        if (rc) return rc;
+        if (e != hipSuccess) return fail(e, "the filter spectrum of an any-length setup");
+        return 0;
+    }
+    PF_CHECK(hipStreamSynchronize(nullptr));
+    return 0;
+}
+
+// first call: binds the setup to the current device and builds its tables (allocates and synchronises: not during a stream capture)
+template <typename T>
+static int any_ensure(AnySetup* a, hipStream_t st) {
+    int dev = -1;
+    PF_CHECK(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(a->mu);
+    if (a->ready) return a->device == dev ? 0 : bad("any: this setup holds its tables on another device (one setup serves one device)", hipErrorInvalidDevice);
+    if (stream_capturing(st))
+        return bad("any: the tables of this setup would have to be built during graph capture: run the call once before capturing",
+                   hipErrorStreamCaptureUnsupported);
+    if (a->route != ANY_DIRECT)
+        if (int rc = any_build_tables<T>(a)) return rc;
+    a->device = dev;
+    a->ready = true;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ fused launch
+template <class C>
+static int any_fused_launch(AnySetup* a, const float* in, float* out, size_t batch, int cj, hipStream_t st) {
+    constexpr int HOLD = AnyHold<C>::value;
+    auto k = fft_conv_kernel<C, 0, AnyChirpIO<C, HOLD>>;
+    Setup* s = a->inner;
+    int rc = allow_big_lds(k, C::LDS_BYTES);
+    if (rc) return rc;
+    int per_cu = 0;
+    if ((rc = cached_occupancy(reinterpret_cast<const void*>(k), C::WG_THREADS, C::LDS_BYTES, &per_cu))) return rc;
+    // (the launch rule of the convolution kernel, conv_tu.hip)
+    const size_t groups = (batch + C::T_PER_WG - 1) / C::T_PER_WG;
+    size_t grid = (size_t)num_cus() * per_cu;
+    if (groups <= 4 * grid) grid = groups;
+    if (grid > groups) grid = groups;
+    unsigned* ctr = groups <= grid ? nullptr : take_counters(s, st);
+    const AnyChirpIO<C, HOLD> io{in, out, a->d_chirp.as<cx<float>>(), (unsigned)a->N, cj};
+    const cx<float>* tw = s->d_tw.as<cx<float>>();
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(C::WG_THREADS), C::LDS_BYTES, st, io, (const float*)a->d_H.as<float>(), (unsigned)batch,
+                       1.0f / (float)a->M, tw, tw, ctr);
+    PF_CHECK(hipGetLastError());
+    return 0;
+}
+
+static int any_fused(AnySetup* a, const float* in, float* out, size_t batch, int cj, hipStream_t st) {
+    typedef ConvPick<float> P;
+    Setup* s = for_device(a->inner);
+    if (s != a->inner) return bad("any: this setup holds its tables on another device", hipErrorInvalidDevice);
+    int rc = ensure_device_any(s);
+    if (rc) return rc;
+    // (the kernel counts vectors in 32 bits: longer batches go out in slices on the same stream)
+    constexpr size_t SLICE = (size_t)3 << 30;
+    for (size_t b0 = 0; b0 < batch; b0 += SLICE) {
+        const size_t nb = std::min(batch - b0, SLICE);
+        const float* pi = in + b0 * 2 * (size_t)a->N;
+        float* po = out + b0 * 2 * (size_t)a->N;
+        switch (a->M) {
+            case 512: rc = any_fused_launch<P::C512>(a, pi, po, nb, cj, st); break;
+            case 1024: rc = any_fused_launch<P::C1024>(a, pi, po, nb, cj, st); break;
+            case 2048: rc = any_fused_launch<P::C2048>(a, pi, po, nb, cj, st); break;
+            case 4096: rc = any_fused_launch<P::C4096>(a, pi, po, nb, cj, st); break;
+            default: return bad("any: no fused kernel for this length");
+        }
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ composed
+static unsigned any_grid(size_t items) {
+    return (unsigned)std::max<size_t>(1, std::min<size_t>((items + 255) / 256, (size_t)num_cus() * 16));
+}
+
+template <typename T>
+static int any_composed(AnySetup* a, const T* in, T* out, size_t batch, int cj, hipStream_t st) {
+    const size_t N = (size_t)a->N, M = (size_t)a->M;
+    const size_t chunk = std::max<size_t>(1, std::min(batch, ANY_CAP_BYTES / (M * sizeof(cx<T>))));
+    const size_t bytes = chunk * M * sizeof(cx<T>);
+    std::lock_guard<std::mutex> lk(a->pad.mu);
+    StreamScratch::Entry& sc = a->pad.acquire(st);
+    if (sc.buf[0].bytes() < bytes && stream_capturing(st))
+        return bad("the scratch image of this stream would have to grow during graph capture: run the call once on this stream before capturing",
+                   hipErrorStreamCaptureUnsupported);
+    int rc = a->pad.grow(sc, 0, bytes);
+    if (rc) return rc;
+    cx<T>* X = sc.buf[0].as<cx<T>>();
+    const cx<T>* w = a->d_chirp.as<cx<T>>();
+    const T scaling = (T)1 / (T)M;
+    for (size_t v0 = 0; v0 < batch; v0 += chunk) {
+        const size_t cnt = std::min(batch - v0, chunk);
+        hipLaunchKernelGGL((any_pad_kernel<T>), dim3(any_grid(cnt * M)), dim3(256), 0, st, reinterpret_cast<const cx<T>*>(in) + v0 * N, X, w, cnt,
+                           N, M, cj);
+        PF_CHECK(hipGetLastError());
+        if constexpr (sizeof(T) == 8)
+            rc = pffftd_hip_convolve_batch(static_cast<PFFFTD_Setup*>(a->inner), (const double*)X, a->d_H.as<double>(), (double*)X, scaling, cnt, 0, 1, st);
+        else
+            rc = pffft_hip_convolve_batch(static_cast<PFFFT_Setup*>(a->inner), (const float*)X, a->d_H.as<float>(), (float*)X, scaling, cnt, 0, 1, st);
+        if (rc) return rc;
+        hipLaunchKernelGGL((any_crop_kernel<T>), dim3(any_grid(cnt * N)), dim3(256), 0, st, (const cx<T>*)X, reinterpret_cast<cx<T>*>(out) + v0 * N, w,
+                           cnt, N, M, cj);
+        PF_CHECK(hipGetLastError());
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ the entry
+template <typename T>
+static int any_transform_batch(void* setup, const T* in, T* out, size_t batch, int dir, hipStream_t st) {
+    AnySetup* a = any_checked(setup);
+    if (!a || a->is_double != (sizeof(T) == 8)) {
+        g_last_error = "pffft_hip: bad any-length setup handle";
+        return (int)hipErrorInvalidHandle;
+    }
+    if (dir != PFFFT_FORWARD && dir != PFFFT_BACKWARD) return bad("any: bad direction");
+    if (batch && (!in || !out)) return bad("any: NULL in / out");
+    // (the direct route is transform_batch: its 16- / 32-byte rule; the other routes access one complex value at a time)
+    const uintptr_t align = a->route == ANY_DIRECT ? 4 * sizeof(T) : 2 * sizeof(T);
+    if (((uintptr_t)in | (uintptr_t)out) & (align - 1))
+        return bad(a->route == ANY_DIRECT ? "any: in / out not 16-byte (float) / 32-byte (double) aligned" : "any: in / out not aligned to one complex value");
+    int rc = any_ensure<T>(a, st);
+    if (rc || batch == 0) return rc;
+    const AnyRoute r = any_route_now(a, ab());
+    if (r == ANY_DIRECT) return transform_batch_any(a->inner, in, out, batch, dir, 1, st);
+    const int cj = dir == PFFFT_BACKWARD;
+    if constexpr (sizeof(T) == 4)
+        if (r == ANY_FUSED) return any_fused(a, in, out, batch, cj, st);
+    return any_composed<T>(a, in, out, batch, cj, st);
+}
+
+}  // namespace pf
+
+PF_EXPORT PFFFT_HIP_AnySetup* pffft_hip_any_new_setup(int N, pffft_transform_t tr) {
+    return reinterpret_cast<PFFFT_HIP_AnySetup*>(pf::any_new_setup(N, (int)tr, 0));
+}
+PF_EXPORT PFFFTD_HIP_AnySetup* pffftd_hip_any_new_setup(int N, pffft_transform_t tr) {
+    return reinterpret_cast<PFFFTD_HIP_AnySetup*>(pf::any_new_setup(N, (int)tr, 1));
+}
+PF_EXPORT void pffft_hip_any_destroy_setup(PFFFT_HIP_AnySetup* s) { pf::any_destroy_setup(reinterpret_cast<pf::AnySetup*>(s)); }
+PF_EXPORT void pffftd_hip_any_destroy_setup(PFFFTD_HIP_AnySetup* s) { pf::any_destroy_setup(reinterpret_cast<pf::AnySetup*>(s)); }
+PF_EXPORT int pffft_hip_any_transform_batch(PFFFT_HIP_AnySetup* s, const float* in, float* out, size_t batch, pffft_direction_t d, void* stream) {
+    return pf::any_transform_batch<float>(s, in, out, batch, (int)d, (hipStream_t)stream);
+}
+PF_EXPORT int pffftd_hip_any_transform_batch(PFFFTD_HIP_AnySetup* s, const double* in, double* out, size_t batch, pffft_direction_t d,
+                                             void* stream) {
+    return pf::any_transform_batch<double>(s, in, out, batch, (int)d, (hipStream_t)stream);
+}
+PF_EXPORT int pffft_hip_any_conv_size(const void* setup) {
+    const pf::AnySetup* a = pf::any_checked(setup);
+    return a ? a->M : -1;
+}
+PF_EXPORT const char* pffft_hip_any_route(const void* setup) {
+    const pf::AnySetup* a = pf::any_checked(setup);
+    if (!a) return "";
+    switch (pf::any_route_now(a, pf::ab())) {
+        case pf::ANY_DIRECT: return "direct";
+        case pf::ANY_FUSED: return "fused";
+        default: return "composed";
+    }
+}
+PF_EXPORT int pffft_hip_any_chirp(const void* setup, void* host_out) {
+    const pf::AnySetup* a = pf::any_checked(setup);
+    if (!a || !host_out) { pf::g_last_error = "pffft_hip: bad any-length setup handle / NULL output"; return (int)hipErrorInvalidValue; }
+    const unsigned long long N = (unsigned long long)a->N;
+    if (a->is_double) {
+        pf::cx<double>* o = static_cast<pf::cx<double>*>(host_out);
+        for (unsigned long long n = 0; n < N; ++n) o[n] = pf::chirp_value<double>(n, N);
+    } else {
+        pf::cx<float>* o = static_cast<pf::cx<float>*>(host_out);
+        for (unsigned long long n = 0; n < N; ++n) o[n] = pf::chirp_value<float>(n, N);
+    }
+    return 0;
+}

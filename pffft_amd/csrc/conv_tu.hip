@@ -7,11 +7,9 @@
 
 namespace pf {
 
-template <typename T, class C>
-static int conv_launch(Setup* s, const T* in, const T* H, T* out, size_t batch, T scaling, int accumulate, hipStream_t st) {
-    const bool real = s->transform == PFFFT_REAL;
-    void (*k)(const T*, const T*, T*, unsigned, T, int, const cx<T>*, const cx<T>*, unsigned*) =
-        real ? fft_conv_kernel<C, 1> : fft_conv_kernel<C, 0>;
+template <typename T, class C, int REAL>
+static int conv_launch_io(Setup* s, const T* in, const T* H, T* out, size_t batch, T scaling, int accumulate, hipStream_t st) {
+    auto k = fft_conv_kernel<C, REAL>;
     int rc = allow_big_lds(k, C::LDS_BYTES);
     if (rc) return rc;
     int per_cu = 0;
@@ -21,10 +19,17 @@ static int conv_launch(Setup* s, const T* in, const T* H, T* out, size_t batch, 
     if (groups <= 4 * grid) grid = groups;        // (short launches: one group per workgroup in dispatch order - the rule of launch_tiled)
     if (grid > groups) grid = groups;
     unsigned* ctr = groups <= grid ? nullptr : take_counters(s, st);
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(C::WG_THREADS), C::LDS_BYTES, st, in, H, out, (unsigned)batch, scaling, accumulate,
-                       s->d_tw.as<cx<T>>(), s->d_twr.as<cx<T>>(), ctr);
+    const ConvDenseIO<C, REAL> io{in, out, accumulate};
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(C::WG_THREADS), C::LDS_BYTES, st, io, H, (unsigned)batch, scaling,
+                       (const cx<T>*)s->d_tw.as<cx<T>>(), (const cx<T>*)s->d_twr.as<cx<T>>(), ctr);
     PF_CHECK(hipGetLastError());
     return 0;
+}
+
+template <typename T, class C>
+static int conv_launch(Setup* s, const T* in, const T* H, T* out, size_t batch, T scaling, int accumulate, hipStream_t st) {
+    if (s->transform == PFFFT_REAL) return conv_launch_io<T, C, 1>(s, in, H, out, batch, scaling, accumulate, st);
+    return conv_launch_io<T, C, 0>(s, in, H, out, batch, scaling, accumulate, st);
 }
 
 template <typename T>

@@ -17,10 +17,78 @@
 
 namespace pf {
 
+// The two ends of the kernel are a policy (IO): where a thread's first-stage operands come from and where the last stage's results go.
+//   Regs                       what the policy keeps in registers across the persistent loop (it depends on the thread only)
+//   init(regs, t)              fills them, once
+//   load(raw, vec, t)          requests vector `vec` into the raw chunks (called one vector ahead: the prefetch)
+//   unpack(raw, v, regs, t)    raw chunks -> first-stage operand order
+//   store(v, vec, regs, t)     the last stage's natural order -> vector `vec`
+// The policy object is a kernel argument.  ConvDenseIO is pffft_hip_convolve_batch: dense vectors of n points, 16-byte accesses.
+// fft_any.h has the chirping, zero-padding / cropping one of the any-length transforms.
 template <class C, int REAL>
+struct ConvDenseIO {
+    typedef typename C::real_t T;
+    typedef cx<T> CX;
+    typedef Tiled<C, FWD, REAL> KF;
+    typedef typename KF::S0 S0;
+    typedef ChunkOps<T> CO;
+    static constexpr int n = C::n, E = C::E, TPT = C::TPT, VEC = C::VEC, NCH = C::NCH;
+    static constexpr int R0 = C::rad(0), RL = C::rad(C::NS - 1);
+    struct Regs {};
+    const T* in;
+    T* out;
+    int accumulate;
+    __device__ __forceinline__ void init(Regs&, int) const {}
+    __device__ __forceinline__ void load(chunk16 (&raw)[NCH], size_t vec, int t) const { KF::load_raw(raw, in + vec * 2 * (size_t)n, t, true); }
+    // first-stage operand order straight from the raw chunks
+    __device__ __forceinline__ void unpack(const chunk16 (&raw)[NCH], CX (&v)[E], const Regs&, int) const {
+        if constexpr (VEC == 2) {
+#pragma unroll
+            for (int ii = 0; ii < S0::B / 2; ++ii)
+#pragma unroll
+                for (int q = 0; q < R0; ++q) {
+                    const chunk16 c = raw[ii * R0 + q];
+                    v[(2 * ii) * R0 + q] = mk<T>(c.x, c.y);
+                    v[(2 * ii + 1) * R0 + q] = mk<T>(c.z, c.w);
+                }
+        } else {
+#pragma unroll
+            for (int i = 0; i < NCH; ++i) v[i] = mk<T>(CO::get(raw[i], 0), CO::get(raw[i], 1));
+        }
+    }
+    // the last stage's natural order, 16-byte units in lane order (accumulate: out += result)
+    __device__ __forceinline__ void store(const CX (&v)[E], size_t vec, const Regs&, int t) const {
+        chunk16* d16 = reinterpret_cast<chunk16*>(out + vec * 2 * (size_t)n);
+        if constexpr (VEC == 2) {
+#pragma unroll
+            for (int ii = 0; ii < S0::B / 2; ++ii)
+#pragma unroll
+                for (int d = 0; d < RL; ++d) {
+                    const CX a = v[(2 * ii) * RL + d], b = v[(2 * ii + 1) * RL + d];
+                    chunk16 x; x.x = a.x; x.y = a.y; x.z = b.x; x.w = b.y;
+                    chunk16* p = d16 + t + TPT * ii + d * (n / (2 * RL));
+                    if (accumulate) { const chunk16 o = *p; x.x += o.x; x.y += o.y; x.z += o.z; x.w += o.w; }
+                    __builtin_nontemporal_store(x, p);
+                }
+        } else {
+#pragma unroll
+            for (int u = 0; u < E / RL; ++u)
+#pragma unroll
+                for (int d = 0; d < RL; ++d) {
+                    chunk16* p = d16 + t + TPT * u + d * (n / RL);
+                    T re = v[u * RL + d].x, im = v[u * RL + d].y;
+                    if (accumulate) { const chunk16 o = *p; re += CO::get(o, 0); im += CO::get(o, 1); }
+                    chunk16 x;
+                    CO::set(x, 0, re); CO::set(x, 1, im);
+                    __builtin_nontemporal_store(x, p);
+                }
+        }
+    }
+};
+
+template <class C, int REAL, class IO = ConvDenseIO<C, REAL>>
 __global__ void __launch_bounds__(C::WG_THREADS, C::WG_THREADS >= 1024 ? 4 : C::OCC)
-fft_conv_kernel(const typename C::real_t* in, const typename C::real_t* __restrict__ H, typename C::real_t* out, unsigned batch,
-                typename C::real_t scaling, int accumulate,
+fft_conv_kernel(const IO io, const typename C::real_t* __restrict__ H, unsigned batch, typename C::real_t scaling,
                 const cx<typename C::real_t>* __restrict__ twg, const cx<typename C::real_t>* __restrict__ twrg, unsigned* ctr) {
     typedef typename C::real_t T;
     typedef cx<T> CX;
@@ -81,9 +149,11 @@ fft_conv_kernel(const typename C::real_t* in, const typename C::real_t* __restri
     __syncthreads();
     const size_t last = (size_t)batch - 1;
     chunk16 raw[NCH];
+    typename IO::Regs regs;
+    io.init(regs, t);
     {
         size_t t0 = (size_t)g * C::T_PER_WG + slot;
-        KF::load_raw(raw, in + (t0 < last ? t0 : last) * 2 * (size_t)n, t, true);
+        io.load(raw, t0 < last ? t0 : last, t);
     }
     for (unsigned it = 0; (size_t)g * C::T_PER_WG < batch; ++it) {
         if (dyn && threadIdx.x == 0) {
@@ -92,22 +162,10 @@ fft_conv_kernel(const typename C::real_t* in, const typename C::real_t* __restri
         }
         const size_t tr = (size_t)g * C::T_PER_WG + slot;
         const bool active = tr < batch;  // inactive slots recompute the last vector and never store
-        T* dst = out + (active ? tr : last) * 2 * (size_t)n;
+        const size_t dv = active ? tr : last;
         CX v[E];
-        // ---- input: first-stage operand order straight from the raw chunks
-        if constexpr (VEC == 2) {
-#pragma unroll
-            for (int ii = 0; ii < S0::B / 2; ++ii)
-#pragma unroll
-                for (int q = 0; q < R0; ++q) {
-                    const chunk16 c = raw[ii * R0 + q];
-                    v[(2 * ii) * R0 + q] = mk<T>(c.x, c.y);
-                    v[(2 * ii + 1) * R0 + q] = mk<T>(c.z, c.w);
-                }
-        } else {
-#pragma unroll
-            for (int i = 0; i < NCH; ++i) v[i] = mk<T>(CO::get(raw[i], 0), CO::get(raw[i], 1));
-        }
+        // ---- input: first-stage operand order from the raw chunks
+        io.unpack(raw, v, regs, t);
         // ---- forward transform
         KF::template butterflies<0>(v, t, wf, twt);
         if constexpr (NS > 1) KF::template xwrite<0>(v, t, img);
@@ -115,7 +173,7 @@ fft_conv_kernel(const typename C::real_t* in, const typename C::real_t* __restri
         const unsigned gn = dyn ? s_next[(it + 1) & 1] : g + gridDim.x;
         if constexpr (C::PREFETCH) {  // the loads of the next vector fly while this one is finished
             const size_t tn = (size_t)gn * C::T_PER_WG + slot;
-            KF::load_raw(raw, in + (tn < last ? tn : last) * 2 * (size_t)n, t, true);
+            io.load(raw, tn < last ? tn : last, t);
         }
         if constexpr (NS > 1) { KF::template xread<0>(v, t, img); KF::xsync(); KF::template butterflies<1>(v, t, wf, twt); }
         if constexpr (NS > 2) { KF::template xwrite<1>(v, t, img); KF::xsync(); KF::template xread<1>(v, t, img); KF::xsync(); KF::template butterflies<2>(v, t, wf, twt); }
@@ -137,38 +195,12 @@ fft_conv_kernel(const typename C::real_t* in, const typename C::real_t* __restri
         if constexpr (NS > 2) { KB::template xwrite<1>(v, t, img); KB::xsync(); KB::template xread<1>(v, t, img); KB::xsync(); KB::template butterflies<2>(v, t, wb, twt); }
         if constexpr (NS > 3) { KB::template xwrite<2>(v, t, img); KB::xsync(); KB::template xread<2>(v, t, img); KB::xsync(); KB::template butterflies<3>(v, t, wb, twt); }
         if constexpr (NS > 4) { KB::template xwrite<3>(v, t, img); KB::xsync(); KB::template xread<3>(v, t, img); KB::xsync(); KB::template butterflies<4>(v, t, wb, twt); }
-        // ---- output: the last stage's natural order, 16-byte units in lane order (accumulate: out += result)
-        if (active) {
-            chunk16* d16 = reinterpret_cast<chunk16*>(dst);
-            if constexpr (VEC == 2) {
-#pragma unroll
-                for (int ii = 0; ii < S0::B / 2; ++ii)
-#pragma unroll
-                    for (int d = 0; d < RL; ++d) {
-                        const CX a = v[(2 * ii) * RL + d], b = v[(2 * ii + 1) * RL + d];
-                        chunk16 x; x.x = a.x; x.y = a.y; x.z = b.x; x.w = b.y;
-                        chunk16* p = d16 + t + TPT * ii + d * (n / (2 * RL));
-                        if (accumulate) { const chunk16 o = *p; x.x += o.x; x.y += o.y; x.z += o.z; x.w += o.w; }
-                        __builtin_nontemporal_store(x, p);
-                    }
-            } else {
-#pragma unroll
-                for (int u = 0; u < E / RL; ++u)
-#pragma unroll
-                    for (int d = 0; d < RL; ++d) {
-                        chunk16* p = d16 + t + TPT * u + d * (n / RL);
-                        T re = v[u * RL + d].x, im = v[u * RL + d].y;
-                        if (accumulate) { const chunk16 o = *p; re += CO::get(o, 0); im += CO::get(o, 1); }
-                        chunk16 x;
-                        CO::set(x, 0, re); CO::set(x, 1, im);
-                        __builtin_nontemporal_store(x, p);
-                    }
-            }
-        }
+        // ---- output: the last stage's natural order
+        if (active) io.store(v, dv, regs, t);
         KB::xsync();
         if constexpr (!C::PREFETCH) {
             const size_t tn = (size_t)gn * C::T_PER_WG + slot;
-            KF::load_raw(raw, in + (tn < last ? tn : last) * 2 * (size_t)n, t, true);
+            io.load(raw, tn < last ? tn : last, t);
         }
         g = gn;
     }
