@@ -361,6 +361,37 @@ int pffft_hip_any_conv_size(const void *setup);
 const char *pffft_hip_any_route(const void *setup);
 int pffft_hip_any_chirp(const void *setup, void *host_out);
 
+/* REAL transforms of any length 1 <= N <= 2^25 with half-spectrum I/O (numpy's rfft / irfft . N).  PFFFT_REAL stays reserved in
+ * pffft[d]_hip_any_new_setup; a real setup comes from its own constructor (NULL for N < 1 and N > 2^25; touches no device) and is an
+ * any-length setup with a real flag: pffft[d]_hip_any_transform_batch, _any_destroy_setup, pffft_hip_any_route, _any_conv_size and
+ * _any_chirp (the same N chirp values as for a complex setup of N) accept it.  With H = floor(N / 2) + 1:
+ *   FORWARD   in: batch dense rows of N real scalars; out: batch dense rows of H interleaved complex bins (2H scalars),
+ *             out[v][k] = sum_n in[v][n] exp(-2 pi j n k / N), k < H.  The imaginary part of bin 0, and of bin N/2 for even N, is what the
+ *             arithmetic yields (a rounding-sized value) on the fused and composed routes and exactly +0 on the direct route.
+ *   BACKWARD  in: rows of H complex bins; out: rows of N reals, UNSCALED (backward(forward(x)) = N x).  The imaginary parts of bin 0 and of
+ *             bin N/2 (even N) are NOT part of the input: whatever they hold, NaN included, the output has the same bits.
+ * in and out must not overlap (their rows differ in size).  Routes, planned once at setup:
+ *   "direct"    N is a legal REAL size (pffft_is_valid_size(N, PFFFT_REAL)): transform_batch(ordered = 1) on an inner real setup through a
+ *               per-stream scratch of canonical spectra, and a kernel that moves the values between that layout and the H bins, bit for
+ *               bit.  in / out 16-byte (float) / 32-byte (double) aligned.  pffft_hip_any_conv_size = 0.
+ *   "fused"     float and M = the next power of two >= N + floor(N / 2) is 512, 1024, 2048 or 4096 (N = 172 ... 2731): ONE kernel, the
+ *               fused convolution kernel with a real loader / store policy: 4 N + 8 H bytes per row.  Only the bins k < H are wanted, so
+ *               a circular length M >= N + floor(N / 2) suffices where the complex transform needs 2N - 1.
+ *   "composed"  everything else (double, other N; selector 132 everywhere): pad kernel, pffft[d]_hip_convolve_batch at length
+ *               M = pffft_nearest_transform_size(N + floor(N / 2), PFFFT_COMPLEX, higher), crop kernel (a setup that can run fused uses its
+ *               power of two on both routes).
+ * On the fused and composed routes the real-side pointer may be aligned to one scalar and the complex-side pointer to one complex value.
+ * Each direction has its own filter spectrum (the two supports are mirror images); both are built with the chirp at the first call.
+ * Validation before any device is touched, the first-call table build and its stream-capture rule, one setup per device, the 256 MiB
+ * scratch cap with chunking: as for the complex setup above. */
+PFFFT_HIP_AnySetup *pffft_hip_any_new_real_setup(int N);
+PFFFTD_HIP_AnySetup *pffftd_hip_any_new_real_setup(int N);
+/* Host arithmetic only, handles of both precisions.  pffft_hip_any_is_real: 1 for a real setup, 0 for a complex one.
+ * pffft_hip_any_bins: complex values per spectrum row: floor(N / 2) + 1 for a real setup, N for a complex one.  Both -1 for an invalid
+ * handle. */
+int pffft_hip_any_is_real(const void *setup);
+int pffft_hip_any_bins(const void *setup);
+
 /* Overlap-save FIR on device-resident signal/output (same block schedule as pffastconv_apply,
  * src/pffastconv.c:204-261): returns the number of output samples written, or -1 on error. */
 int pffastconv_hip_apply_device(PFFASTCONV_Setup *, const float *d_input, int inputLen, float *d_output,

@@ -90,6 +90,7 @@ def lib():
         g("hip_pfb_synthesis_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
                                                  C.c_void_p, C.c_size_t, ct, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
         g("hip_any_new_setup").restype = C.c_void_p; g("hip_any_new_setup").argtypes = [C.c_int, C.c_int]
+        g("hip_any_new_real_setup").restype = C.c_void_p; g("hip_any_new_real_setup").argtypes = [C.c_int]
         g("hip_any_destroy_setup").restype = None; g("hip_any_destroy_setup").argtypes = [C.c_void_p]
         g("hip_any_transform_batch").restype = C.c_int
         g("hip_any_transform_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
@@ -118,6 +119,8 @@ def lib():
     L.pffft_hip_any_conv_size.restype = C.c_int; L.pffft_hip_any_conv_size.argtypes = [C.c_void_p]
     L.pffft_hip_any_route.restype = C.c_char_p; L.pffft_hip_any_route.argtypes = [C.c_void_p]
     L.pffft_hip_any_chirp.restype = C.c_int; L.pffft_hip_any_chirp.argtypes = [C.c_void_p, C.c_void_p]
+    L.pffft_hip_any_is_real.restype = C.c_int; L.pffft_hip_any_is_real.argtypes = [C.c_void_p]
+    L.pffft_hip_any_bins.restype = C.c_int; L.pffft_hip_any_bins.argtypes = [C.c_void_p]
     L.pffft_hip_kernel_name.restype = C.c_char_p; L.pffft_hip_kernel_name.argtypes = [C.c_void_p]
     L.pffft_hip_describe.restype = C.c_int; L.pffft_hip_describe.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.pffft_hip_setup_devices.restype = C.c_int; L.pffft_hip_setup_devices.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_int]
@@ -226,9 +229,9 @@ def pfb_route(setup: "Setup", hop, taps, signal_stride=0, out_stride=0, output="
                                      FRAMES_OUTPUTS[output]).decode()
 
 
-def any_route(setup: "AnySetup") -> str:
-    """pffft_hip_any_route: "direct" / "fused" / "composed" for an any-length setup under the calling thread's selector.  Host
-    arithmetic only."""
+def any_route(setup) -> str:
+    """pffft_hip_any_route: "direct" / "fused" / "composed" for an any-length setup (AnySetup or AnyRealSetup) under the calling thread's
+    selector.  Host arithmetic only."""
     return lib().pffft_hip_any_route(setup.handle).decode()
 
 
@@ -567,6 +570,66 @@ class AnySetup:
         if out is None:
             out = torch.empty_like(x)
         assert out.is_cuda and out.dtype == want and out.is_contiguous() and out.numel() == x.numel()
+        fn = getattr(self._L, f"{self._pfx}_hip_any_transform_batch")
+        _check(fn(self.handle, x.data_ptr(), out.data_ptr(), batch, direction, C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+               "hip_any_transform_batch")
+        return out
+
+
+class AnyRealSetup:
+    """pffft[d]_hip_any_new_real_setup: real transforms of any length 1 <= N <= 2^25 with half-spectrum I/O (include/pffft_hip.h).  FORWARD
+    takes rows of N reals to rows of bins = N // 2 + 1 interleaved complex values (numpy's rfft), BACKWARD the reverse, unscaled (irfft . N).
+    Raises ValueError where the constructor returns NULL."""
+
+    def __init__(self, N: int, dtype=np.float32):
+        self.N, self.dtype = int(N), np.dtype(dtype)
+        self._pfx = _pfx(dtype)
+        self._L = lib()
+        self.handle = getattr(self._L, f"{self._pfx}_hip_any_new_real_setup")(self.N)
+        if not self.handle:
+            raise ValueError(f"pffft_hip_any_new_real_setup({N}) returned NULL")
+        self.bins = int(self._L.pffft_hip_any_bins(self.handle))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            getattr(self._L, f"{self._pfx}_hip_any_destroy_setup")(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def conv_size(self) -> int:
+        """The convolution length M (0 on the direct route)."""
+        return int(self._L.pffft_hip_any_conv_size(self.handle))
+
+    @property
+    def route(self) -> str:
+        return any_route(self)
+
+    def chirp(self) -> np.ndarray:
+        """pffft_hip_any_chirp: the N chirp values, as for a complex setup of the same N."""
+        out = np.empty(2 * self.N, dtype=self.dtype)
+        rc = self._L.pffft_hip_any_chirp(self.handle, out.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"pffft_hip_any_chirp failed ({rc})")
+        return out.view(np.complex128 if self.dtype == np.float64 else np.complex64)
+
+    def transform_batch(self, x, out=None, direction=FORWARD):
+        """x: contiguous CUDA tensor of the setup's dtype holding `batch` rows of N scalars (FORWARD) or 2 * bins scalars (BACKWARD); the
+        result has `batch` rows of 2 * bins (FORWARD) or N (BACKWARD) scalars.  out must not overlap x."""
+        import torch
+        want = torch.float64 if self.dtype == np.float64 else torch.float32
+        rin, rout = (self.N, 2 * self.bins) if direction == FORWARD else (2 * self.bins, self.N)
+        assert x.is_cuda and x.dtype == want and x.is_contiguous() and x.numel() % rin == 0, \
+            "need a contiguous CUDA tensor of the setup dtype holding whole rows"
+        batch = x.numel() // rin
+        if out is None:
+            out = torch.empty((batch, rout), dtype=want, device=x.device)
+        assert out.is_cuda and out.dtype == want and out.is_contiguous() and out.numel() == batch * rout
         fn = getattr(self._L, f"{self._pfx}_hip_any_transform_batch")
         _check(fn(self.handle, x.data_ptr(), out.data_ptr(), batch, direction, C.c_void_p(torch.cuda.current_stream().cuda_stream)),
                "hip_any_transform_batch")

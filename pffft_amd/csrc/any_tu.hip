@@ -1,5 +1,5 @@
-// libpffft_hip.so, translation unit of the any-length complex transforms (include/pffft_hip.h: pffft[d]_hip_any_*): Bluestein's algorithm
-// on the library's own convolution.  Plan (route, convolution length) at setup, tables on first use, the fused kernel's launch and the
+// libpffft_hip.so, translation unit of the any-length transforms, complex and real (include/pffft_hip.h: pffft[d]_hip_any_*): Bluestein's
+// algorithm on the library's own convolution.  Plan (route, convolution length) at setup, tables on first use, the fused kernel's launch and the
 // composed route through a per-stream scratch image.  Kernels: fft_any.h.
 #include <hip/hip_runtime.h>
 
@@ -28,6 +28,7 @@ enum AnyRoute { ANY_DIRECT = 0, ANY_FUSED = 1, ANY_COMPOSED = 2 };
 struct AnySetup {
     uint32_t magic = ANY_MAGIC;
     int N = 0, is_double = 0;
+    int is_real = 0;               // pffft[d]_hip_any_new_real_setup: rows of N reals <-> H = N/2 + 1 complex bins
     AnyRoute route = ANY_DIRECT;   // the default route, fixed at setup
     int M = 0;                     // convolution length; 0 on the direct route
     Setup* inner = nullptr;        // length N (direct) or M: a PFFFT_Setup / PFFFTD_Setup, owned
@@ -35,8 +36,11 @@ struct AnySetup {
     bool ready = false;
     int device = -1;
     DevBuf d_chirp;                // w[n], n < N (where the fused kernel is legal: M entries, zero from N on)
-    DevBuf d_H;                    // spectrum of the filter b in the inner setup's internal layout
-    StreamScratch pad;             // batch x M image of the composed route: one per stream, pad.mu held while a call enqueues
+    DevBuf d_H;                    // spectrum of the filter b in the inner setup's internal layout (real setups: of b_f, the forward one)
+    DevBuf d_Hr;                   // real setups: spectrum of b_r, the backward filter (the index reversal of b_f)
+    StreamScratch pad;             // batch x M image of the composed route (real direct route: batch x N canonical spectra): one per
+                                   // stream, pad.mu held while a call enqueues
+    int bins() const { return is_real ? N / 2 + 1 : N; }
 };
 
 static int bad(const char* what, hipError_t e = hipErrorInvalidValue) {
@@ -79,6 +83,29 @@ static AnySetup* any_new_setup(int N, int transform, int is_double) {
     return a.release();
 }
 
+// Real setups: the bins k < H = N/2 + 1 only, so k - n runs over [-(N-1), N/2] and M >= N + N/2 suffices.  The fused cells are then
+// N = 172 ... 2731 (M2 = 512 ... 4096); like the complex setup, one that can run fused uses M2 on both routes.
+static AnySetup* any_new_real_setup(int N, int is_double) {
+    if (N < 1 || N > ANY_MAX_N) return nullptr;
+    std::unique_ptr<AnySetup> a(new AnySetup);
+    a->N = N; a->is_double = is_double; a->is_real = 1;
+    int len = N, tr = PFFFT_REAL;
+    if (pffft_is_valid_size(N, PFFFT_REAL)) {
+        a->route = ANY_DIRECT;
+    } else {
+        const long long need = (long long)N + N / 2;
+        long long p2 = 16;
+        while (p2 < need) p2 *= 2;
+        const bool fused = !is_double && any_fused_len((int)p2);
+        a->M = len = fused ? (int)p2 : pffft_nearest_transform_size((int)need, PFFFT_COMPLEX, 1);
+        a->route = fused ? ANY_FUSED : ANY_COMPOSED;
+        tr = PFFFT_COMPLEX;
+    }
+    a->inner = is_double ? static_cast<Setup*>(pffftd_new_setup(len, (pffft_transform_t)tr)) : static_cast<Setup*>(pffft_new_setup(len, (pffft_transform_t)tr));
+    if (!a->inner) return nullptr;
+    return a.release();
+}
+
 static void any_destroy_setup(AnySetup* a) {
     if (!a || a->magic != ANY_MAGIC) return;
     a->magic = 0;
@@ -106,26 +133,15 @@ static cx<T> chirp_value(unsigned long long n, unsigned long long N) {
     return w;
 }
 
+// the spectrum of one filter b (M values, double whatever the setup's type) in the inner setup's internal layout, into `dst`
 template <typename T>
-static int any_build_tables(AnySetup* a) {
-    const size_t N = (size_t)a->N, M = (size_t)a->M;
-    std::vector<cx<T>> w(a->route == ANY_FUSED ? M : N);
-    for (size_t n = 0; n < N; ++n) w[n] = chirp_value<T>(n, N);
-    for (size_t n = N; n < w.size(); ++n) w[n] = mk<T>(0, 0);
-    int rc = upload_table(a->d_chirp, w);
+static int any_filter_spectrum(AnySetup* a, std::vector<cx<double>>& b, DevBuf& dst) {
+    const size_t M = (size_t)a->M;
+    int rc = dst.grow(M * sizeof(cx<T>));
     if (rc) return rc;
-    // b[m] = conj(w[m]), m < N; b[M - m] = b[m]; zero elsewhere - in double whatever the setup's type
-    std::vector<cx<double>> b(M);
-    for (size_t m = 0; m < M; ++m) b[m] = mk<double>(0, 0);
-    for (size_t m = 0; m < N; ++m) {
-        const cx<double> c = chirp_value<double>(m, N);
-        b[m] = mk<double>(c.x, -c.y);
-        if (m) b[M - m] = b[m];
-    }
-    if ((rc = a->d_H.grow(M * sizeof(cx<T>)))) return rc;
     if constexpr (sizeof(T) == 8) {
-        PF_CHECK(hipMemcpy(a->d_H.get(), b.data(), M * sizeof(cx<double>), hipMemcpyHostToDevice));
-        if ((rc = pffftd_hip_transform_batch(static_cast<PFFFTD_Setup*>(a->inner), a->d_H.as<double>(), a->d_H.as<double>(), 1, PFFFT_FORWARD, 0, nullptr)))
+        PF_CHECK(hipMemcpy(dst.get(), b.data(), M * sizeof(cx<double>), hipMemcpyHostToDevice));
+        if ((rc = pffftd_hip_transform_batch(static_cast<PFFFTD_Setup*>(a->inner), dst.as<double>(), dst.as<double>(), 1, PFFFT_FORWARD, 0, nullptr)))
             return rc;
     } else {
         // float: the filter spectrum from the DOUBLE transform, rounded once (a float transform of b would add its error to every output);
@@ -146,7 +162,7 @@ static int any_build_tables(AnySetup* a) {
         std::vector<cx<float>> bf(M);
         for (size_t m = 0; m < M; ++m) bf[m] = mk<float>((float)b[m].x, (float)b[m].y);
         PF_CHECK(hipMemcpy(tmpf.get(), bf.data(), M * sizeof(cx<float>), hipMemcpyHostToDevice));
-        rc = pffft_hip_zreorder_batch(static_cast<PFFFT_Setup*>(a->inner), tmpf.as<float>(), a->d_H.as<float>(), 1, PFFFT_BACKWARD, nullptr);
+        rc = pffft_hip_zreorder_batch(static_cast<PFFFT_Setup*>(a->inner), tmpf.as<float>(), dst.as<float>(), 1, PFFFT_BACKWARD, nullptr);
         e = hipStreamSynchronize(nullptr);   // (the permutation reads tmpf: it has finished before the temporaries go)
         if (rc) return rc;
         if (e != hipSuccess) return fail(e, "the filter spectrum of an any-length setup");
@@ -154,6 +170,39 @@ static int any_build_tables(AnySetup* a) {
     }
     PF_CHECK(hipStreamSynchronize(nullptr));
     return 0;
+}
+
+// b[m] = conj(w[|m|]) for -(neg - 1) <= m <= pos - 1 (negative m at M + m), zero elsewhere
+static std::vector<cx<double>> any_filter(size_t N, size_t M, size_t pos, size_t neg) {
+    std::vector<cx<double>> b(M);
+    for (size_t m = 0; m < M; ++m) b[m] = mk<double>(0, 0);
+    for (size_t m = 0; m < std::max(pos, neg); ++m) {
+        const cx<double> c = chirp_value<double>(m, N);
+        if (m < pos) b[m] = mk<double>(c.x, -c.y);
+        if (m && m < neg) b[M - m] = mk<double>(c.x, -c.y);
+    }
+    return b;
+}
+
+template <typename T>
+static int any_build_tables(AnySetup* a) {
+    const size_t N = (size_t)a->N, M = (size_t)a->M;
+    std::vector<cx<T>> w(a->route == ANY_FUSED ? M : N);
+    for (size_t n = 0; n < N; ++n) w[n] = chirp_value<T>(n, N);
+    for (size_t n = N; n < w.size(); ++n) w[n] = mk<T>(0, 0);
+    int rc = upload_table(a->d_chirp, w);
+    if (rc) return rc;
+    if (!a->is_real) {
+        // b[m] = conj(w[m]), m < N; b[M - m] = b[m]; zero elsewhere - in double whatever the setup's type
+        std::vector<cx<double>> b = any_filter(N, M, N, N);
+        return any_filter_spectrum<T>(a, b, a->d_H);
+    }
+    // real: b_f on [-(N-1), H-1], b_r on [-(H-1), N-1]
+    const size_t H = (size_t)a->bins();
+    std::vector<cx<double>> b = any_filter(N, M, H, N);
+    if ((rc = any_filter_spectrum<T>(a, b, a->d_H))) return rc;
+    b = any_filter(N, M, N, H);
+    return any_filter_spectrum<T>(a, b, a->d_Hr);
 }
 
 // first call: binds the setup to the current device and builds its tables (allocates and synchronises: not during a stream capture)
@@ -258,6 +307,142 @@ static int any_composed(AnySetup* a, const T* in, T* out, size_t batch, int cj, 
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------ real setups
+template <class C, int DIRN>
+static int any_real_fused_launch(AnySetup* a, const float* in, float* out, size_t batch, hipStream_t st) {
+    constexpr int HOLD = AnyHold<C>::value;
+    typedef AnyRealIO<C, HOLD, DIRN> IO;
+    auto k = fft_conv_kernel<C, 0, IO>;
+    Setup* s = a->inner;
+    int rc = allow_big_lds(k, C::LDS_BYTES);
+    if (rc) return rc;
+    int per_cu = 0;
+    if ((rc = cached_occupancy(reinterpret_cast<const void*>(k), C::WG_THREADS, C::LDS_BYTES, &per_cu))) return rc;
+    // (the launch rule of the convolution kernel, conv_tu.hip)
+    const size_t groups = (batch + C::T_PER_WG - 1) / C::T_PER_WG;
+    size_t grid = (size_t)num_cus() * per_cu;
+    if (groups <= 4 * grid) grid = groups;
+    if (grid > groups) grid = groups;
+    unsigned* ctr = groups <= grid ? nullptr : take_counters(s, st);
+    const IO io{in, out, a->d_chirp.as<cx<float>>(), (unsigned)a->N, (unsigned)a->bins()};
+    const cx<float>* tw = s->d_tw.as<cx<float>>();
+    const DevBuf& Hs = DIRN == FWD ? a->d_H : a->d_Hr;
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(C::WG_THREADS), C::LDS_BYTES, st, io, (const float*)Hs.as<float>(), (unsigned)batch,
+                       1.0f / (float)a->M, tw, tw, ctr);
+    PF_CHECK(hipGetLastError());
+    return 0;
+}
+
+template <int DIRN>
+static int any_real_fused(AnySetup* a, const float* in, float* out, size_t batch, hipStream_t st) {
+    typedef ConvPick<float> P;
+    Setup* s = for_device(a->inner);
+    if (s != a->inner) return bad("any: this setup holds its tables on another device", hipErrorInvalidDevice);
+    int rc = ensure_device_any(s);
+    if (rc) return rc;
+    const size_t rin = DIRN == FWD ? (size_t)a->N : 2 * (size_t)a->bins(), rout = DIRN == FWD ? 2 * (size_t)a->bins() : (size_t)a->N;
+    // (the kernel counts vectors in 32 bits: longer batches go out in slices on the same stream)
+    constexpr size_t SLICE = (size_t)3 << 30;
+    for (size_t b0 = 0; b0 < batch; b0 += SLICE) {
+        const size_t nb = std::min(batch - b0, SLICE);
+        const float* pi = in + b0 * rin;
+        float* po = out + b0 * rout;
+        switch (a->M) {
+            case 512: rc = any_real_fused_launch<P::C512, DIRN>(a, pi, po, nb, st); break;
+            case 1024: rc = any_real_fused_launch<P::C1024, DIRN>(a, pi, po, nb, st); break;
+            case 2048: rc = any_real_fused_launch<P::C2048, DIRN>(a, pi, po, nb, st); break;
+            case 4096: rc = any_real_fused_launch<P::C4096, DIRN>(a, pi, po, nb, st); break;
+            default: return bad("any: no fused kernel for this length");
+        }
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// the scratch image of one call on `st` (under a->pad.mu): at least `bytes`, never grown during a capture
+static int any_scratch(AnySetup* a, hipStream_t st, size_t bytes, void** p) {
+    StreamScratch::Entry& sc = a->pad.acquire(st);
+    if (sc.buf[0].bytes() < bytes && stream_capturing(st))
+        return bad("the scratch image of this stream would have to grow during graph capture: run the call once on this stream before capturing",
+                   hipErrorStreamCaptureUnsupported);
+    int rc = a->pad.grow(sc, 0, bytes);
+    *p = sc.buf[0].get();
+    return rc;
+}
+
+template <typename T>
+static int any_real_composed(AnySetup* a, const T* in, T* out, size_t batch, int back, hipStream_t st) {
+    const size_t N = (size_t)a->N, M = (size_t)a->M, H = (size_t)a->bins();
+    const size_t rin = back ? 2 * H : N, rout = back ? N : 2 * H;
+    const size_t chunk = std::max<size_t>(1, std::min(batch, ANY_CAP_BYTES / (M * sizeof(cx<T>))));
+    std::lock_guard<std::mutex> lk(a->pad.mu);
+    void* p = nullptr;
+    int rc = any_scratch(a, st, chunk * M * sizeof(cx<T>), &p);
+    if (rc) return rc;
+    cx<T>* X = static_cast<cx<T>*>(p);
+    const cx<T>* w = a->d_chirp.as<cx<T>>();
+    const T* Hs = (back ? a->d_Hr : a->d_H).template as<T>();
+    const T scaling = (T)1 / (T)M;
+    for (size_t v0 = 0; v0 < batch; v0 += chunk) {
+        const size_t cnt = std::min(batch - v0, chunk);
+        hipLaunchKernelGGL((any_real_pad_kernel<T>), dim3(any_grid(cnt * M)), dim3(256), 0, st, in + v0 * rin, X, w, cnt, N, H, M, back);
+        PF_CHECK(hipGetLastError());
+        if constexpr (sizeof(T) == 8)
+            rc = pffftd_hip_convolve_batch(static_cast<PFFFTD_Setup*>(a->inner), (const double*)X, Hs, (double*)X, scaling, cnt, 0, 1, st);
+        else
+            rc = pffft_hip_convolve_batch(static_cast<PFFFT_Setup*>(a->inner), (const float*)X, Hs, (float*)X, scaling, cnt, 0, 1, st);
+        if (rc) return rc;
+        hipLaunchKernelGGL((any_real_crop_kernel<T>), dim3(any_grid(cnt * (back ? N : H))), dim3(256), 0, st, (const cx<T>*)X, out + v0 * rout, w,
+                           cnt, N, H, M, back);
+        PF_CHECK(hipGetLastError());
+    }
+    return 0;
+}
+
+// direct route: the inner REAL setup's ordered transform, its canonical spectrum (DC, Nyquist, then bins 1 ... N/2 - 1) staged per stream
+template <typename T>
+static int any_real_direct(AnySetup* a, const T* in, T* out, size_t batch, int back, hipStream_t st) {
+    const size_t N = (size_t)a->N, H = (size_t)a->bins();
+    const size_t chunk = std::max<size_t>(1, std::min(batch, ANY_CAP_BYTES / (N * sizeof(T))));
+    std::lock_guard<std::mutex> lk(a->pad.mu);
+    void* p = nullptr;
+    int rc = any_scratch(a, st, chunk * N * sizeof(T), &p);
+    if (rc) return rc;
+    T* S = static_cast<T*>(p);
+    for (size_t v0 = 0; v0 < batch; v0 += chunk) {
+        const size_t cnt = std::min(batch - v0, chunk);
+        if (!back) {
+            if ((rc = transform_batch_any(a->inner, in + v0 * N, S, cnt, PFFFT_FORWARD, 1, st))) return rc;
+            hipLaunchKernelGGL((any_real_unpack_kernel<T>), dim3(any_grid(cnt * H)), dim3(256), 0, st, (const T*)S,
+                               reinterpret_cast<cx<T>*>(out) + v0 * H, cnt, N);
+            PF_CHECK(hipGetLastError());
+        } else {
+            hipLaunchKernelGGL((any_real_pack_kernel<T>), dim3(any_grid(cnt * H)), dim3(256), 0, st, reinterpret_cast<const cx<T>*>(in) + v0 * H, S,
+                               cnt, N);
+            PF_CHECK(hipGetLastError());
+            if ((rc = transform_batch_any(a->inner, S, out + v0 * N, cnt, PFFFT_BACKWARD, 1, st))) return rc;
+        }
+    }
+    return 0;
+}
+
+template <typename T>
+static int any_real_transform_batch(AnySetup* a, const T* in, T* out, size_t batch, int dir, hipStream_t st) {
+    const int back = dir == PFFFT_BACKWARD;
+    // (direct: transform_batch's 16- / 32-byte rule; otherwise one scalar on the real side, one complex value on the complex side)
+    const uintptr_t ar = a->route == ANY_DIRECT ? 4 * sizeof(T) : sizeof(T), ac = a->route == ANY_DIRECT ? 4 * sizeof(T) : 2 * sizeof(T);
+    if (((uintptr_t)in & ((back ? ac : ar) - 1)) || ((uintptr_t)out & ((back ? ar : ac) - 1)))
+        return bad(a->route == ANY_DIRECT ? "any: in / out not 16-byte (float) / 32-byte (double) aligned"
+                                          : "any: in / out not aligned to one scalar (real rows) / one complex value (spectra)");
+    int rc = any_ensure<T>(a, st);
+    if (rc || batch == 0) return rc;
+    const AnyRoute r = any_route_now(a, ab());
+    if (r == ANY_DIRECT) return any_real_direct<T>(a, in, out, batch, back, st);
+    if constexpr (sizeof(T) == 4)
+        if (r == ANY_FUSED) return back ? any_real_fused<BWD>(a, in, out, batch, st) : any_real_fused<FWD>(a, in, out, batch, st);
+    return any_real_composed<T>(a, in, out, batch, back, st);
+}
+
 // ------------------------------------------------------------------------------------------------ the entry
 template <typename T>
 static int any_transform_batch(void* setup, const T* in, T* out, size_t batch, int dir, hipStream_t st) {
@@ -268,6 +453,7 @@ static int any_transform_batch(void* setup, const T* in, T* out, size_t batch, i
     }
     if (dir != PFFFT_FORWARD && dir != PFFFT_BACKWARD) return bad("any: bad direction");
     if (batch && (!in || !out)) return bad("any: NULL in / out");
+    if (a->is_real) return any_real_transform_batch<T>(a, in, out, batch, dir, st);
     // (the direct route is transform_batch: its 16- / 32-byte rule; the other routes access one complex value at a time)
     const uintptr_t align = a->route == ANY_DIRECT ? 4 * sizeof(T) : 2 * sizeof(T);
     if (((uintptr_t)in | (uintptr_t)out) & (align - 1))
@@ -290,6 +476,8 @@ PF_EXPORT PFFFT_HIP_AnySetup* pffft_hip_any_new_setup(int N, pffft_transform_t t
 PF_EXPORT PFFFTD_HIP_AnySetup* pffftd_hip_any_new_setup(int N, pffft_transform_t tr) {
     return reinterpret_cast<PFFFTD_HIP_AnySetup*>(pf::any_new_setup(N, (int)tr, 1));
 }
+PF_EXPORT PFFFT_HIP_AnySetup* pffft_hip_any_new_real_setup(int N) { return reinterpret_cast<PFFFT_HIP_AnySetup*>(pf::any_new_real_setup(N, 0)); }
+PF_EXPORT PFFFTD_HIP_AnySetup* pffftd_hip_any_new_real_setup(int N) { return reinterpret_cast<PFFFTD_HIP_AnySetup*>(pf::any_new_real_setup(N, 1)); }
 PF_EXPORT void pffft_hip_any_destroy_setup(PFFFT_HIP_AnySetup* s) { pf::any_destroy_setup(reinterpret_cast<pf::AnySetup*>(s)); }
 PF_EXPORT void pffftd_hip_any_destroy_setup(PFFFTD_HIP_AnySetup* s) { pf::any_destroy_setup(reinterpret_cast<pf::AnySetup*>(s)); }
 PF_EXPORT int pffft_hip_any_transform_batch(PFFFT_HIP_AnySetup* s, const float* in, float* out, size_t batch, pffft_direction_t d, void* stream) {
@@ -302,6 +490,14 @@ PF_EXPORT int pffftd_hip_any_transform_batch(PFFFTD_HIP_AnySetup* s, const doubl
 PF_EXPORT int pffft_hip_any_conv_size(const void* setup) {
     const pf::AnySetup* a = pf::any_checked(setup);
     return a ? a->M : -1;
+}
+PF_EXPORT int pffft_hip_any_is_real(const void* setup) {
+    const pf::AnySetup* a = pf::any_checked(setup);
+    return a ? a->is_real : -1;
+}
+PF_EXPORT int pffft_hip_any_bins(const void* setup) {
+    const pf::AnySetup* a = pf::any_checked(setup);
+    return a ? a->bins() : -1;
 }
 PF_EXPORT const char* pffft_hip_any_route(const void* setup) {
     const pf::AnySetup* a = pf::any_checked(setup);
