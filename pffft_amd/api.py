@@ -123,6 +123,7 @@ def lib():
     L.pffft_hip_any_bins.restype = C.c_int; L.pffft_hip_any_bins.argtypes = [C.c_void_p]
     L.pffft_hip_kernel_name.restype = C.c_char_p; L.pffft_hip_kernel_name.argtypes = [C.c_void_p]
     L.pffft_hip_describe.restype = C.c_int; L.pffft_hip_describe.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+    L.pffft_hip_route_occupancy.restype = C.c_int; L.pffft_hip_route_occupancy.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.pffft_hip_setup_devices.restype = C.c_int; L.pffft_hip_setup_devices.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_int]
     L.pffft_hip_last_error.restype = C.c_char_p
     L.pffft_hip_device_count.restype = C.c_int
@@ -200,6 +201,15 @@ def describe(setup: "Setup") -> str:
     if n < 0:
         raise ValueError("pffft_hip_describe: invalid handle")
     return buf.value.decode()
+
+
+def route_occupancy(setup: "Setup", direction, ordered) -> int:
+    """pffft_hip_route_occupancy: resident workgroups per CU of the LDS-resident kernel a (direction, layout) runs on, as its launcher sees
+    them; 0 where the route has no single persistent kernel of the tiled / Stockham / single-image families.  Needs a device."""
+    n = lib().pffft_hip_route_occupancy(setup.handle, int(direction), int(bool(ordered)))
+    if n < 0:
+        raise RuntimeError("pffft_hip_route_occupancy failed: " + lib().pffft_hip_last_error().decode())
+    return n
 
 
 def setup_devices(setup: "Setup"):

@@ -1205,19 +1205,20 @@ static int describe_route(const Setup* s, const Route& r, int dir, int ordered, 
     switch (r.fam) {
         case FAM_TINY: return snprintf(buf, len, "tiny: one thread per transform, %s", launch_rule_name(r.rule));
         case FAM_C1024:
-            return snprintf(buf, len, "c1024_f32: loop 8 waves/wg x 1 wg/CU %s; <= %d resident sets: once kernel %d waves/wg %s",
-                            launch_rule_name(r.rule), r.oneshot, C1024_ONCE_W, launch_rule_name(LR_DISPATCH));
+            return snprintf(buf, len, "c1024_f32: loop 8 waves/wg x 1 wg/CU %s; <= %d resident sets: once kernel %d waves/wg %s, resident set %d waves/CU",
+                            launch_rule_name(r.rule), r.oneshot, C1024_ONCE_W, launch_rule_name(LR_DISPATCH), C1024_ONCE_RESIDENT);
         case FAM_TILED:
             return snprintf(buf, len, "tiled: cfg %s wg %d vec/wg %d lds %zu %s oneshot<=%d groups/wg", r.tiled.cfg, r.tiled.wg, r.tiled.t_per_wg,
                             r.tiled.lds, launch_rule_name(r.rule), r.oneshot);
         case FAM_STOCK: {
-            char grid[48];
+            char grid[48], once[48] = "";
+            if (r.rule == LR_INORDER && r.oneshot) snprintf(once, sizeof once, " oneshot<=%d groups/wg", r.oneshot);
             if (r.stock.groups_per_wg > 0) snprintf(grid, sizeof grid, "%d groups/wg (table)", r.stock.groups_per_wg);
             else snprintf(grid, sizeof grid, "%d x resident set", r.stock.grid_mul);
             return snprintf(buf, len, "stockham: %s%s%s threads %d lds %zu %s grid %s%s", r.stock.wl ? "wave-local" : "workgroup",
                             r.stock.df ? " direct-first-stage" : " deposit", r.stock.fn ? "" : " run-time-plan", r.stock.threads, r.stock.lds,
                             launch_rule_name(r.rule), r.rule == LR_INORDER ? "resident set" : grid,
-                            r.rule == LR_INORDER ? (r.oneshot ? " oneshot" : "") : "");
+                            once);
         }
         case FAM_BIG: {
             const BigPlan& b = r.big;

@@ -252,7 +252,7 @@ def test_graph_replay_capture_rule_and_two_streams():
     """The first call builds the tables: during a capture it is refused.  A composed call that would have to grow its scratch image during
     capture is hipErrorStreamCaptureUnsupported with nothing launched.  After a warm call both routes replay from a captured graph (three
     replays, the input changed between them) while a second stream runs the same setup."""
-    N, batch = 1021, 5000                                                  # 625 groups of 8: past the static ones of every workgroup
+    N, batch = 1021, 5000         # at most 4 groups per resident workgroup: one group per workgroup in dispatch order, no counter (the loop: test_gpu_launch_shapes.py)
     s = pa.AnySetup(N, pa.COMPLEX, np.float32)
     st = torch.cuda.Stream()
     try:

@@ -292,7 +292,7 @@ def test_batch_beyond_the_scratch_cap_runs_in_chunks():
 def test_graph_replay_capture_rule_and_two_streams():
     """The first call builds the tables: during a capture it fails with hipErrorStreamCaptureUnsupported and launches nothing.  After a
     warm call both routes replay from a captured graph with the warm call's bits, while a second stream runs the same setup."""
-    N, batch = 1021, 5000                                                  # 625 groups of 8: past the static ones of every workgroup
+    N, batch = 1021, 5000         # at most 4 groups per resident workgroup: one group per workgroup in dispatch order, no counter (the loop: test_gpu_launch_shapes.py)
     H2 = 2 * rm.bins(N)
     s = pa.AnyRealSetup(N, np.float32)
     st = torch.cuda.Stream()
