@@ -234,6 +234,41 @@ int pffftd_hip_frames_overlap_add_batch(PFFFTD_Setup *, const double *spectra, s
  * Host arithmetic only; PFFFT_Setup and PFFFTD_Setup handles. */
 const char *pffft_hip_frames_route(const void *setup, size_t hop, size_t signal_stride, size_t out_stride, int output);
 
+/* Averaged power spectra over overlapping frames (Welch's method; one row of a time-averaged spectrogram per navg frames) without the
+ * nframes x P intermediate.  Framing, `window` (NULL = no product), `hop`, `signal_stride`, the sample / scalar rules and the pointer rules
+ * are exactly those of pffft_hip_frames_transform_batch; real and complex setups, float and double, every legal size.
+ * GROUPING.  navg == 0 means navg = nframes (one row per signal: Welch); otherwise nframes % navg must be 0.  With G = nframes / navg,
+ * group g of signal i is frames g*navg ... g*navg + navg - 1, and output row v = i*G + g is written at out + v*out_stride (0 = dense).  A
+ * row holds P scalars: N/2 + 1 for a real setup (bins 0 ... N/2, DC and Nyquist unpacked), N for a complex one.
+ * ARITHMETIC - THE ORDER IS PART OF THE CONTRACT.  p_f[k] is the value pffft_hip_frames_transform_batch(..., PFFFT_HIP_FRAMES_POWER)
+ * produces for frame f, bit for bit.  A group is cut into runs of PFFFT_HIP_PSD_RUN consecutive frames (the last run may be shorter); a
+ * run's partial is the sum of its p_f[k], f ascending, started from the first term, every addition rounded once; the group's value is the
+ * sum of its run partials, run ascending, started from the first; the result is multiplied ONCE by `scaling` (1/(navg * sum w^2 * fs) or
+ * whatever the caller's normalisation is: the library normalises nothing).  No atomics and no FMA: the result is deterministic and equal
+ * on every route.
+ * Real float setups of N = 1024 / 2048 / 4096 run FUSED when hop and signal_stride are multiples of 4 and signal and window are 16-byte
+ * aligned (out needs scalar alignment only): the framed kernel keeps a workgroup slot on the consecutive frames of one run, accumulates
+ * |X|^2 in registers and stores once per run - hop + P / min(navg, 32) scalars of HBM traffic per frame; averages longer than one run
+ * leave their run partials in a per-stream partial buffer that a small second kernel adds up.  Everything else is COMPOSED: the framing
+ * kernel into the per-stream frame matrix (256 MiB cap, chunks of whole runs; as large as one run needs where a run exceeds the cap),
+ * pffft_hip_transform_batch(ordered = 1), a kernel that adds the |X|^2 of each run's rows in order, and the same reduction.  The partial
+ * buffer holds at most 256 MiB (one group's partials where a group needs more) and is gone through in whole groups.  Both buffers grow
+ * outside HIP graph capture only: a call that would have to grow one while `stream` is capturing fails with
+ * hipErrorStreamCaptureUnsupported and launches nothing.  signal and out must not overlap.
+ * Validation happens before any device is touched: a NULL or foreign setup or the other precision's handle, hop == 0, nframes % navg != 0,
+ * an out_stride smaller than P, a signal_stride smaller than one signal's scalars when nsignals > 1, a NULL signal / out -> non-zero,
+ * nothing launched.  nsignals == 0 or nframes == 0 -> 0, nothing launched. */
+#define PFFFT_HIP_PSD_RUN 32
+int pffft_hip_frames_psd_batch(PFFFT_Setup *, const float *signal, size_t signal_stride, size_t nsignals, size_t nframes, size_t hop,
+                               const float *window, size_t navg, float scaling, float *out, size_t out_stride, void *stream);
+int pffftd_hip_frames_psd_batch(PFFFTD_Setup *, const double *signal, size_t signal_stride, size_t nsignals, size_t nframes, size_t hop,
+                                const double *window, size_t navg, double scaling, double *out, size_t out_stride, void *stream);
+/* The route pffft_hip_frames_psd_batch takes for these arguments under the calling thread's selector (pffft_hip_set_variant: 134 = always
+ * composed, 135 = fused wherever it is legal): "fused" or "composed"; "" for an invalid handle or hop == 0.  Pointer alignment is checked
+ * at the call: the query assumes 16-byte aligned pointers.  signal_stride = 0: one signal; navg = 0: every frame of a signal.
+ * Host arithmetic only; PFFFT_Setup and PFFFTD_Setup handles. */
+const char *pffft_hip_frames_psd_route(const void *setup, size_t hop, size_t signal_stride, size_t navg);
+
 /* Polyphase filter-bank analysis (weighted overlap-add channelizer): the framing of pffft_hip_frames_transform_batch with a prototype
  * filter of taps*N real coefficients that is folded onto N points before the transform.  For frame f of signal i
  *     u_f[j] = sum over p = 0 ... taps-1 of  prototype[p*N + j] * x_i[f*hop + p*N + j],   j < N

@@ -80,6 +80,9 @@ def lib():
         g("hip_frames_transform_batch").restype = C.c_int
         g("hip_frames_transform_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
                                                     C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+        g("hip_frames_psd_batch").restype = C.c_int
+        g("hip_frames_psd_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p,
+                                              C.c_size_t, ct, C.c_void_p, C.c_size_t, C.c_void_p]
         g("hip_pfb_transform_batch").restype = C.c_int
         g("hip_pfb_transform_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
                                                  C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
@@ -114,6 +117,8 @@ def lib():
                                                   C.c_double, C.c_void_p]
     L.pffft_hip_frames_route.restype = C.c_char_p
     L.pffft_hip_frames_route.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int]
+    L.pffft_hip_frames_psd_route.restype = C.c_char_p
+    L.pffft_hip_frames_psd_route.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t]
     L.pffft_hip_pfb_route.restype = C.c_char_p
     L.pffft_hip_pfb_route.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int]
     L.pffft_hip_any_conv_size.restype = C.c_int; L.pffft_hip_any_conv_size.argtypes = [C.c_void_p]
@@ -227,6 +232,15 @@ def frames_route(setup: "Setup", hop, signal_stride=0, out_stride=0, output="ord
     thread's selector.  Host arithmetic only."""
     return lib().pffft_hip_frames_route(setup.handle, int(hop), int(signal_stride), int(out_stride),
                                         FRAMES_OUTPUTS[output]).decode()
+
+
+PSD_RUN = 32   # PFFFT_HIP_PSD_RUN of include/pffft_hip.h
+
+
+def frames_psd_route(setup: "Setup", hop, signal_stride=0, navg=0) -> str:
+    """pffft_hip_frames_psd_route: "fused" / "composed" for an averaged-power call with 16-byte aligned pointers, under the calling
+    thread's selector.  Host arithmetic only."""
+    return lib().pffft_hip_frames_psd_route(setup.handle, int(hop), int(signal_stride), int(navg)).decode()
 
 
 PFB_FUSED_MAX_TAPS = 16   # PFFFT_HIP_PFB_FUSED_MAX_TAPS of include/pffft_hip.h
@@ -405,6 +419,35 @@ class Setup:
         fn = getattr(self._L, f"{self._pfx}_hip_frames_transform_batch")
         _check(fn(self.handle, signal.data_ptr(), sstride, nsig, nframes, hop, window.data_ptr() if window is not None else None,
                   out.data_ptr(), pitch, FRAMES_OUTPUTS[output], self._stream()), "hip_frames_transform_batch")
+        return out
+
+    def frames_psd_batch(self, signal, hop, nframes=None, window=None, navg=0, scaling=1.0, out=None):
+        """pffft_hip_frames_psd_batch: |X|^2 of the frames of frames_transform_batch, averaged over groups of `navg` consecutive frames
+        (0 = every frame of a signal: Welch) in the documented order and multiplied once by `scaling`.  Returns [nsignals,] nframes / navg,
+        P]; `out` may have padded rows (its stride(-2) is the row pitch)."""
+        import torch
+        spp = 2 if self.transform_type == COMPLEX else 1
+        nsig, sstride, scalars = self._frames_rows(signal, "signal")
+        samples = scalars // spp
+        if nframes is None:
+            assert samples >= self.N, "the signal holds no frame"
+            nframes = (samples - self.N) // hop + 1
+        assert nframes == 0 or (nframes - 1) * hop + self.N <= samples, "the signal is shorter than its frames"
+        per = navg if navg else nframes
+        assert nframes == 0 or nframes % per == 0, "nframes must be a multiple of navg"
+        groups = nframes // per if nframes else 0
+        row = self.frames_out_row("power")
+        if out is None:
+            out = torch.empty((nsig, groups, row) if signal.dim() == 2 else (groups, row), dtype=signal.dtype, device=signal.device)
+        assert out.dtype == signal.dtype and out.is_cuda and out.stride(-1) == 1 and out.shape[-1] == row and out.shape[-2] == groups
+        assert out.dim() == 2 or (out.dim() == 3 and out.shape[0] == nsig)
+        pitch = out.stride(-2) if groups > 1 else (out.stride(0) if out.dim() == 3 and nsig > 1 else row)
+        assert out.dim() == 2 or nsig == 1 or out.stride(0) == groups * pitch, "row v = i groups + g is written at v * pitch"
+        if window is not None:
+            assert window.is_cuda and window.dtype == signal.dtype and window.is_contiguous() and window.numel() == self.N
+        fn = getattr(self._L, f"{self._pfx}_hip_frames_psd_batch")
+        _check(fn(self.handle, signal.data_ptr(), sstride, nsig, nframes, hop, window.data_ptr() if window is not None else None,
+                  int(navg), float(scaling), out.data_ptr(), pitch, self._stream()), "hip_frames_psd_batch")
         return out
 
     def pfb_transform_batch(self, signal, hop, prototype, nframes=None, out=None, output="internal"):

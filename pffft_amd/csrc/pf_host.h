@@ -99,6 +99,9 @@ struct Setup {
     StreamScratch conv;
     // frame matrix of the composed pffft_hip_frames_* routes (frames_tu.hip): one per stream, frames.mu held while a call enqueues
     StreamScratch frames;
+    // run partials of pffft_hip_frames_psd_batch for averages longer than one run (psd_tu.hip): one per stream, psd.mu held while a call
+    // enqueues (taken BEFORE frames.mu where a call needs both)
+    StreamScratch psd;
     DevBuf d_stage[3];     // staging for host-pointer legacy calls
     PinnedBuf h_stage[4];  // pinned host images the kernels read / write directly (small vectors)
 };

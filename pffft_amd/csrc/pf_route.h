@@ -75,6 +75,8 @@ enum AbValue : int {
     AB_PFB_SYN_XCD = 131,       // ... the gather's tiles in XCD-contiguous sweeps, whatever the measured default is (same arithmetic)
     AB_ANY_COMPOSED = 132,      // pffft_hip_any_transform_batch: never the fused chirp kernel (pad kernel + convolve_batch + crop kernel)
     AB_ANY_FUSED = 133,         // ... the fused chirp kernel wherever it is legal (today the default in every legal cell)
+    AB_PSD_COMPOSED = 134,      // pffft_hip_frames_psd_batch: framing kernel + transform_batch + run kernel through the frame matrix
+    AB_PSD_FUSED = 135,         // ... the accumulating framed kernel wherever it is legal, whatever the measured default of the size is
     AB_FAKE_DEVICE = 130,      // the calling thread counts as being on ANOTHER device than its current one (key + 64): exercises the per-device
                                 // replicas of a shared setup on a box with one GPU (tests/test_gpu_round6.py)
 };

@@ -1,0 +1,222 @@
+// libpffft_hip.so, translation unit of the averaged-power-spectrum entries (include/pffft_hip.h: pffft_hip_frames_psd_batch,
+// pffft_hip_frames_psd_route): validation, route decision, the fused kernel's instantiations and the composed route through the per-stream
+// frame matrix.  Kernels: fft_psd.h; the frame matrix and the framing kernel: frames_host.h / fft_frames.h.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "../../include/pffft_hip.h"
+#include "frames_host.h"
+#include "fft_psd.h"
+
+struct PFFFT_Setup : pf::Setup {};
+struct PFFFTD_Setup : pf::Setup {};
+
+#define PF_EXPORT extern "C" __attribute__((visibility("default")))
+
+static_assert(pf::PSD_RUN == PFFFT_HIP_PSD_RUN, "the run length is part of the contract");
+
+namespace pf {
+
+// The partial buffer of one call holds at most this many bytes (one group's partials where a group needs more): the call goes through it in
+// whole groups.
+constexpr size_t PSD_CAP_BYTES = (size_t)256 << 20;
+// runs of one fused launch (the kernel counts them in 32 bits)
+constexpr size_t PSD_SLICE = (size_t)3 << 30;
+
+// ------------------------------------------------------------------------------------------------ fused
+typedef void (*PsdFn)(const float*, size_t, unsigned, unsigned, size_t, const float*, float*, size_t, size_t, unsigned, float,
+                      const cx<float>*, const cx<float>*, unsigned*);
+struct PsdSel { PsdFn fn = nullptr; size_t lds = 0; int wg = 0, t_per_wg = 0; };
+
+// Window values: resident in registers (WMODE 1), as in the frame kernel.  With the E + 1 accumulators on top of them the resource remarks
+// of the three configurations still show no scratch and the occupancy of fft_frames_kernel<C, FR_POWER, 1>, so the LDS
+// twin (WMODE 2) is not needed.
+constexpr int PSD_WMODE = 1;
+
+template <class C>
+static PsdSel psd_sel(bool windowed) {
+    PsdSel e;
+    e.wg = C::WG_THREADS; e.t_per_wg = C::T_PER_WG;
+    e.lds = frames_lds_bytes<C>(windowed ? PSD_WMODE : 0);
+    e.fn = windowed ? fft_psd_kernel<C, PSD_WMODE> : fft_psd_kernel<C, 0>;
+    return e;
+}
+
+// The frame entry's rule: p_f equals the POWER output of pffft_hip_frames_transform_batch bit for bit only on the configuration
+// transform_batch(ordered = 1) runs on, so that is read from the setup's stored route.
+static bool psd_fusable_setup(const Setup* s, PsdSel* e, bool windowed) {
+    if (s->is_double || s->transform != PFFFT_REAL || s->kernel != K_TILED) return false;
+    const Route& r = s->route[PFFFT_FORWARD][1];
+    if (r.fam != FAM_TILED) return false;
+    const std::string cfg = r.tiled.cfg;
+    if (s->n == 512 && cfg == "TiledPick::C512") { if (e) *e = psd_sel<TiledPick<float>::C512>(windowed); return true; }
+    if (s->n == 1024 && cfg == "TiledPick::C1024") { if (e) *e = psd_sel<TiledPick<float>::C1024>(windowed); return true; }
+    if (s->n == 2048 && cfg == "TiledPick::C2048") { if (e) *e = psd_sel<TiledPick<float>::C2048>(windowed); return true; }
+    return false;
+}
+
+// sizes where the fused kernel is the default: all three until a measurement says otherwise (tests/test_gpu_psd.py times every cell; a size
+// that loses returns false here and stays reachable through AB_PSD_FUSED)
+static bool psd_fused_default(int n) {
+    (void)n;
+    return true;
+}
+
+// the route of a call whose pointers are 16-byte aligned: true = fused
+static bool psd_route_fused(const Setup* s, size_t hop, size_t signal_stride, size_t navg, const AbSel& sel) {
+    if (sel.is(AB_PSD_COMPOSED)) return false;
+    if (!psd_fusable_setup(s, nullptr, true)) return false;
+    if (hop % 4 || signal_stride % 4) return false;       // 16-byte loads of every frame and every signal; the rows are stored scalar by scalar
+    if (navg > 0xffffffffull) return false;               // (the kernel counts the frames of one average in 32 bits)
+    return sel.is(AB_PSD_FUSED) || psd_fused_default(s->n);
+}
+
+static int launch_psd_fused(Setup* s, const PsdSel& e, const float* signal, size_t signal_stride, size_t G, size_t navg, size_t hop,
+                            const float* window, float* dst, size_t dst_stride, size_t row0, size_t nruns, float scale, hipStream_t st) {
+    int rc = allow_big_lds(e.fn, e.lds);
+    if (rc) return rc;
+    int per_cu = 0;
+    if ((rc = cached_occupancy(reinterpret_cast<const void*>(e.fn), e.wg, e.lds, &per_cu))) return rc;
+    const size_t groups = (nruns + e.t_per_wg - 1) / e.t_per_wg;
+    size_t grid = (size_t)num_cus() * per_cu;
+    const int oneshot = env().oneshot;    // the launch rule of launch_tiled
+    if (oneshot > 0 && groups <= (size_t)oneshot * grid) grid = groups;
+    if (grid > groups) grid = groups;
+    unsigned* ctr = groups <= grid ? nullptr : take_counters(s, st);
+    hipLaunchKernelGGL(e.fn, dim3((unsigned)grid), dim3(e.wg), e.lds, st, signal, signal_stride, (unsigned)G, (unsigned)navg, hop, window, dst,
+                       dst_stride, row0, (unsigned)nruns, scale, s->d_tw.as<cx<float>>(), s->d_twr.as<cx<float>>(), ctr);
+    PF_CHECK(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ shared pieces
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// the partial buffer of `st` (psd.mu held by the caller), grown to `bytes`: outside graph capture only
+static int psd_buffer(Setup* s, hipStream_t st, size_t bytes, void** buf) {
+    StreamScratch::Entry& sc = s->psd.acquire(st);
+    if (sc.buf[0].bytes() < bytes && stream_capturing(st))
+        return bad("the partial buffer of this stream would have to grow during graph capture: run the call once on this stream before capturing",
+                   hipErrorStreamCaptureUnsupported);
+    if (int rc = s->psd.grow(sc, 0, bytes)) return rc;
+    *buf = sc.buf[0].get();
+    return 0;
+}
+
+template <typename T>
+static int psd_batch(Setup* s, const T* signal, size_t signal_stride, size_t nsignals, size_t nframes, size_t hop, const T* window,
+                     size_t navg, T scaling, T* out, size_t out_stride, hipStream_t st) {
+    if (!s || s->magic != MAGIC || s->is_double != (sizeof(T) == 8)) {
+        g_last_error = "pffft_hip: bad setup handle";
+        return (int)hipErrorInvalidHandle;
+    }
+    if (hop == 0) return bad("psd: hop == 0");
+    if (nsignals == 0 || nframes == 0) return 0;
+    if (navg == 0) navg = nframes;
+    if (nframes % navg) return bad("psd: nframes is no multiple of navg");
+    const bool real = s->transform == PFFFT_REAL;
+    const size_t spp = real ? 1 : 2, N = (size_t)s->N, row = s->vec_scalars;
+    const size_t P = real ? N / 2 + 1 : N;
+    if (out_stride == 0) out_stride = P;
+    if (out_stride < P) return bad("psd: out_stride smaller than one output row");
+    const size_t sig_scalars = ((nframes - 1) * hop + N) * spp;
+    if (nsignals > 1 && signal_stride < sig_scalars) return bad("psd: signal_stride smaller than one signal's samples");
+    if (!signal || !out) return bad("psd: NULL signal / out");
+    const size_t hop_s = hop * spp, G = nframes / navg, V = nsignals * G;   // V output rows; row v = i G + g
+    const size_t rpg = (navg + PSD_RUN - 1) / PSD_RUN;                       // runs per group
+    if (nsignals == 1) signal_stride = 0;   // (one signal: the stride is not read)
+
+    int rc;
+    s = for_device(s);
+    if ((rc = ensure_device_any(s))) return rc;
+    const AbSel sel = ab();
+    PsdSel e;
+    bool fused = false;
+    if constexpr (sizeof(T) == 4)
+        fused = psd_route_fused(s, hop, signal_stride, navg, sel) && aligned16(signal) && (!window || aligned16(window)) && G <= 0xffffffffull &&
+                psd_fusable_setup(s, &e, window != nullptr);
+
+    // Averages of one run are scaled and stored by the run itself.  Longer ones go through the partial buffer in whole groups: `vstep`
+    // output rows per pass, then the reduction of those rows.
+    size_t vstep = V;
+    if (rpg > 1) vstep = std::max<size_t>(1, PSD_CAP_BYTES / (rpg * P * sizeof(T)));
+    if (fused) vstep = std::min(vstep, std::max<size_t>(1, PSD_SLICE / rpg));
+    vstep = std::min(vstep, V);
+    // composed: the frames of whole runs through the frame matrix (as large as one run needs where a run exceeds the cap)
+    const size_t lfull = std::min<size_t>(navg, PSD_RUN);
+    const size_t cap_rows = std::max<size_t>(1, FRAMES_CAP_BYTES / (row * sizeof(T)));
+    const size_t crun = std::max<size_t>(1, cap_rows / lfull);
+    auto first_frame = [&](size_t r) { return (r / rpg) * navg + (r % rpg) * PSD_RUN; };   // in the numbering v = i nframes + f
+
+    std::unique_lock<std::mutex> lkp(s->psd.mu, std::defer_lock), lkf(s->frames.mu, std::defer_lock);
+    void* buf = nullptr;
+    T* part = nullptr;
+    T* X = nullptr;
+    if (rpg > 1) {
+        lkp.lock();
+        if ((rc = psd_buffer(s, st, vstep * rpg * P * sizeof(T), &buf))) return rc;
+        part = (T*)buf;
+    }
+    if (!fused) {
+        lkf.lock();
+        const size_t rows_x = std::min(V * navg, std::min(crun, vstep * rpg) * lfull);
+        if ((rc = frames_buffer(s, st, rows_x * row * sizeof(T), &buf))) return rc;
+        X = (T*)buf;
+    }
+    constexpr int U = 16 / (int)sizeof(T);
+    const bool wide = aligned16(signal) && signal_stride % U == 0 && hop_s % U == 0;
+    for (size_t v0 = 0; v0 < V; v0 += vstep) {
+        const size_t rows = std::min(V - v0, vstep), ra = v0 * rpg, rb = (v0 + rows) * rpg;
+        T* dst = rpg == 1 ? out + v0 * out_stride : part;
+        const size_t dstride = rpg == 1 ? out_stride : P;
+        const T scale = rpg == 1 ? scaling : (T)1;
+        if (fused) {
+            if constexpr (sizeof(T) == 4)
+                if ((rc = launch_psd_fused(s, e, signal, signal_stride, G, navg, hop_s, window, dst, dstride, v0, rb - ra, scale, st))) return rc;
+        } else {
+            for (size_t r = ra; r < rb; r += crun) {
+                const size_t cnt = std::min(rb - r, crun), fa = first_frame(r), nfr = first_frame(r + cnt) - fa;
+                if (wide)
+                    hipLaunchKernelGGL((frames_gather_kernel<T, U>), dim3(stream_grid(nfr * row / U)), dim3(256), 0, st, signal, signal_stride,
+                                       nframes, hop_s, (int)spp, window, X, fa, nfr, (unsigned)row);
+                else
+                    hipLaunchKernelGGL((frames_gather_kernel<T, 1>), dim3(stream_grid(nfr * row)), dim3(256), 0, st, signal, signal_stride,
+                                       nframes, hop_s, (int)spp, window, X, fa, nfr, (unsigned)row);
+                PF_CHECK(hipGetLastError());
+                if ((rc = transform_batch_any(s, X, X, nfr, PFFFT_FORWARD, 1, st))) return rc;
+                if (real)
+                    hipLaunchKernelGGL((psd_runs_kernel<T, 1>), dim3(stream_grid(cnt * P)), dim3(256), 0, st, X, (unsigned)row, r, cnt, navg, rpg,
+                                       dst + (r - ra) * dstride, dstride, scale);
+                else
+                    hipLaunchKernelGGL((psd_runs_kernel<T, 0>), dim3(stream_grid(cnt * P)), dim3(256), 0, st, X, (unsigned)row, r, cnt, navg, rpg,
+                                       dst + (r - ra) * dstride, dstride, scale);
+                PF_CHECK(hipGetLastError());
+            }
+        }
+        if (rpg > 1) {
+            hipLaunchKernelGGL((psd_reduce_kernel<T>), dim3(stream_grid(rows * P)), dim3(256), 0, st, part, rpg, (unsigned)P, rows, scaling,
+                               out + v0 * out_stride, out_stride);
+            PF_CHECK(hipGetLastError());
+        }
+    }
+    return 0;
+}
+
+}  // namespace pf
+
+PF_EXPORT int pffft_hip_frames_psd_batch(PFFFT_Setup* s, const float* signal, size_t signal_stride, size_t nsignals, size_t nframes, size_t hop,
+                                         const float* window, size_t navg, float scaling, float* out, size_t out_stride, void* stream) {
+    return pf::psd_batch<float>(s, signal, signal_stride, nsignals, nframes, hop, window, navg, scaling, out, out_stride, (hipStream_t)stream);
+}
+PF_EXPORT int pffftd_hip_frames_psd_batch(PFFFTD_Setup* s, const double* signal, size_t signal_stride, size_t nsignals, size_t nframes,
+                                          size_t hop, const double* window, size_t navg, double scaling, double* out, size_t out_stride,
+                                          void* stream) {
+    return pf::psd_batch<double>(s, signal, signal_stride, nsignals, nframes, hop, window, navg, scaling, out, out_stride, (hipStream_t)stream);
+}
+
+PF_EXPORT const char* pffft_hip_frames_psd_route(const void* setup, size_t hop, size_t signal_stride, size_t navg) {
+    const pf::Setup* s = static_cast<const pf::Setup*>(setup);
+    if (!s || s->magic != pf::MAGIC || hop == 0) return "";
+    return pf::psd_route_fused(s, hop, signal_stride, navg, pf::ab()) ? "fused" : "composed";
+}
