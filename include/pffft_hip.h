@@ -427,6 +427,58 @@ PFFFTD_HIP_AnySetup *pffftd_hip_any_new_real_setup(int N);
 int pffft_hip_any_is_real(const void *setup);
 int pffft_hip_any_bins(const void *setup);
 
+/* ZOOM transforms (the chirp-z transform on the unit circle, scipy's zoom_fft): K spectral lines from f0 in steps of df, both in cycles
+ * per sample (finite doubles of any sign and magnitude), of rows of N samples - where the any-length setups answer "the DFT of these N
+ * samples", this one answers "K lines between two frequencies at a resolution of my choosing" without padding to a long size or mixing,
+ * decimating and transforming in three calls:
+ *     out[v][k] = sum_{n<N} in[v][n] * exp(-/+ 2 pi j n (f0 + k df)),   k < K     (forward / backward; UNSCALED)
+ * `in` holds batch dense rows of N interleaved complex values, `out` batch dense rows of K.  BACKWARD is the conjugate kernel,
+ * conj(zoom(conj x)) - it is NOT an inverse.  f0 = 0, df = 1 / N, K = N is the DFT.  Real-input rows and spirals off the unit circle
+ * (|w| != 1, |a| != 1 of the general chirp-z transform) are not offered.  NULL for N < 1, K < 1, N + K - 1 > 2^26 (the library's
+ * largest setup) or a non-finite f0 / df.  Creating a setup touches no device.
+ * Bluestein's algorithm on the library's own convolution, with n k df = (n^2 + k^2 - (k - n)^2) df / 2:
+ *     a[n] = exp(-2 pi j frac(n f0 + n^2 df / 2)), n < N      c[k] = exp(-2 pi j frac(k^2 df / 2)), k < K
+ *     b[m] = exp(+2 pi j frac(m^2 df / 2)), -(N-1) <= m <= K-1     out[k] = c[k] sum_n (in[n] a[n]) b[k - n]     (circular length M >= N + K - 1)
+ * THE PHASE REDUCTION IS PART OF THE CONTRACT: frac is taken from the exact rational value of the doubles (a double is an integer times a
+ * power of two; n^2 times a 53-bit mantissa fits 128 bits), the reduced phase in (-1/2, 1/2] is rounded once to long double and multiplied
+ * by 2 pi there, cos and sin are rounded once to the table's type.  a and c are in the setup's type, the filter b always in double; its
+ * spectrum comes from the double transform and is rounded once.
+ * in / out are device pointers aligned to one complex value (8 / 16 bytes).  in and out MUST NOT OVERLAP (their rows differ in size):
+ * overlapping ranges are refused.  The call is asynchronous on `stream`; 0, else a hipError_t with its text in pffft_hip_last_error().
+ * Validation happens before any device is touched: a NULL or foreign handle or the other precision's, a bad direction, NULL, misaligned
+ * or overlapping in / out -> non-zero, nothing launched.
+ * Routes, planned once at setup (pffft_hip_zoom_route names the one a call takes under the calling thread's selector):
+ *   "fused"     float and M2 = the next power of two >= N + K - 1 is 512, 1024, 2048 or 4096 (257 <= N + K - 1 <= 4096): ONE kernel - the
+ *               fused convolution kernel of pffft_hip_convolve_batch with a loader that takes N samples times a (zeros above N) and a
+ *               store that writes the first K results times c: 8 N bytes read and 8 K written per row.  The default at all four lengths: on
+ *               an MI355X it takes 0.37 ... 0.64 of the composed route's time.
+ *   "composed"  double, every other N + K - 1, selector 136 everywhere: a pad kernel (times a) into a per-stream scratch image of
+ *               batch x M, pffft[d]_hip_convolve_batch on an inner setup of length M with one broadcast filter spectrum, a crop kernel
+ *               (times c, K values).  M = pffft_nearest_transform_size(N + K - 1, PFFFT_COMPLEX, higher); a setup that can run fused
+ *               uses M2 on both routes.
+ * The first-call table build and its stream-capture rule, one setup per device, the 256 MiB per-stream scratch with chunking and its
+ * capture rule, batch == 0 (builds the tables, launches nothing else, returns 0): as for the any-length complex setup above. */
+typedef struct PFFFT_HIP_ZoomSetup PFFFT_HIP_ZoomSetup;
+typedef struct PFFFTD_HIP_ZoomSetup PFFFTD_HIP_ZoomSetup;
+PFFFT_HIP_ZoomSetup *pffft_hip_zoom_new_setup(int N, int K, double f0, double df);
+PFFFTD_HIP_ZoomSetup *pffftd_hip_zoom_new_setup(int N, int K, double f0, double df);
+void pffft_hip_zoom_destroy_setup(PFFFT_HIP_ZoomSetup *);     /* NULL-safe */
+void pffftd_hip_zoom_destroy_setup(PFFFTD_HIP_ZoomSetup *);
+int pffft_hip_zoom_transform_batch(PFFFT_HIP_ZoomSetup *, const float *in, float *out, size_t batch, pffft_direction_t direction,
+                                   void *stream);
+int pffftd_hip_zoom_transform_batch(PFFFTD_HIP_ZoomSetup *, const double *in, double *out, size_t batch, pffft_direction_t direction,
+                                    void *stream);
+/* Host arithmetic only, handles of both precisions.  pffft_hip_zoom_conv_size: the convolution length M; -1 for an invalid handle.
+ * pffft_hip_zoom_route: "fused" / "composed" under the calling thread's selector (pffft_hip_set_variant: 136 = never fused, 137 = fused
+ * wherever it is legal); "" for an invalid handle.  pffft_hip_zoom_table: the host evaluation of the phase functions above, `count` values
+ * from index `first` as interleaved (re, im) pairs rounded to the setup's type into host_out: which = 0 is a (indices below N: the values
+ * of the device's input table), which = 1 is c for indices below max(N, K) (below K the values of the device's output table; the filter
+ * is conj(c[|m|]) in double, so the indices from K to N - 1 exist in the filter only).  0; non-zero for an invalid handle, another
+ * `which`, a range beyond these counts or a NULL host_out. */
+int pffft_hip_zoom_conv_size(const void *setup);
+const char *pffft_hip_zoom_route(const void *setup);
+int pffft_hip_zoom_table(const void *setup, int which, size_t first, size_t count, void *host_out);
+
 /* Overlap-save FIR on device-resident signal/output (same block schedule as pffastconv_apply,
  * src/pffastconv.c:204-261): returns the number of output samples written, or -1 on error. */
 int pffastconv_hip_apply_device(PFFASTCONV_Setup *, const float *d_input, int inputLen, float *d_output,

@@ -97,6 +97,10 @@ def lib():
         g("hip_any_destroy_setup").restype = None; g("hip_any_destroy_setup").argtypes = [C.c_void_p]
         g("hip_any_transform_batch").restype = C.c_int
         g("hip_any_transform_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+        g("hip_zoom_new_setup").restype = C.c_void_p; g("hip_zoom_new_setup").argtypes = [C.c_int, C.c_int, C.c_double, C.c_double]
+        g("hip_zoom_destroy_setup").restype = None; g("hip_zoom_destroy_setup").argtypes = [C.c_void_p]
+        g("hip_zoom_transform_batch").restype = C.c_int
+        g("hip_zoom_transform_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
         getattr(L, f"validate_{pfx}_simd").restype = C.c_int
         getattr(L, f"validate_{pfx}_simd_ex").restype = C.c_int
         getattr(L, f"validate_{pfx}_simd_ex").argtypes = [C.c_void_p]
@@ -126,6 +130,10 @@ def lib():
     L.pffft_hip_any_chirp.restype = C.c_int; L.pffft_hip_any_chirp.argtypes = [C.c_void_p, C.c_void_p]
     L.pffft_hip_any_is_real.restype = C.c_int; L.pffft_hip_any_is_real.argtypes = [C.c_void_p]
     L.pffft_hip_any_bins.restype = C.c_int; L.pffft_hip_any_bins.argtypes = [C.c_void_p]
+    L.pffft_hip_zoom_conv_size.restype = C.c_int; L.pffft_hip_zoom_conv_size.argtypes = [C.c_void_p]
+    L.pffft_hip_zoom_route.restype = C.c_char_p; L.pffft_hip_zoom_route.argtypes = [C.c_void_p]
+    L.pffft_hip_zoom_table.restype = C.c_int
+    L.pffft_hip_zoom_table.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p]
     L.pffft_hip_kernel_name.restype = C.c_char_p; L.pffft_hip_kernel_name.argtypes = [C.c_void_p]
     L.pffft_hip_describe.restype = C.c_int; L.pffft_hip_describe.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.pffft_hip_route_occupancy.restype = C.c_int; L.pffft_hip_route_occupancy.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -257,6 +265,11 @@ def any_route(setup) -> str:
     """pffft_hip_any_route: "direct" / "fused" / "composed" for an any-length setup (AnySetup or AnyRealSetup) under the calling thread's
     selector.  Host arithmetic only."""
     return lib().pffft_hip_any_route(setup.handle).decode()
+
+
+def zoom_route(setup) -> str:
+    """pffft_hip_zoom_route: "fused" / "composed" for a ZoomSetup under the calling thread's selector.  Host arithmetic only."""
+    return lib().pffft_hip_zoom_route(setup.handle).decode()
 
 
 def _is_torch(x) -> bool:
@@ -686,6 +699,67 @@ class AnyRealSetup:
         fn = getattr(self._L, f"{self._pfx}_hip_any_transform_batch")
         _check(fn(self.handle, x.data_ptr(), out.data_ptr(), batch, direction, C.c_void_p(torch.cuda.current_stream().cuda_stream)),
                "hip_any_transform_batch")
+        return out
+
+
+class ZoomSetup:
+    """PFFFT_HIP_ZoomSetup / PFFFTD_HIP_ZoomSetup: K spectral lines from f0 in steps of df (cycles per sample) of rows of N complex samples
+    (include/pffft_hip.h).  Raises ValueError where pffft_hip_zoom_new_setup returns NULL.  Rows of N interleaved complex values in, rows of
+    K out, dense."""
+
+    def __init__(self, N: int, K: int, f0: float, df: float, dtype=np.float32):
+        self.N, self.K, self.f0, self.df, self.dtype = int(N), int(K), float(f0), float(df), np.dtype(dtype)
+        self._pfx = _pfx(dtype)
+        self._L = lib()
+        self.handle = getattr(self._L, f"{self._pfx}_hip_zoom_new_setup")(self.N, self.K, self.f0, self.df)
+        if not self.handle:
+            raise ValueError(f"pffft_hip_zoom_new_setup({N}, {K}, {f0}, {df}) returned NULL")
+
+    def close(self):
+        if getattr(self, "handle", None):
+            getattr(self._L, f"{self._pfx}_hip_zoom_destroy_setup")(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def conv_size(self) -> int:
+        """The convolution length M."""
+        return int(self._L.pffft_hip_zoom_conv_size(self.handle))
+
+    @property
+    def route(self) -> str:
+        return zoom_route(self)
+
+    def table(self, which: int, first: int = 0, count=None) -> np.ndarray:
+        """pffft_hip_zoom_table: `count` values from index `first` of the input table a (which = 0, N entries) or the output table c
+        (which = 1, max(N, K) entries) as a complex array of the setup's precision (host arithmetic only)."""
+        if count is None:
+            count = (self.N if which == 0 else max(self.N, self.K)) - first
+        out = np.empty(2 * max(int(count), 0), dtype=self.dtype)
+        rc = self._L.pffft_hip_zoom_table(self.handle, int(which), int(first), int(count), out.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"pffft_hip_zoom_table failed ({rc}): {self._L.pffft_hip_last_error().decode()}")
+        return out.view(np.complex128 if self.dtype == np.float64 else np.complex64)
+
+    def transform_batch(self, x, out=None, direction=FORWARD):
+        """x: contiguous CUDA tensor of the setup's dtype holding `batch` rows of 2N scalars; the result has `batch` rows of 2K scalars.
+        out must not overlap x."""
+        import torch
+        want = torch.float64 if self.dtype == np.float64 else torch.float32
+        assert x.is_cuda and x.dtype == want and x.is_contiguous() and x.numel() % (2 * self.N) == 0, \
+            "need a contiguous CUDA tensor of the setup dtype holding whole rows"
+        batch = x.numel() // (2 * self.N)
+        if out is None:
+            out = torch.empty((batch, 2 * self.K), dtype=want, device=x.device)
+        assert out.is_cuda and out.dtype == want and out.is_contiguous() and out.numel() == batch * 2 * self.K
+        fn = getattr(self._L, f"{self._pfx}_hip_zoom_transform_batch")
+        _check(fn(self.handle, x.data_ptr(), out.data_ptr(), batch, direction, C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+               "hip_zoom_transform_batch")
         return out
 
 

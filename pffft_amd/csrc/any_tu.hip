@@ -6,12 +6,8 @@
 #include <algorithm>
 #include <memory>
 
-#include "../../include/pffft_hip.h"
-#include "pf_host.h"
+#include "bluestein_host.h"
 #include "fft_any.h"
-
-struct PFFFT_Setup : pf::Setup {};
-struct PFFFTD_Setup : pf::Setup {};
 
 #define PF_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -19,7 +15,6 @@ namespace pf {
 
 constexpr uint32_t ANY_MAGIC = 0x50464159u;   // "PFAY"
 constexpr int ANY_MAX_N = 1 << 25;             // M <= 2^26, the library's largest setup
-constexpr size_t ANY_CAP_BYTES = (size_t)256 << 20;   // the scratch image of one composed launch sequence; longer batches go in chunks
 
 enum AnyRoute { ANY_DIRECT = 0, ANY_FUSED = 1, ANY_COMPOSED = 2 };
 
@@ -134,42 +129,10 @@ static cx<T> chirp_value(unsigned long long n, unsigned long long N) {
 }
 
 // the spectrum of one filter b (M values, double whatever the setup's type) in the inner setup's internal layout, into `dst`
+// (bluestein_host.h: shared with the zoom transforms)
 template <typename T>
 static int any_filter_spectrum(AnySetup* a, std::vector<cx<double>>& b, DevBuf& dst) {
-    const size_t M = (size_t)a->M;
-    int rc = dst.grow(M * sizeof(cx<T>));
-    if (rc) return rc;
-    if constexpr (sizeof(T) == 8) {
-        PF_CHECK(hipMemcpy(dst.get(), b.data(), M * sizeof(cx<double>), hipMemcpyHostToDevice));
-        if ((rc = pffftd_hip_transform_batch(static_cast<PFFFTD_Setup*>(a->inner), dst.as<double>(), dst.as<double>(), 1, PFFFT_FORWARD, 0, nullptr)))
-            return rc;
-    } else {
-        // float: the filter spectrum from the DOUBLE transform, rounded once (a float transform of b would add its error to every output);
-        // the permutation into the internal layout is exact
-        PFFFTD_Setup* sd = pffftd_new_setup((int)M, PFFFT_COMPLEX);
-        if (!sd) return bad("any: no double setup for the filter spectrum");
-        DevBuf tmp, tmpf;
-        rc = tmp.grow(M * sizeof(cx<double>));
-        if (!rc) rc = tmpf.grow(M * sizeof(cx<float>));
-        hipError_t e = hipSuccess;
-        if (!rc) e = hipMemcpy(tmp.get(), b.data(), M * sizeof(cx<double>), hipMemcpyHostToDevice);
-        if (!rc && e == hipSuccess) rc = pffftd_hip_transform_batch(sd, tmp.as<double>(), tmp.as<double>(), 1, PFFFT_FORWARD, 1, nullptr);
-        if (!rc && e == hipSuccess) e = hipStreamSynchronize(nullptr);
-        if (!rc && e == hipSuccess) e = hipMemcpy(b.data(), tmp.get(), M * sizeof(cx<double>), hipMemcpyDeviceToHost);
-        pffftd_destroy_setup(sd);
-        if (rc) return rc;
-        if (e != hipSuccess) return fail(e, "the filter spectrum of an any-length setup");
-        std::vector<cx<float>> bf(M);
-        for (size_t m = 0; m < M; ++m) bf[m] = mk<float>((float)b[m].x, (float)b[m].y);
-        PF_CHECK(hipMemcpy(tmpf.get(), bf.data(), M * sizeof(cx<float>), hipMemcpyHostToDevice));
-        rc = pffft_hip_zreorder_batch(static_cast<PFFFT_Setup*>(a->inner), tmpf.as<float>(), dst.as<float>(), 1, PFFFT_BACKWARD, nullptr);
-        e = hipStreamSynchronize(nullptr);   // (the permutation reads tmpf: it has finished before the temporaries go)
-        if (rc) return rc;
-        if (e != hipSuccess) return fail(e, "the filter spectrum of an any-length setup");
-        return 0;
-    }
-    PF_CHECK(hipStreamSynchronize(nullptr));
-    return 0;
+    return bluestein_filter_spectrum<T>(a->inner, (size_t)a->M, b, dst);
 }
 
 // b[m] = conj(w[|m|]) for -(neg - 1) <= m <= pos - 1 (negative m at M + m), zero elsewhere
@@ -222,202 +185,88 @@ static int any_ensure(AnySetup* a, hipStream_t st) {
     return 0;
 }
 
-// ------------------------------------------------------------------------------------------------ fused launch
-template <class C>
-static int any_fused_launch(AnySetup* a, const float* in, float* out, size_t batch, int cj, hipStream_t st) {
-    constexpr int HOLD = AnyHold<C>::value;
-    auto k = fft_conv_kernel<C, 0, AnyChirpIO<C, HOLD>>;
-    Setup* s = a->inner;
-    int rc = allow_big_lds(k, C::LDS_BYTES);
-    if (rc) return rc;
-    int per_cu = 0;
-    if ((rc = cached_occupancy(reinterpret_cast<const void*>(k), C::WG_THREADS, C::LDS_BYTES, &per_cu))) return rc;
-    // (the launch rule of the convolution kernel, conv_tu.hip)
-    const size_t groups = (batch + C::T_PER_WG - 1) / C::T_PER_WG;
-    size_t grid = (size_t)num_cus() * per_cu;
-    if (groups <= 4 * grid) grid = groups;
-    if (grid > groups) grid = groups;
-    unsigned* ctr = groups <= grid ? nullptr : take_counters(s, st);
-    const AnyChirpIO<C, HOLD> io{in, out, a->d_chirp.as<cx<float>>(), (unsigned)a->N, cj};
-    const cx<float>* tw = s->d_tw.as<cx<float>>();
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(C::WG_THREADS), C::LDS_BYTES, st, io, (const float*)a->d_H.as<float>(), (unsigned)batch,
-                       1.0f / (float)a->M, tw, tw, ctr);
-    PF_CHECK(hipGetLastError());
-    return 0;
-}
-
+// ------------------------------------------------------------------------------------------------ the two routes (bluestein_host.h)
 static int any_fused(AnySetup* a, const float* in, float* out, size_t batch, int cj, hipStream_t st) {
-    typedef ConvPick<float> P;
-    Setup* s = for_device(a->inner);
-    if (s != a->inner) return bad("any: this setup holds its tables on another device", hipErrorInvalidDevice);
-    int rc = ensure_device_any(s);
-    if (rc) return rc;
-    // (the kernel counts vectors in 32 bits: longer batches go out in slices on the same stream)
-    constexpr size_t SLICE = (size_t)3 << 30;
-    for (size_t b0 = 0; b0 < batch; b0 += SLICE) {
-        const size_t nb = std::min(batch - b0, SLICE);
-        const float* pi = in + b0 * 2 * (size_t)a->N;
-        float* po = out + b0 * 2 * (size_t)a->N;
-        switch (a->M) {
-            case 512: rc = any_fused_launch<P::C512>(a, pi, po, nb, cj, st); break;
-            case 1024: rc = any_fused_launch<P::C1024>(a, pi, po, nb, cj, st); break;
-            case 2048: rc = any_fused_launch<P::C2048>(a, pi, po, nb, cj, st); break;
-            case 4096: rc = any_fused_launch<P::C4096>(a, pi, po, nb, cj, st); break;
-            default: return bad("any: no fused kernel for this length");
-        }
-        if (rc) return rc;
-    }
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------------ composed
-static unsigned any_grid(size_t items) {
-    return (unsigned)std::max<size_t>(1, std::min<size_t>((items + 255) / 256, (size_t)num_cus() * 16));
+    return bluestein_fused(a->inner, a->M, batch, [&](auto tag, size_t b0, size_t nb) {
+        typedef typename decltype(tag)::type C;
+        const AnyChirpIO<C, AnyHold<C>::value> io{in + b0 * 2 * (size_t)a->N, out + b0 * 2 * (size_t)a->N, a->d_chirp.as<cx<float>>(),
+                                                  (unsigned)a->N, cj};
+        return bluestein_fused_launch<C>(a->inner, io, (const float*)a->d_H.as<float>(), nb, a->M, st);
+    });
 }
 
 template <typename T>
 static int any_composed(AnySetup* a, const T* in, T* out, size_t batch, int cj, hipStream_t st) {
     const size_t N = (size_t)a->N, M = (size_t)a->M;
-    const size_t chunk = std::max<size_t>(1, std::min(batch, ANY_CAP_BYTES / (M * sizeof(cx<T>))));
-    const size_t bytes = chunk * M * sizeof(cx<T>);
-    std::lock_guard<std::mutex> lk(a->pad.mu);
-    StreamScratch::Entry& sc = a->pad.acquire(st);
-    if (sc.buf[0].bytes() < bytes && stream_capturing(st))
-        return bad("the scratch image of this stream would have to grow during graph capture: run the call once on this stream before capturing",
-                   hipErrorStreamCaptureUnsupported);
-    int rc = a->pad.grow(sc, 0, bytes);
-    if (rc) return rc;
-    cx<T>* X = sc.buf[0].as<cx<T>>();
     const cx<T>* w = a->d_chirp.as<cx<T>>();
-    const T scaling = (T)1 / (T)M;
-    for (size_t v0 = 0; v0 < batch; v0 += chunk) {
-        const size_t cnt = std::min(batch - v0, chunk);
-        hipLaunchKernelGGL((any_pad_kernel<T>), dim3(any_grid(cnt * M)), dim3(256), 0, st, reinterpret_cast<const cx<T>*>(in) + v0 * N, X, w, cnt,
-                           N, M, cj);
-        PF_CHECK(hipGetLastError());
-        if constexpr (sizeof(T) == 8)
-            rc = pffftd_hip_convolve_batch(static_cast<PFFFTD_Setup*>(a->inner), (const double*)X, a->d_H.as<double>(), (double*)X, scaling, cnt, 0, 1, st);
-        else
-            rc = pffft_hip_convolve_batch(static_cast<PFFFT_Setup*>(a->inner), (const float*)X, a->d_H.as<float>(), (float*)X, scaling, cnt, 0, 1, st);
-        if (rc) return rc;
-        hipLaunchKernelGGL((any_crop_kernel<T>), dim3(any_grid(cnt * N)), dim3(256), 0, st, (const cx<T>*)X, reinterpret_cast<cx<T>*>(out) + v0 * N, w,
-                           cnt, N, M, cj);
-        PF_CHECK(hipGetLastError());
-    }
-    return 0;
+    return bluestein_composed<T>(
+        a->inner, a->pad, (const T*)a->d_H.as<T>(), M, batch, st,
+        [&](cx<T>* X, size_t v0, size_t cnt) {
+            hipLaunchKernelGGL((any_pad_kernel<T>), dim3(bluestein_grid(cnt * M)), dim3(256), 0, st, reinterpret_cast<const cx<T>*>(in) + v0 * N, X,
+                               w, cnt, N, M, cj);
+            PF_CHECK(hipGetLastError());
+            return 0;
+        },
+        [&](cx<T>* X, size_t v0, size_t cnt) {
+            hipLaunchKernelGGL((any_crop_kernel<T>), dim3(bluestein_grid(cnt * N)), dim3(256), 0, st, (const cx<T>*)X,
+                               reinterpret_cast<cx<T>*>(out) + v0 * N, w, cnt, N, M, cj);
+            PF_CHECK(hipGetLastError());
+            return 0;
+        });
 }
 
 // ------------------------------------------------------------------------------------------------ real setups
-template <class C, int DIRN>
-static int any_real_fused_launch(AnySetup* a, const float* in, float* out, size_t batch, hipStream_t st) {
-    constexpr int HOLD = AnyHold<C>::value;
-    typedef AnyRealIO<C, HOLD, DIRN> IO;
-    auto k = fft_conv_kernel<C, 0, IO>;
-    Setup* s = a->inner;
-    int rc = allow_big_lds(k, C::LDS_BYTES);
-    if (rc) return rc;
-    int per_cu = 0;
-    if ((rc = cached_occupancy(reinterpret_cast<const void*>(k), C::WG_THREADS, C::LDS_BYTES, &per_cu))) return rc;
-    // (the launch rule of the convolution kernel, conv_tu.hip)
-    const size_t groups = (batch + C::T_PER_WG - 1) / C::T_PER_WG;
-    size_t grid = (size_t)num_cus() * per_cu;
-    if (groups <= 4 * grid) grid = groups;
-    if (grid > groups) grid = groups;
-    unsigned* ctr = groups <= grid ? nullptr : take_counters(s, st);
-    const IO io{in, out, a->d_chirp.as<cx<float>>(), (unsigned)a->N, (unsigned)a->bins()};
-    const cx<float>* tw = s->d_tw.as<cx<float>>();
-    const DevBuf& Hs = DIRN == FWD ? a->d_H : a->d_Hr;
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(C::WG_THREADS), C::LDS_BYTES, st, io, (const float*)Hs.as<float>(), (unsigned)batch,
-                       1.0f / (float)a->M, tw, tw, ctr);
-    PF_CHECK(hipGetLastError());
-    return 0;
-}
-
 template <int DIRN>
 static int any_real_fused(AnySetup* a, const float* in, float* out, size_t batch, hipStream_t st) {
-    typedef ConvPick<float> P;
-    Setup* s = for_device(a->inner);
-    if (s != a->inner) return bad("any: this setup holds its tables on another device", hipErrorInvalidDevice);
-    int rc = ensure_device_any(s);
-    if (rc) return rc;
     const size_t rin = DIRN == FWD ? (size_t)a->N : 2 * (size_t)a->bins(), rout = DIRN == FWD ? 2 * (size_t)a->bins() : (size_t)a->N;
-    // (the kernel counts vectors in 32 bits: longer batches go out in slices on the same stream)
-    constexpr size_t SLICE = (size_t)3 << 30;
-    for (size_t b0 = 0; b0 < batch; b0 += SLICE) {
-        const size_t nb = std::min(batch - b0, SLICE);
-        const float* pi = in + b0 * rin;
-        float* po = out + b0 * rout;
-        switch (a->M) {
-            case 512: rc = any_real_fused_launch<P::C512, DIRN>(a, pi, po, nb, st); break;
-            case 1024: rc = any_real_fused_launch<P::C1024, DIRN>(a, pi, po, nb, st); break;
-            case 2048: rc = any_real_fused_launch<P::C2048, DIRN>(a, pi, po, nb, st); break;
-            case 4096: rc = any_real_fused_launch<P::C4096, DIRN>(a, pi, po, nb, st); break;
-            default: return bad("any: no fused kernel for this length");
-        }
-        if (rc) return rc;
-    }
-    return 0;
-}
-
-// the scratch image of one call on `st` (under a->pad.mu): at least `bytes`, never grown during a capture
-static int any_scratch(AnySetup* a, hipStream_t st, size_t bytes, void** p) {
-    StreamScratch::Entry& sc = a->pad.acquire(st);
-    if (sc.buf[0].bytes() < bytes && stream_capturing(st))
-        return bad("the scratch image of this stream would have to grow during graph capture: run the call once on this stream before capturing",
-                   hipErrorStreamCaptureUnsupported);
-    int rc = a->pad.grow(sc, 0, bytes);
-    *p = sc.buf[0].get();
-    return rc;
+    const DevBuf& Hs = DIRN == FWD ? a->d_H : a->d_Hr;
+    return bluestein_fused(a->inner, a->M, batch, [&](auto tag, size_t b0, size_t nb) {
+        typedef typename decltype(tag)::type C;
+        const AnyRealIO<C, AnyHold<C>::value, DIRN> io{in + b0 * rin, out + b0 * rout, a->d_chirp.as<cx<float>>(), (unsigned)a->N,
+                                                       (unsigned)a->bins()};
+        return bluestein_fused_launch<C>(a->inner, io, (const float*)Hs.as<float>(), nb, a->M, st);
+    });
 }
 
 template <typename T>
 static int any_real_composed(AnySetup* a, const T* in, T* out, size_t batch, int back, hipStream_t st) {
     const size_t N = (size_t)a->N, M = (size_t)a->M, H = (size_t)a->bins();
     const size_t rin = back ? 2 * H : N, rout = back ? N : 2 * H;
-    const size_t chunk = std::max<size_t>(1, std::min(batch, ANY_CAP_BYTES / (M * sizeof(cx<T>))));
-    std::lock_guard<std::mutex> lk(a->pad.mu);
-    void* p = nullptr;
-    int rc = any_scratch(a, st, chunk * M * sizeof(cx<T>), &p);
-    if (rc) return rc;
-    cx<T>* X = static_cast<cx<T>*>(p);
     const cx<T>* w = a->d_chirp.as<cx<T>>();
-    const T* Hs = (back ? a->d_Hr : a->d_H).template as<T>();
-    const T scaling = (T)1 / (T)M;
-    for (size_t v0 = 0; v0 < batch; v0 += chunk) {
-        const size_t cnt = std::min(batch - v0, chunk);
-        hipLaunchKernelGGL((any_real_pad_kernel<T>), dim3(any_grid(cnt * M)), dim3(256), 0, st, in + v0 * rin, X, w, cnt, N, H, M, back);
-        PF_CHECK(hipGetLastError());
-        if constexpr (sizeof(T) == 8)
-            rc = pffftd_hip_convolve_batch(static_cast<PFFFTD_Setup*>(a->inner), (const double*)X, Hs, (double*)X, scaling, cnt, 0, 1, st);
-        else
-            rc = pffft_hip_convolve_batch(static_cast<PFFFT_Setup*>(a->inner), (const float*)X, Hs, (float*)X, scaling, cnt, 0, 1, st);
-        if (rc) return rc;
-        hipLaunchKernelGGL((any_real_crop_kernel<T>), dim3(any_grid(cnt * (back ? N : H))), dim3(256), 0, st, (const cx<T>*)X, out + v0 * rout, w,
-                           cnt, N, H, M, back);
-        PF_CHECK(hipGetLastError());
-    }
-    return 0;
+    return bluestein_composed<T>(
+        a->inner, a->pad, (const T*)(back ? a->d_Hr : a->d_H).template as<T>(), M, batch, st,
+        [&](cx<T>* X, size_t v0, size_t cnt) {
+            hipLaunchKernelGGL((any_real_pad_kernel<T>), dim3(bluestein_grid(cnt * M)), dim3(256), 0, st, in + v0 * rin, X, w, cnt, N, H, M, back);
+            PF_CHECK(hipGetLastError());
+            return 0;
+        },
+        [&](cx<T>* X, size_t v0, size_t cnt) {
+            hipLaunchKernelGGL((any_real_crop_kernel<T>), dim3(bluestein_grid(cnt * (back ? N : H))), dim3(256), 0, st, (const cx<T>*)X,
+                               out + v0 * rout, w, cnt, N, H, M, back);
+            PF_CHECK(hipGetLastError());
+            return 0;
+        });
 }
 
 // direct route: the inner REAL setup's ordered transform, its canonical spectrum (DC, Nyquist, then bins 1 ... N/2 - 1) staged per stream
 template <typename T>
 static int any_real_direct(AnySetup* a, const T* in, T* out, size_t batch, int back, hipStream_t st) {
     const size_t N = (size_t)a->N, H = (size_t)a->bins();
-    const size_t chunk = std::max<size_t>(1, std::min(batch, ANY_CAP_BYTES / (N * sizeof(T))));
+    const size_t chunk = std::max<size_t>(1, std::min(batch, BLUESTEIN_CAP_BYTES / (N * sizeof(T))));
     std::lock_guard<std::mutex> lk(a->pad.mu);
     void* p = nullptr;
-    int rc = any_scratch(a, st, chunk * N * sizeof(T), &p);
+    int rc = bluestein_scratch(a->pad, st, chunk * N * sizeof(T), &p);
     if (rc) return rc;
     T* S = static_cast<T*>(p);
     for (size_t v0 = 0; v0 < batch; v0 += chunk) {
         const size_t cnt = std::min(batch - v0, chunk);
         if (!back) {
             if ((rc = transform_batch_any(a->inner, in + v0 * N, S, cnt, PFFFT_FORWARD, 1, st))) return rc;
-            hipLaunchKernelGGL((any_real_unpack_kernel<T>), dim3(any_grid(cnt * H)), dim3(256), 0, st, (const T*)S,
+            hipLaunchKernelGGL((any_real_unpack_kernel<T>), dim3(bluestein_grid(cnt * H)), dim3(256), 0, st, (const T*)S,
                                reinterpret_cast<cx<T>*>(out) + v0 * H, cnt, N);
             PF_CHECK(hipGetLastError());
         } else {
-            hipLaunchKernelGGL((any_real_pack_kernel<T>), dim3(any_grid(cnt * H)), dim3(256), 0, st, reinterpret_cast<const cx<T>*>(in) + v0 * H, S,
+            hipLaunchKernelGGL((any_real_pack_kernel<T>), dim3(bluestein_grid(cnt * H)), dim3(256), 0, st, reinterpret_cast<const cx<T>*>(in) + v0 * H, S,
                                cnt, N);
             PF_CHECK(hipGetLastError());
             if ((rc = transform_batch_any(a->inner, S, out + v0 * N, cnt, PFFFT_BACKWARD, 1, st))) return rc;

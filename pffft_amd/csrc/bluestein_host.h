@@ -1,0 +1,158 @@
+// Host code shared by the translation units that run Bluestein's algorithm on the library's own convolution (any_tu.hip, zoom_tu.hip):
+// the handle types of the inner setups, the spectrum of the fixed filter, the launch of fft_conv_kernel with a loader / store policy
+// (the fused route) and the pad -> convolve_batch -> crop sequence through a per-stream scratch image (the composed route).
+#pragma once
+#include <algorithm>
+#include <vector>
+
+#include "../../include/pffft_hip.h"
+#include "pf_host.h"
+#include "fft_conv.h"
+
+struct PFFFT_Setup : pf::Setup {};
+struct PFFFTD_Setup : pf::Setup {};
+
+namespace pf {
+
+// the spectrum of one filter b (M values, double whatever the setup's type; overwritten) in the internal layout of `inner` (a complex
+// PFFFT_Setup / PFFFTD_Setup of length M in the type T), into `dst`
+template <typename T>
+static int bluestein_filter_spectrum(Setup* inner, size_t M, std::vector<cx<double>>& b, DevBuf& dst) {
+    int rc = dst.grow(M * sizeof(cx<T>));
+    if (rc) return rc;
+    if constexpr (sizeof(T) == 8) {
+        PF_CHECK(hipMemcpy(dst.get(), b.data(), M * sizeof(cx<double>), hipMemcpyHostToDevice));
+        if ((rc = pffftd_hip_transform_batch(static_cast<PFFFTD_Setup*>(inner), dst.as<double>(), dst.as<double>(), 1, PFFFT_FORWARD, 0, nullptr)))
+            return rc;
+    } else {
+        // float: the filter spectrum from the DOUBLE transform, rounded once (a float transform of b would add its error to every output);
+        // the permutation into the internal layout is exact
+        PFFFTD_Setup* sd = pffftd_new_setup((int)M, PFFFT_COMPLEX);
+        if (!sd) {
+            g_last_error = "pffft_hip: no double setup for the filter spectrum";
+            return (int)hipErrorInvalidValue;
+        }
+        DevBuf tmp, tmpf;
+        rc = tmp.grow(M * sizeof(cx<double>));
+        if (!rc) rc = tmpf.grow(M * sizeof(cx<float>));
+        hipError_t e = hipSuccess;
+        if (!rc) e = hipMemcpy(tmp.get(), b.data(), M * sizeof(cx<double>), hipMemcpyHostToDevice);
+        if (!rc && e == hipSuccess) rc = pffftd_hip_transform_batch(sd, tmp.as<double>(), tmp.as<double>(), 1, PFFFT_FORWARD, 1, nullptr);
+        if (!rc && e == hipSuccess) e = hipStreamSynchronize(nullptr);
+        if (!rc && e == hipSuccess) e = hipMemcpy(b.data(), tmp.get(), M * sizeof(cx<double>), hipMemcpyDeviceToHost);
+        pffftd_destroy_setup(sd);
+        if (rc) return rc;
+        if (e != hipSuccess) return fail(e, "the filter spectrum of a Bluestein setup");
+        std::vector<cx<float>> bf(M);
+        for (size_t m = 0; m < M; ++m) bf[m] = mk<float>((float)b[m].x, (float)b[m].y);
+        PF_CHECK(hipMemcpy(tmpf.get(), bf.data(), M * sizeof(cx<float>), hipMemcpyHostToDevice));
+        rc = pffft_hip_zreorder_batch(static_cast<PFFFT_Setup*>(inner), tmpf.as<float>(), dst.as<float>(), 1, PFFFT_BACKWARD, nullptr);
+        e = hipStreamSynchronize(nullptr);   // (the permutation reads tmpf: it has finished before the temporaries go)
+        if (rc) return rc;
+        if (e != hipSuccess) return fail(e, "the filter spectrum of a Bluestein setup");
+        return 0;
+    }
+    PF_CHECK(hipStreamSynchronize(nullptr));
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ the fused route
+template <class C> struct CfgTag { typedef C type; };
+
+// fft_conv_kernel<C, 0, IO> on `batch` rows under the launch rule of the convolution kernel (conv_tu.hip); `s` is the resolved inner
+// setup of length M, H the filter spectrum in its internal layout
+template <class C, class IO>
+static int bluestein_fused_launch(Setup* s, const IO& io, const float* H, size_t batch, int M, hipStream_t st) {
+    auto k = fft_conv_kernel<C, 0, IO>;
+    int rc = allow_big_lds(k, C::LDS_BYTES);
+    if (rc) return rc;
+    int per_cu = 0;
+    if ((rc = cached_occupancy(reinterpret_cast<const void*>(k), C::WG_THREADS, C::LDS_BYTES, &per_cu))) return rc;
+    const size_t groups = (batch + C::T_PER_WG - 1) / C::T_PER_WG;
+    size_t grid = (size_t)num_cus() * per_cu;
+    if (groups <= 4 * grid) grid = groups;
+    if (grid > groups) grid = groups;
+    unsigned* ctr = groups <= grid ? nullptr : take_counters(s, st);
+    const cx<float>* tw = s->d_tw.as<cx<float>>();
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(C::WG_THREADS), C::LDS_BYTES, st, io, H, (unsigned)batch, 1.0f / (float)M, tw, tw, ctr);
+    PF_CHECK(hipGetLastError());
+    return 0;
+}
+
+// The fused route of a float setup whose convolution length M is one of the fused lengths: the inner setup must hold its tables on the
+// calling thread's device; the batch goes out in slices on the same stream (the kernel counts rows in 32 bits).  launch(CfgTag<C>(),
+// first row, rows) forms the policy object of that slice and calls bluestein_fused_launch<C>.
+template <class F>
+static int bluestein_fused(Setup* inner, int M, size_t batch, F&& launch) {
+    typedef ConvPick<float> P;
+    Setup* s = for_device(inner);
+    if (s != inner) {
+        g_last_error = "pffft_hip: this setup holds its tables on another device";
+        return (int)hipErrorInvalidDevice;
+    }
+    int rc = ensure_device_any(s);
+    if (rc) return rc;
+    constexpr size_t SLICE = (size_t)3 << 30;
+    for (size_t b0 = 0; b0 < batch; b0 += SLICE) {
+        const size_t nb = std::min(batch - b0, SLICE);
+        switch (M) {
+            case 512: rc = launch(CfgTag<P::C512>(), b0, nb); break;
+            case 1024: rc = launch(CfgTag<P::C1024>(), b0, nb); break;
+            case 2048: rc = launch(CfgTag<P::C2048>(), b0, nb); break;
+            case 4096: rc = launch(CfgTag<P::C4096>(), b0, nb); break;
+            default:
+                g_last_error = "pffft_hip: no fused kernel for this convolution length";
+                return (int)hipErrorInvalidValue;
+        }
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ the composed route
+constexpr size_t BLUESTEIN_CAP_BYTES = (size_t)256 << 20;   // the scratch image of one launch sequence; longer batches go in chunks
+
+// the scratch image of one call on `st` (under pad.mu): at least `bytes`, never grown during a capture
+static int bluestein_scratch(StreamScratch& pad, hipStream_t st, size_t bytes, void** p) {
+    StreamScratch::Entry& sc = pad.acquire(st);
+    if (sc.buf[0].bytes() < bytes && stream_capturing(st)) {
+        g_last_error = "pffft_hip: the scratch image of this stream would have to grow during graph capture: run the call once on this stream "
+                       "before capturing";
+        return (int)hipErrorStreamCaptureUnsupported;
+    }
+    int rc = pad.grow(sc, 0, bytes);
+    *p = sc.buf[0].get();
+    return rc;
+}
+
+// pad kernel -> pffft[d]_hip_convolve_batch on `inner` (length M, one broadcast filter spectrum H, scaled by 1 / M) -> crop kernel, in
+// chunks of at most 256 MiB of scratch (one row where a row is longer).  pad_k(X, first row, rows) and crop_k(X, first row, rows) launch
+// the two ends on `st` and return 0 or an error.
+template <typename T, class PadK, class CropK>
+static int bluestein_composed(Setup* inner, StreamScratch& pad, const T* H, size_t M, size_t batch, hipStream_t st, PadK&& pad_k, CropK&& crop_k) {
+    const size_t chunk = std::max<size_t>(1, std::min(batch, BLUESTEIN_CAP_BYTES / (M * sizeof(cx<T>))));
+    std::lock_guard<std::mutex> lk(pad.mu);
+    void* p = nullptr;
+    int rc = bluestein_scratch(pad, st, chunk * M * sizeof(cx<T>), &p);
+    if (rc) return rc;
+    cx<T>* X = static_cast<cx<T>*>(p);
+    const T scaling = (T)1 / (T)M;
+    for (size_t v0 = 0; v0 < batch; v0 += chunk) {
+        const size_t cnt = std::min(batch - v0, chunk);
+        if ((rc = pad_k(X, v0, cnt))) return rc;
+        if constexpr (sizeof(T) == 8)
+            rc = pffftd_hip_convolve_batch(static_cast<PFFFTD_Setup*>(inner), (const double*)X, H, (double*)X, scaling, cnt, 0, 1, st);
+        else
+            rc = pffft_hip_convolve_batch(static_cast<PFFFT_Setup*>(inner), (const float*)X, H, (float*)X, scaling, cnt, 0, 1, st);
+        if (rc) return rc;
+        if ((rc = crop_k(X, v0, cnt))) return rc;
+    }
+    return 0;
+}
+
+// grid of the grid-stride pad / crop kernels (256 threads)
+static unsigned bluestein_grid(size_t items) {
+    return (unsigned)std::max<size_t>(1, std::min<size_t>((items + 255) / 256, (size_t)num_cus() * 16));
+}
+
+}  // namespace pf

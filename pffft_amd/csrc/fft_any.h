@@ -17,7 +17,7 @@ namespace pf {
 // A thread loads and stores the SAME sample indices (R0 == RL in every convolution configuration), so one chirp value per point serves
 // both ends.  HOLD = 1 keeps those E values in registers across the persistent loop; HOLD = 0 reads them at the point of use (the
 // table is a few KiB: L1 / L2 hits) where 16 points per thread and the filter spectrum leave no room.  The table holds n (= M) entries,
-// zero from N on.  Chirp-z / zoom variants would differ in the two tables only.
+// zero from N on.  The zoom transforms (fft_zoom.h) are this policy with rows of N in and K out and one table per end.
 template <class C, int HOLD>
 struct AnyChirpIO {
     typedef typename C::real_t T;
