@@ -479,6 +479,52 @@ int pffft_hip_zoom_conv_size(const void *setup);
 const char *pffft_hip_zoom_route(const void *setup);
 int pffft_hip_zoom_table(const void *setup, int which, size_t first, size_t count, void *host_out);
 
+/* COSINE AND SINE transforms of types II and III (scipy.fft.dct / dst with type = 2 / 3; FFTPACK's cosqb / cosqf / sinqb / sinqf are
+ * 2 x DCT-II, DCT-III, 2 x DST-II, DST-III): rows of N reals in, rows of N reals out, dense.  norm = NONE (scipy's norm=None):
+ *     DCT-II   X[k] = 2 sum_n x[n] cos(pi k (2n+1) / 2N)
+ *     DCT-III  y[n] = X[0] + 2 sum_{k>=1} X[k] cos(pi k (2n+1) / 2N)                          DCT-III(DCT-II(x)) = 2N x
+ *     DST-II   X[k] = 2 sum_n x[n] sin(pi (k+1) (2n+1) / 2N)                                  = DCT-II((-1)^n x)[N-1-k]
+ *     DST-III  y[n] = (-1)^n X[N-1] + 2 sum_{k<N-1} X[k] sin(pi (k+1) (2n+1) / 2N)            = (-1)^n DCT-III(reverse X)[n]
+ * norm = ORTHO is scipy's norm="ortho": the transforms are orthogonal, II and III exact inverses.  Legal N: every N pffft_new_setup(N,
+ * PFFFT_REAL) takes (a multiple of 32, 2^a 3^b 5^c, up to 2^26); NULL for any other N, a kind or a norm out of range.  Creating a setup
+ * touches no device; the handle owns a real setup of N, whose per-device behaviour carries over (one handle may serve several devices).
+ * Makhoul's algorithm, ONE real transform of the same N (n = N/2, w_k = exp(-j pi k / 2N)):
+ *     II   v[m] = x[2m], v[N-1-m] = x[2m+1];  V = forward transform of v;  z_k = V[k] t_k;  X[k] = Re z_k, X[N-k] = -Im z_k (0 < k < n),
+ *          X[0] = V[0] Re t_0, X[n] = V[n] Re t_n
+ *     III  V[k] = (X[k] - j X[N-k]) t_k (0 < k < n), V[0] = X[0] Re t_0, V[n] = 2 X[n] Re t_n;  v = unscaled backward transform of V;
+ *          y[2m] = v[m], y[2m+1] = v[N-1-m]
+ * with ONE folded table t_k, k = 0 ... n: t_k = 2 s_k w_k (II) / s'_k conj(w_k) (III); NONE: s = s' = 1; ORTHO: s_0 = 1/sqrt(4N),
+ * s'_0 = 1/sqrt(N), s_k = s'_k = 1/sqrt(2N).  Each t_k is evaluated in long double and rounded once; every route forms the product with
+ * the same operations (one product and one fused multiply-add per component), so the routes agree bit for bit.
+ * in / out are device pointers aligned to 16 bytes.  out == in IS LEGAL on every route (any other overlap is refused).  The call is
+ * asynchronous on `stream`; 0, else a hipError_t with its text in pffft_hip_last_error().  batch == 0 returns 0.
+ * Routes (pffft_hip_dct_route names the one a call takes under the calling thread's selector):
+ *   "fused"     float, N = 1024 / 2048 / 4096: ONE kernel - the register-tiled real transform between an input and an output round trip
+ *               through its own LDS image: 4N bytes read and 4N written per row.  Which (size, kind) cells run it by default is a measured
+ *               table - all twelve: on an MI355X it takes 0.30 ... 0.38 of the composed route's time;
+ *               pffft_hip_set_variant(139) runs it wherever it is legal, 138 never.
+ *   "composed"  every setup: a permutation / table kernel into a per-stream scratch image of batch x N, pffft[d]_hip_transform_batch in
+ *               the canonical layout in place there, a table / permutation kernel into out.  The scratch holds at most 256 MiB (longer
+ *               batches go through it in chunks on the stream); a call that would have to grow it - or build the table of a first call -
+ *               on a capturing stream returns hipErrorStreamCaptureUnsupported before any launch: run the call once before capturing.
+ * Types I and IV, strided rows and lengths pffft_new_setup refuses are not offered. */
+typedef enum { PFFFT_HIP_DCT2, PFFFT_HIP_DCT3, PFFFT_HIP_DST2, PFFFT_HIP_DST3 } pffft_hip_dct_kind_t;
+typedef enum { PFFFT_HIP_DCT_NORM_NONE, PFFFT_HIP_DCT_NORM_ORTHO } pffft_hip_dct_norm_t;
+typedef struct PFFFT_HIP_DctSetup PFFFT_HIP_DctSetup;
+typedef struct PFFFTD_HIP_DctSetup PFFFTD_HIP_DctSetup;
+PFFFT_HIP_DctSetup *pffft_hip_dct_new_setup(int N, pffft_hip_dct_kind_t kind, pffft_hip_dct_norm_t norm);
+PFFFTD_HIP_DctSetup *pffftd_hip_dct_new_setup(int N, pffft_hip_dct_kind_t kind, pffft_hip_dct_norm_t norm);
+void pffft_hip_dct_destroy_setup(PFFFT_HIP_DctSetup *);     /* NULL-safe */
+void pffftd_hip_dct_destroy_setup(PFFFTD_HIP_DctSetup *);
+int pffft_hip_dct_transform_batch(PFFFT_HIP_DctSetup *, const float *in, float *out, size_t batch, void *stream);
+int pffftd_hip_dct_transform_batch(PFFFTD_HIP_DctSetup *, const double *in, double *out, size_t batch, void *stream);
+/* Host arithmetic only, handles of both precisions.  pffft_hip_dct_route: "fused" / "composed" under the calling thread's selector; ""
+ * for an invalid handle.  pffft_hip_dct_table: `count` values t_k from k = `first` (k <= N/2) as interleaved (re, im) pairs in the
+ * setup's type into host_out - the values of the device's table.  0; non-zero for an invalid handle, a range beyond N/2 + 1 values or a
+ * NULL host_out. */
+const char *pffft_hip_dct_route(const void *setup);
+int pffft_hip_dct_table(const void *setup, size_t first, size_t count, void *host_out);
+
 /* Overlap-save FIR on device-resident signal/output (same block schedule as pffastconv_apply,
  * src/pffastconv.c:204-261): returns the number of output samples written, or -1 on error. */
 int pffastconv_hip_apply_device(PFFASTCONV_Setup *, const float *d_input, int inputLen, float *d_output,

@@ -101,6 +101,10 @@ def lib():
         g("hip_zoom_destroy_setup").restype = None; g("hip_zoom_destroy_setup").argtypes = [C.c_void_p]
         g("hip_zoom_transform_batch").restype = C.c_int
         g("hip_zoom_transform_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+        g("hip_dct_new_setup").restype = C.c_void_p; g("hip_dct_new_setup").argtypes = [C.c_int, C.c_int, C.c_int]
+        g("hip_dct_destroy_setup").restype = None; g("hip_dct_destroy_setup").argtypes = [C.c_void_p]
+        g("hip_dct_transform_batch").restype = C.c_int
+        g("hip_dct_transform_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         getattr(L, f"validate_{pfx}_simd").restype = C.c_int
         getattr(L, f"validate_{pfx}_simd_ex").restype = C.c_int
         getattr(L, f"validate_{pfx}_simd_ex").argtypes = [C.c_void_p]
@@ -134,6 +138,9 @@ def lib():
     L.pffft_hip_zoom_route.restype = C.c_char_p; L.pffft_hip_zoom_route.argtypes = [C.c_void_p]
     L.pffft_hip_zoom_table.restype = C.c_int
     L.pffft_hip_zoom_table.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p]
+    L.pffft_hip_dct_route.restype = C.c_char_p; L.pffft_hip_dct_route.argtypes = [C.c_void_p]
+    L.pffft_hip_dct_table.restype = C.c_int
+    L.pffft_hip_dct_table.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
     L.pffft_hip_kernel_name.restype = C.c_char_p; L.pffft_hip_kernel_name.argtypes = [C.c_void_p]
     L.pffft_hip_describe.restype = C.c_int; L.pffft_hip_describe.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.pffft_hip_route_occupancy.restype = C.c_int; L.pffft_hip_route_occupancy.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -760,6 +767,68 @@ class ZoomSetup:
         fn = getattr(self._L, f"{self._pfx}_hip_zoom_transform_batch")
         _check(fn(self.handle, x.data_ptr(), out.data_ptr(), batch, direction, C.c_void_p(torch.cuda.current_stream().cuda_stream)),
                "hip_zoom_transform_batch")
+        return out
+
+
+DCT_KINDS = {"dct2": 0, "dct3": 1, "dst2": 2, "dst3": 3}      # pffft_hip_dct_kind_t
+DCT_NORMS = {None: 0, "none": 0, "ortho": 1}                  # pffft_hip_dct_norm_t
+
+
+class DctSetup:
+    """PFFFT_HIP_DctSetup / PFFFTD_HIP_DctSetup: cosine / sine transforms of type II / III of rows of N reals (include/pffft_hip.h;
+    scipy.fft.dct / dst with type = 2 / 3).  kind: "dct2" / "dct3" / "dst2" / "dst3" (or the enum value), norm: None / "ortho".  Raises
+    ValueError where pffft_hip_dct_new_setup returns NULL."""
+
+    def __init__(self, N: int, kind, norm=None, dtype=np.float32):
+        self.N, self.dtype = int(N), np.dtype(dtype)
+        self.kind = DCT_KINDS[kind] if kind in DCT_KINDS else int(kind)
+        self.norm = DCT_NORMS[norm] if norm in DCT_NORMS else int(norm)
+        self._pfx = _pfx(dtype)
+        self._L = lib()
+        self.handle = getattr(self._L, f"{self._pfx}_hip_dct_new_setup")(self.N, self.kind, self.norm)
+        if not self.handle:
+            raise ValueError(f"pffft_hip_dct_new_setup({N}, {kind}, {norm}) returned NULL")
+
+    def close(self):
+        if getattr(self, "handle", None):
+            getattr(self._L, f"{self._pfx}_hip_dct_destroy_setup")(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def route(self) -> str:
+        """pffft_hip_dct_route: "fused" / "composed" under the calling thread's selector.  Host arithmetic only."""
+        return self._L.pffft_hip_dct_route(self.handle).decode()
+
+    def table(self, first: int = 0, count=None) -> np.ndarray:
+        """pffft_hip_dct_table: the folded table t_k, k = first ... (N/2 + 1 values in all), as a complex array of the setup's precision
+        (host arithmetic only)."""
+        if count is None:
+            count = self.N // 2 + 1 - first
+        out = np.empty(2 * max(int(count), 0), dtype=self.dtype)
+        rc = self._L.pffft_hip_dct_table(self.handle, int(first), int(count), out.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"pffft_hip_dct_table failed ({rc}): {self._L.pffft_hip_last_error().decode()}")
+        return out.view(np.complex128 if self.dtype == np.float64 else np.complex64)
+
+    def transform_batch(self, x, out=None):
+        """x: contiguous CUDA tensor of the setup's dtype holding `batch` rows of N scalars; the result has the same shape.  out may be x."""
+        import torch
+        want = torch.float64 if self.dtype == np.float64 else torch.float32
+        assert x.is_cuda and x.dtype == want and x.is_contiguous() and x.numel() % self.N == 0, \
+            "need a contiguous CUDA tensor of the setup dtype holding whole rows"
+        batch = x.numel() // self.N
+        if out is None:
+            out = torch.empty((batch, self.N), dtype=want, device=x.device)
+        assert out.is_cuda and out.dtype == want and out.is_contiguous() and out.numel() == batch * self.N
+        fn = getattr(self._L, f"{self._pfx}_hip_dct_transform_batch")
+        _check(fn(self.handle, x.data_ptr(), out.data_ptr(), batch, C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+               "hip_dct_transform_batch")
         return out
 
 

@@ -90,6 +90,18 @@ template <typename V> __device__ __forceinline__ V cmulc(V a, V w) {
 template <int DIR, typename V> __device__ __forceinline__ V twmul(V a, V w) {
     return DIR == FWD ? cmul(a, w) : cmulc(a, w);
 }
+// The table product of the cosine / sine transforms (fft_dct.h), the ONE place it is written: every route - the composed kernels in
+// either precision and the fused kernel - rounds it the same way.  Regular bins: a t, each component one product and one fused
+// multiply-add (the components do not share a rounding, so a caller may use one of them alone).  `edge`: the bin that packs the two
+// real ends, a = (value at k = 0, value at k = N/2), t = (t_0.x, t_{N/2}.x): two real products; the type-III spectrum doubles the
+// second one (V[N/2] = X[N/2] (t.x + t.y) with t.x = t.y there; the doubling is exact).
+template <bool TYPE3, typename V> __device__ __forceinline__ V dct_mul(V a, V t, bool edge) {
+    typedef sc<V> T;
+    const T yy = a.y * t.y;
+    const V z = mk<T>(fma_(a.x, t.x, -yy), fma_(a.x, t.y, a.y * t.x));
+    const V e = mk<T>(a.x * t.x, TYPE3 ? (T)2 * yy : yy);
+    return mk<T>(edge ? e.x : z.x, edge ? e.y : z.y);
+}
 // the same for a COMPILE-TIME constant w (the fixed twiddles inside radix 16 / 32 / 9 / 25 / 27): the scalar form lets the
 // compiler keep the constants in scalar registers / literals; an asm operand would pin each one in a VGPR pair.  Same
 // operations as cmul / cmulc.

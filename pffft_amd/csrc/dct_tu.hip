@@ -1,0 +1,263 @@
+// libpffft_hip.so, translation unit of the cosine / sine transforms (include/pffft_hip.h: pffft[d]_hip_dct_*): types II and III by
+// Makhoul's algorithm on ONE real transform of the same length.  The handle owns an ordinary real setup of N and the folded table t_k;
+// the fused kernel's instantiations and launch, and the composed route through a per-stream scratch image.  Kernels: fft_dct.h.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <memory>
+
+#include "../../include/pffft_hip.h"
+#include "pf_host.h"
+#include "fft_dct.h"
+
+struct PFFFT_Setup : pf::Setup {};
+struct PFFFTD_Setup : pf::Setup {};
+
+#define PF_EXPORT extern "C" __attribute__((visibility("default")))
+
+namespace pf {
+
+constexpr uint32_t DCT_MAGIC = 0x50464443u;   // "PFDC"
+constexpr size_t DCT_CAP_BYTES = (size_t)256 << 20;   // the scratch image of one launch sequence; longer batches go in chunks
+
+struct DctSetup {
+    uint32_t magic = DCT_MAGIC;
+    int N = 0, kind = 0, norm = 0, is_double = 0;
+    Setup* inner = nullptr;        // a real PFFFT_Setup / PFFFTD_Setup of N, owned
+    std::mutex mu;                 // guards the lazy tables
+    // t_k, k = 0 ... N/2, per object that holds the inner setup's device state (for_device): one table per device the setup is used on
+    std::map<const Setup*, DevBuf> d_tab;
+    StreamScratch scratch;         // batch x N image of the composed route: one per stream, scratch.mu held while a call enqueues
+};
+
+static int bad(const char* what, hipError_t e = hipErrorInvalidValue) {
+    g_last_error = std::string("pffft_hip: ") + what;
+    return (int)e;
+}
+
+static DctSetup* dct_checked(const void* p) {
+    const DctSetup* z = static_cast<const DctSetup*>(p);
+    return z && z->magic == DCT_MAGIC ? const_cast<DctSetup*>(z) : nullptr;
+}
+
+// ------------------------------------------------------------------------------------------------ the folded table
+// t_k = 2 s_k w_k (type II) / s'_k conj(w_k) (type III), w_k = exp(-j pi k / 2N) = W_{4N}^k; norm none: s = s' = 1; ortho:
+// s_0 = 1/sqrt(4N), s'_0 = 1/sqrt(N), s_k = s'_k = 1/sqrt(2N).  The sine forms run the cosine form on a reversed index, so their end
+// factors sit at the same k of the table.  Scale and root are multiplied in long double and rounded once (pf_devmem.h).
+template <typename T>
+static cx<T> dct_table_value(const DctSetup* z, size_t k) {
+    const bool t3 = dct_type3(z->kind);
+    long double s = 1.0L;
+    if (z->norm == PFFFT_HIP_DCT_NORM_ORTHO)
+        s = 1.0L / sqrtl(k == 0 ? (t3 ? (long double)z->N : 4.0L * (long double)z->N) : 2.0L * (long double)z->N);
+    return scaled_unit_root<T>((long long)k, 4ll * z->N, t3 ? s : 2.0L * s, t3);
+}
+
+template <typename T>
+static int dct_table(DctSetup* z, const Setup* s, hipStream_t st, const cx<T>** tab) {
+    std::lock_guard<std::mutex> lk(z->mu);
+    auto it = z->d_tab.find(s);
+    if (it == z->d_tab.end()) {
+        if (stream_capturing(st))
+            return bad("dct: the table of this setup would have to be built during graph capture: run the call once before capturing",
+                       hipErrorStreamCaptureUnsupported);
+        std::vector<cx<T>> h((size_t)z->N / 2 + 1);
+        for (size_t k = 0; k < h.size(); ++k) h[k] = dct_table_value<T>(z, k);
+        DevBuf d;
+        if (int rc = upload_table(d, h)) return rc;
+        it = z->d_tab.emplace(s, std::move(d)).first;
+    }
+    *tab = it->second.as<cx<T>>();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ plan
+typedef void (*DctFn)(const float*, float*, unsigned, const cx<float>*, const cx<float>*, const cx<float>*, unsigned*);
+struct DctSel { DctFn fn = nullptr; size_t lds = 0; int wg = 0, t_per_wg = 0; };
+
+template <class C>
+static DctSel dct_sel(int kind) {
+    DctSel e;
+    e.wg = C::WG_THREADS; e.t_per_wg = C::T_PER_WG; e.lds = dct_lds_bytes<C>();
+    e.fn = kind == DCT_2 ? fft_dct_kernel<C, DCT_2> : kind == DCT_3 ? fft_dct_kernel<C, DCT_3>
+           : kind == DST_2 ? fft_dct_kernel<C, DST_2> : fft_dct_kernel<C, DST_3>;
+    return e;
+}
+
+// The configuration the fused kernel runs on must be the one transform_batch runs on for the same direction in the canonical layout - the
+// results are equal bit for bit only then -, so it is read from the inner setup's stored route: real float on TiledPick C512 / C1024 /
+// C2048 (N = 1024 / 2048 / 4096), forward for type II, backward for type III.  Everything else has no fused kernel.
+static bool dct_fusable(const DctSetup* z, DctSel* e) {
+    const Setup* s = z->inner;
+    if (s->is_double || s->kernel != K_TILED) return false;
+    const Route& r = s->route[dct_type3(z->kind) ? PFFFT_BACKWARD : PFFFT_FORWARD][1];
+    if (r.fam != FAM_TILED) return false;
+    const std::string cfg = r.tiled.cfg;
+    if (s->n == 512 && cfg == "TiledPick::C512") { if (e) *e = dct_sel<TiledPick<float>::C512>(z->kind); return true; }
+    if (s->n == 1024 && cfg == "TiledPick::C1024") { if (e) *e = dct_sel<TiledPick<float>::C1024>(z->kind); return true; }
+    if (s->n == 2048 && cfg == "TiledPick::C2048") { if (e) *e = dct_sel<TiledPick<float>::C2048>(z->kind); return true; }
+    return false;
+}
+
+// (size, kind) cells where the fused kernel is the default: a cell is in it where tools/dct_bench.py holds the fused kernel faster than
+// selector 138 on the device by more than the spread of identical runs - all twelve (0.30-0.38 of the composed time against a spread
+// below 2.2 %).  A cell that loses on a later measurement returns false here and stays reachable through AB_DCT_FUSED.
+static bool dct_fused_default(int N, int kind) {
+    (void)N; (void)kind;
+    return true;
+}
+
+static bool dct_fused_now(const DctSetup* z, const AbSel& sel) {
+    if (sel.is(AB_DCT_COMPOSED) || !dct_fusable(z, nullptr)) return false;
+    return sel.is(AB_DCT_FUSED) || dct_fused_default(z->N, z->kind);
+}
+
+static DctSetup* dct_new_setup(int N, int kind, int norm, int is_double) {
+    if (N < 1 || kind < PFFFT_HIP_DCT2 || kind > PFFFT_HIP_DST3 || (norm != PFFFT_HIP_DCT_NORM_NONE && norm != PFFFT_HIP_DCT_NORM_ORTHO))
+        return nullptr;
+    std::unique_ptr<DctSetup> z(new DctSetup);
+    z->N = N; z->kind = kind; z->norm = norm; z->is_double = is_double;
+    z->inner = is_double ? static_cast<Setup*>(pffftd_new_setup(N, PFFFT_REAL)) : static_cast<Setup*>(pffft_new_setup(N, PFFFT_REAL));
+    if (!z->inner) return nullptr;
+    return z.release();
+}
+
+static void dct_destroy_setup(DctSetup* z) {
+    if (!z || z->magic != DCT_MAGIC) return;
+    z->magic = 0;
+    if (z->inner) {
+        if (z->is_double) pffftd_destroy_setup(static_cast<PFFFTD_Setup*>(z->inner));
+        else pffft_destroy_setup(static_cast<PFFFT_Setup*>(z->inner));
+    }
+    delete z;
+}
+
+// ------------------------------------------------------------------------------------------------ the two routes
+static int dct_fused(Setup* s, const DctSel& e, const float* in, float* out, size_t batch, const cx<float>* tab, hipStream_t st) {
+    int rc = allow_big_lds(e.fn, e.lds);
+    if (rc) return rc;
+    int per_cu = 0;
+    if ((rc = cached_occupancy(reinterpret_cast<const void*>(e.fn), e.wg, e.lds, &per_cu))) return rc;
+    const size_t N = (size_t)s->N;
+    constexpr size_t SLICE = (size_t)3 << 30;   // (the kernel counts rows in 32 bits: longer batches go out in slices on the stream)
+    for (size_t b0 = 0; b0 < batch; b0 += SLICE) {
+        const size_t nb = std::min(batch - b0, SLICE);
+        const size_t groups = (nb + e.t_per_wg - 1) / e.t_per_wg;
+        size_t grid = (size_t)num_cus() * per_cu;
+        const int oneshot = env().oneshot;    // the launch rule of launch_tiled
+        if (oneshot > 0 && groups <= (size_t)oneshot * grid) grid = groups;
+        if (grid > groups) grid = groups;
+        unsigned* ctr = groups <= grid ? nullptr : take_counters(s, st);
+        hipLaunchKernelGGL(e.fn, dim3((unsigned)grid), dim3(e.wg), e.lds, st, in + b0 * N, out + b0 * N, (unsigned)nb, tab,
+                           s->d_tw.as<cx<float>>(), s->d_twr.as<cx<float>>(), ctr);
+        PF_CHECK(hipGetLastError());
+    }
+    return 0;
+}
+
+static unsigned dct_grid(size_t items) {
+    return (unsigned)std::max<size_t>(1, std::min<size_t>((items + 255) / 256, (size_t)num_cus() * 16));
+}
+
+template <typename T, int KIND>
+static int dct_composed_kind(DctSetup* z, Setup* s, const T* in, T* out, size_t batch, const cx<T>* tab, hipStream_t st) {
+    constexpr bool III = dct_type3(KIND);
+    const size_t N = (size_t)z->N;
+    const size_t chunk = std::max<size_t>(1, std::min(batch, DCT_CAP_BYTES / (N * sizeof(T))));
+    std::lock_guard<std::mutex> lk(z->scratch.mu);
+    StreamScratch::Entry& sc = z->scratch.acquire(st);
+    if (sc.buf[0].bytes() < chunk * N * sizeof(T) && stream_capturing(st))
+        return bad("dct: the scratch image of this stream would have to grow during graph capture: run the call once on this stream before "
+                   "capturing", hipErrorStreamCaptureUnsupported);
+    int rc = z->scratch.grow(sc, 0, chunk * N * sizeof(T));
+    if (rc) return rc;
+    T* X = sc.buf[0].as<T>();
+    for (size_t v0 = 0; v0 < batch; v0 += chunk) {
+        const size_t cnt = std::min(batch - v0, chunk);
+        hipLaunchKernelGGL((dct_pre_kernel<T, KIND>), dim3(dct_grid(cnt * (III ? N / 8 : N / 4))), dim3(256), 0, st, in + v0 * N, X, tab, cnt,
+                           (unsigned)N);
+        PF_CHECK(hipGetLastError());
+        if ((rc = transform_batch_any(s, X, X, cnt, III ? PFFFT_BACKWARD : PFFFT_FORWARD, 1, st))) return rc;
+        hipLaunchKernelGGL((dct_post_kernel<T, KIND>), dim3(dct_grid(cnt * (III ? N / 4 : N / 8))), dim3(256), 0, st, (const T*)X, out + v0 * N,
+                           tab, cnt, (unsigned)N);
+        PF_CHECK(hipGetLastError());
+    }
+    return 0;
+}
+
+template <typename T>
+static int dct_composed(DctSetup* z, Setup* s, const T* in, T* out, size_t batch, const cx<T>* tab, hipStream_t st) {
+    switch (z->kind) {
+        case DCT_2: return dct_composed_kind<T, DCT_2>(z, s, in, out, batch, tab, st);
+        case DCT_3: return dct_composed_kind<T, DCT_3>(z, s, in, out, batch, tab, st);
+        case DST_2: return dct_composed_kind<T, DST_2>(z, s, in, out, batch, tab, st);
+        default: return dct_composed_kind<T, DST_3>(z, s, in, out, batch, tab, st);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ the entry
+template <typename T>
+static int dct_transform_batch(void* setup, const T* in, T* out, size_t batch, hipStream_t st) {
+    DctSetup* z = dct_checked(setup);
+    if (!z || z->is_double != (sizeof(T) == 8)) {
+        g_last_error = "pffft_hip: bad dct setup handle";
+        return (int)hipErrorInvalidHandle;
+    }
+    if (batch == 0) return 0;
+    if (!in || !out) return bad("dct: NULL in / out");
+    if (((uintptr_t)in | (uintptr_t)out) & 15) return bad("dct: in / out not aligned to 16 bytes");
+    if (in != out) {   // the same rows in place, or rows that do not overlap
+        const uintptr_t i0 = (uintptr_t)in, o0 = (uintptr_t)out, len = batch * (size_t)z->N * sizeof(T);
+        if (i0 < o0 + len && o0 < i0 + len) return bad("dct: in and out overlap without being equal");
+    }
+    Setup* s = for_device(z->inner);   // the object that holds the inner setup's tables on the calling thread's device
+    int rc = ensure_device_any(s);
+    if (rc) return rc;
+    const cx<T>* tab = nullptr;
+    if ((rc = dct_table<T>(z, s, st, &tab))) return rc;
+    if constexpr (sizeof(T) == 4) {
+        DctSel e;
+        if (dct_fused_now(z, ab()) && dct_fusable(z, &e)) return dct_fused(s, e, in, out, batch, tab, st);
+    }
+    return dct_composed<T>(z, s, in, out, batch, tab, st);
+}
+
+}  // namespace pf
+
+PF_EXPORT PFFFT_HIP_DctSetup* pffft_hip_dct_new_setup(int N, pffft_hip_dct_kind_t kind, pffft_hip_dct_norm_t norm) {
+    return reinterpret_cast<PFFFT_HIP_DctSetup*>(pf::dct_new_setup(N, (int)kind, (int)norm, 0));
+}
+PF_EXPORT PFFFTD_HIP_DctSetup* pffftd_hip_dct_new_setup(int N, pffft_hip_dct_kind_t kind, pffft_hip_dct_norm_t norm) {
+    return reinterpret_cast<PFFFTD_HIP_DctSetup*>(pf::dct_new_setup(N, (int)kind, (int)norm, 1));
+}
+PF_EXPORT void pffft_hip_dct_destroy_setup(PFFFT_HIP_DctSetup* s) { pf::dct_destroy_setup(reinterpret_cast<pf::DctSetup*>(s)); }
+PF_EXPORT void pffftd_hip_dct_destroy_setup(PFFFTD_HIP_DctSetup* s) { pf::dct_destroy_setup(reinterpret_cast<pf::DctSetup*>(s)); }
+PF_EXPORT int pffft_hip_dct_transform_batch(PFFFT_HIP_DctSetup* s, const float* in, float* out, size_t batch, void* stream) {
+    return pf::dct_transform_batch<float>(s, in, out, batch, (hipStream_t)stream);
+}
+PF_EXPORT int pffftd_hip_dct_transform_batch(PFFFTD_HIP_DctSetup* s, const double* in, double* out, size_t batch, void* stream) {
+    return pf::dct_transform_batch<double>(s, in, out, batch, (hipStream_t)stream);
+}
+PF_EXPORT const char* pffft_hip_dct_route(const void* setup) {
+    const pf::DctSetup* z = pf::dct_checked(setup);
+    if (!z) return "";
+    return pf::dct_fused_now(z, pf::ab()) ? "fused" : "composed";
+}
+PF_EXPORT int pffft_hip_dct_table(const void* setup, size_t first, size_t count, void* host_out) {
+    const pf::DctSetup* z = pf::dct_checked(setup);
+    if (!z || !host_out) {
+        pf::g_last_error = "pffft_hip: bad dct setup handle / NULL output";
+        return (int)hipErrorInvalidValue;
+    }
+    const size_t len = (size_t)z->N / 2 + 1;
+    if (first > len || count > len - first) {
+        pf::g_last_error = "pffft_hip: dct table range beyond the table";
+        return (int)hipErrorInvalidValue;
+    }
+    for (size_t i = 0; i < count; ++i) {
+        if (z->is_double) static_cast<pf::cx<double>*>(host_out)[i] = pf::dct_table_value<double>(z, first + i);
+        else static_cast<pf::cx<float>*>(host_out)[i] = pf::dct_table_value<float>(z, first + i);
+    }
+    return 0;
+}

@@ -114,6 +114,14 @@ static cx<T> unit_root(long long j, long long denom) {
     w.x = (T)cosl(a); w.y = (T)sinl(a);
     return w;
 }
+// scale * W_denom^j (conj_: its conjugate): the product formed in extended precision, rounded once (the folded tables of fft_dct.h)
+template <typename T>
+static cx<T> scaled_unit_root(long long j, long long denom, long double scale, bool conj_) {
+    const long double a = -2.0L * 3.14159265358979323846264338327950288L * (long double)j / (long double)denom;
+    cx<T> w;
+    w.x = (T)(scale * cosl(a)); w.y = (T)(scale * (conj_ ? -sinl(a) : sinl(a)));
+    return w;
+}
 template <typename T>
 static std::vector<cx<T>> unit_roots(size_t count, long long denom) {
     std::vector<cx<T>> tw(count);
