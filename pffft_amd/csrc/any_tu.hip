@@ -9,8 +9,6 @@
 #include "bluestein_host.h"
 #include "fft_any.h"
 
-#define PF_EXPORT extern "C" __attribute__((visibility("default")))
-
 namespace pf {
 
 constexpr uint32_t ANY_MAGIC = 0x50464159u;   // "PFAY"
@@ -37,11 +35,6 @@ struct AnySetup {
                                    // stream, pad.mu held while a call enqueues
     int bins() const { return is_real ? N / 2 + 1 : N; }
 };
-
-static int bad(const char* what, hipError_t e = hipErrorInvalidValue) {
-    g_last_error = std::string("pffft_hip: ") + what;
-    return (int)e;
-}
 
 static AnySetup* any_checked(const void* p) {
     const AnySetup* a = static_cast<const AnySetup*>(p);
@@ -255,7 +248,7 @@ static int any_real_direct(AnySetup* a, const T* in, T* out, size_t batch, int b
     const size_t chunk = std::max<size_t>(1, std::min(batch, BLUESTEIN_CAP_BYTES / (N * sizeof(T))));
     std::lock_guard<std::mutex> lk(a->pad.mu);
     void* p = nullptr;
-    int rc = bluestein_scratch(a->pad, st, chunk * N * sizeof(T), &p);
+    int rc = scratch_buffer(a->pad, st, chunk * N * sizeof(T), "the scratch image", &p);
     if (rc) return rc;
     T* S = static_cast<T*>(p);
     for (size_t v0 = 0; v0 < batch; v0 += chunk) {

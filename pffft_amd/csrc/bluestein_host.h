@@ -6,11 +6,8 @@
 #include <vector>
 
 #include "../../include/pffft_hip.h"
-#include "pf_host.h"
+#include "pf_launch.h"
 #include "fft_conv.h"
-
-struct PFFFT_Setup : pf::Setup {};
-struct PFFFTD_Setup : pf::Setup {};
 
 namespace pf {
 
@@ -64,17 +61,10 @@ template <class C> struct CfgTag { typedef C type; };
 template <class C, class IO>
 static int bluestein_fused_launch(Setup* s, const IO& io, const float* H, size_t batch, int M, hipStream_t st) {
     auto k = fft_conv_kernel<C, 0, IO>;
-    int rc = allow_big_lds(k, C::LDS_BYTES);
-    if (rc) return rc;
-    int per_cu = 0;
-    if ((rc = cached_occupancy(reinterpret_cast<const void*>(k), C::WG_THREADS, C::LDS_BYTES, &per_cu))) return rc;
-    const size_t groups = (batch + C::T_PER_WG - 1) / C::T_PER_WG;
-    size_t grid = (size_t)num_cus() * per_cu;
-    if (groups <= 4 * grid) grid = groups;
-    if (grid > groups) grid = groups;
-    unsigned* ctr = groups <= grid ? nullptr : take_counters(s, st);
+    LoopLaunch ll;
+    if (int rc = loop_launch(s, st, k, C::WG_THREADS, C::LDS_BYTES, (batch + C::T_PER_WG - 1) / C::T_PER_WG, CONV_ONESHOT, &ll)) return rc;
     const cx<float>* tw = s->d_tw.as<cx<float>>();
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(C::WG_THREADS), C::LDS_BYTES, st, io, H, (unsigned)batch, 1.0f / (float)M, tw, tw, ctr);
+    hipLaunchKernelGGL(k, dim3(ll.grid), dim3(C::WG_THREADS), C::LDS_BYTES, st, io, H, (unsigned)batch, 1.0f / (float)M, tw, tw, ll.ctr);
     PF_CHECK(hipGetLastError());
     return 0;
 }
@@ -112,19 +102,6 @@ static int bluestein_fused(Setup* inner, int M, size_t batch, F&& launch) {
 // ------------------------------------------------------------------------------------------------ the composed route
 constexpr size_t BLUESTEIN_CAP_BYTES = (size_t)256 << 20;   // the scratch image of one launch sequence; longer batches go in chunks
 
-// the scratch image of one call on `st` (under pad.mu): at least `bytes`, never grown during a capture
-static int bluestein_scratch(StreamScratch& pad, hipStream_t st, size_t bytes, void** p) {
-    StreamScratch::Entry& sc = pad.acquire(st);
-    if (sc.buf[0].bytes() < bytes && stream_capturing(st)) {
-        g_last_error = "pffft_hip: the scratch image of this stream would have to grow during graph capture: run the call once on this stream "
-                       "before capturing";
-        return (int)hipErrorStreamCaptureUnsupported;
-    }
-    int rc = pad.grow(sc, 0, bytes);
-    *p = sc.buf[0].get();
-    return rc;
-}
-
 // pad kernel -> pffft[d]_hip_convolve_batch on `inner` (length M, one broadcast filter spectrum H, scaled by 1 / M) -> crop kernel, in
 // chunks of at most 256 MiB of scratch (one row where a row is longer).  pad_k(X, first row, rows) and crop_k(X, first row, rows) launch
 // the two ends on `st` and return 0 or an error.
@@ -133,7 +110,7 @@ static int bluestein_composed(Setup* inner, StreamScratch& pad, const T* H, size
     const size_t chunk = std::max<size_t>(1, std::min(batch, BLUESTEIN_CAP_BYTES / (M * sizeof(cx<T>))));
     std::lock_guard<std::mutex> lk(pad.mu);
     void* p = nullptr;
-    int rc = bluestein_scratch(pad, st, chunk * M * sizeof(cx<T>), &p);
+    int rc = scratch_buffer(pad, st, chunk * M * sizeof(cx<T>), "the scratch image", &p);
     if (rc) return rc;
     cx<T>* X = static_cast<cx<T>*>(p);
     const T scaling = (T)1 / (T)M;

@@ -2,7 +2,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/pffft_hip.h"
-#include "pf_host.h"
+#include "pf_launch.h"
 #include "fft_conv.h"
 
 namespace pf {
@@ -10,18 +10,11 @@ namespace pf {
 template <typename T, class C, int REAL>
 static int conv_launch_io(Setup* s, const T* in, const T* H, T* out, size_t batch, T scaling, int accumulate, hipStream_t st) {
     auto k = fft_conv_kernel<C, REAL>;
-    int rc = allow_big_lds(k, C::LDS_BYTES);
-    if (rc) return rc;
-    int per_cu = 0;
-    if ((rc = cached_occupancy(reinterpret_cast<const void*>(k), C::WG_THREADS, C::LDS_BYTES, &per_cu))) return rc;
-    const size_t groups = (batch + C::T_PER_WG - 1) / C::T_PER_WG;
-    size_t grid = (size_t)num_cus() * per_cu;
-    if (groups <= 4 * grid) grid = groups;        // (short launches: one group per workgroup in dispatch order - the rule of launch_tiled)
-    if (grid > groups) grid = groups;
-    unsigned* ctr = groups <= grid ? nullptr : take_counters(s, st);
+    LoopLaunch ll;
+    if (int rc = loop_launch(s, st, k, C::WG_THREADS, C::LDS_BYTES, (batch + C::T_PER_WG - 1) / C::T_PER_WG, CONV_ONESHOT, &ll)) return rc;
     const ConvDenseIO<C, REAL> io{in, out, accumulate};
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(C::WG_THREADS), C::LDS_BYTES, st, io, H, (unsigned)batch, scaling,
-                       (const cx<T>*)s->d_tw.as<cx<T>>(), (const cx<T>*)s->d_twr.as<cx<T>>(), ctr);
+    hipLaunchKernelGGL(k, dim3(ll.grid), dim3(C::WG_THREADS), C::LDS_BYTES, st, io, H, (unsigned)batch, scaling,
+                       (const cx<T>*)s->d_tw.as<cx<T>>(), (const cx<T>*)s->d_twr.as<cx<T>>(), ll.ctr);
     PF_CHECK(hipGetLastError());
     return 0;
 }

@@ -8,13 +8,8 @@
 #include <memory>
 
 #include "../../include/pffft_hip.h"
-#include "pf_host.h"
+#include "pf_launch.h"
 #include "fft_dct.h"
-
-struct PFFFT_Setup : pf::Setup {};
-struct PFFFTD_Setup : pf::Setup {};
-
-#define PF_EXPORT extern "C" __attribute__((visibility("default")))
 
 namespace pf {
 
@@ -30,11 +25,6 @@ struct DctSetup {
     std::map<const Setup*, DevBuf> d_tab;
     StreamScratch scratch;         // batch x N image of the composed route: one per stream, scratch.mu held while a call enqueues
 };
-
-static int bad(const char* what, hipError_t e = hipErrorInvalidValue) {
-    g_last_error = std::string("pffft_hip: ") + what;
-    return (int)e;
-}
 
 static DctSetup* dct_checked(const void* p) {
     const DctSetup* z = static_cast<const DctSetup*>(p);
@@ -74,7 +64,7 @@ static int dct_table(DctSetup* z, const Setup* s, hipStream_t st, const cx<T>** 
 
 // ------------------------------------------------------------------------------------------------ plan
 typedef void (*DctFn)(const float*, float*, unsigned, const cx<float>*, const cx<float>*, const cx<float>*, unsigned*);
-struct DctSel { DctFn fn = nullptr; size_t lds = 0; int wg = 0, t_per_wg = 0; };
+typedef KernelSel<DctFn> DctSel;
 
 template <class C>
 static DctSel dct_sel(int kind) {
@@ -88,10 +78,12 @@ static DctSel dct_sel(int kind) {
 // The configuration the fused kernel runs on must be the one transform_batch runs on for the same direction in the canonical layout - the
 // results are equal bit for bit only then -, so it is read from the inner setup's stored route: real float on TiledPick C512 / C1024 /
 // C2048 (N = 1024 / 2048 / 4096), forward for type II, backward for type III.  Everything else has no fused kernel.
+static const Route& dct_route(const Setup* s, int kind) { return s->route[dct_type3(kind) ? PFFFT_BACKWARD : PFFFT_FORWARD][1]; }
+
 static bool dct_fusable(const DctSetup* z, DctSel* e) {
     const Setup* s = z->inner;
     if (s->is_double || s->kernel != K_TILED) return false;
-    const Route& r = s->route[dct_type3(z->kind) ? PFFFT_BACKWARD : PFFFT_FORWARD][1];
+    const Route& r = dct_route(s, z->kind);
     if (r.fam != FAM_TILED) return false;
     const std::string cfg = r.tiled.cfg;
     if (s->n == 512 && cfg == "TiledPick::C512") { if (e) *e = dct_sel<TiledPick<float>::C512>(z->kind); return true; }
@@ -134,23 +126,17 @@ static void dct_destroy_setup(DctSetup* z) {
 }
 
 // ------------------------------------------------------------------------------------------------ the two routes
-static int dct_fused(Setup* s, const DctSel& e, const float* in, float* out, size_t batch, const cx<float>* tab, hipStream_t st) {
-    int rc = allow_big_lds(e.fn, e.lds);
-    if (rc) return rc;
-    int per_cu = 0;
-    if ((rc = cached_occupancy(reinterpret_cast<const void*>(e.fn), e.wg, e.lds, &per_cu))) return rc;
+// (oneshot: the launch rule of the transform kernel - of the stored route that dct_fusable read `e` from, frames_tu.hip)
+static int dct_fused(Setup* s, const DctSel& e, int oneshot, const float* in, float* out, size_t batch, const cx<float>* tab, hipStream_t st) {
+    size_t resident = 0;
+    if (int rc = loop_resident(e.fn, e.wg, e.lds, &resident)) return rc;
     const size_t N = (size_t)s->N;
     constexpr size_t SLICE = (size_t)3 << 30;   // (the kernel counts rows in 32 bits: longer batches go out in slices on the stream)
     for (size_t b0 = 0; b0 < batch; b0 += SLICE) {
         const size_t nb = std::min(batch - b0, SLICE);
-        const size_t groups = (nb + e.t_per_wg - 1) / e.t_per_wg;
-        size_t grid = (size_t)num_cus() * per_cu;
-        const int oneshot = env().oneshot;    // the launch rule of launch_tiled
-        if (oneshot > 0 && groups <= (size_t)oneshot * grid) grid = groups;
-        if (grid > groups) grid = groups;
-        unsigned* ctr = groups <= grid ? nullptr : take_counters(s, st);
-        hipLaunchKernelGGL(e.fn, dim3((unsigned)grid), dim3(e.wg), e.lds, st, in + b0 * N, out + b0 * N, (unsigned)nb, tab,
-                           s->d_tw.as<cx<float>>(), s->d_twr.as<cx<float>>(), ctr);
+        const LoopLaunch ll = loop_take(s, st, resident, (nb + e.t_per_wg - 1) / e.t_per_wg, oneshot);
+        hipLaunchKernelGGL(e.fn, dim3(ll.grid), dim3(e.wg), e.lds, st, in + b0 * N, out + b0 * N, (unsigned)nb, tab,
+                           s->d_tw.as<cx<float>>(), s->d_twr.as<cx<float>>(), ll.ctr);
         PF_CHECK(hipGetLastError());
     }
     return 0;
@@ -166,13 +152,10 @@ static int dct_composed_kind(DctSetup* z, Setup* s, const T* in, T* out, size_t 
     const size_t N = (size_t)z->N;
     const size_t chunk = std::max<size_t>(1, std::min(batch, DCT_CAP_BYTES / (N * sizeof(T))));
     std::lock_guard<std::mutex> lk(z->scratch.mu);
-    StreamScratch::Entry& sc = z->scratch.acquire(st);
-    if (sc.buf[0].bytes() < chunk * N * sizeof(T) && stream_capturing(st))
-        return bad("dct: the scratch image of this stream would have to grow during graph capture: run the call once on this stream before "
-                   "capturing", hipErrorStreamCaptureUnsupported);
-    int rc = z->scratch.grow(sc, 0, chunk * N * sizeof(T));
+    void* buf = nullptr;
+    int rc = scratch_buffer(z->scratch, st, chunk * N * sizeof(T), "dct: the scratch image", &buf);
     if (rc) return rc;
-    T* X = sc.buf[0].as<T>();
+    T* X = static_cast<T*>(buf);
     for (size_t v0 = 0; v0 < batch; v0 += chunk) {
         const size_t cnt = std::min(batch - v0, chunk);
         hipLaunchKernelGGL((dct_pre_kernel<T, KIND>), dim3(dct_grid(cnt * (III ? N / 8 : N / 4))), dim3(256), 0, st, in + v0 * N, X, tab, cnt,
@@ -218,7 +201,7 @@ static int dct_transform_batch(void* setup, const T* in, T* out, size_t batch, h
     if ((rc = dct_table<T>(z, s, st, &tab))) return rc;
     if constexpr (sizeof(T) == 4) {
         DctSel e;
-        if (dct_fused_now(z, ab()) && dct_fusable(z, &e)) return dct_fused(s, e, in, out, batch, tab, st);
+        if (dct_fused_now(z, ab()) && dct_fusable(z, &e)) return dct_fused(s, e, dct_route(z->inner, z->kind).oneshot, in, out, batch, tab, st);
     }
     return dct_composed<T>(z, s, in, out, batch, tab, st);
 }

@@ -2,7 +2,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/pffft_hip.h"
-#include "pf_host.h"
+#include "pf_launch.h"
 #include "fft_dma.h"
 #include "fft_split.h"
 #include "fft_fir32.h"
@@ -19,11 +19,9 @@ static int fir_dma_cfg(Setup* ps, const float* d_Hc, const float* d_x, float* d_
     int rc = allow_big_lds(k, G::LDS_BYTES);
     if (rc) return rc;
     const size_t groups = ((size_t)nblk * fb.nsig + C::T_PER_WG - 1) / C::T_PER_WG;
-    size_t grid = (size_t)num_cus();
-    if (grid > groups) grid = groups;
-    unsigned* ctr = groups <= grid ? nullptr : take_counters(ps, st);
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(C::WG_THREADS), G::LDS_BYTES, st, d_x, d_y, (const cx<float>*)d_Hc,
-                       nblk, step, inputLen, lastOut, ps->d_tw.as<cx<float>>(), ps->d_twr.as<cx<float>>(), ctr,
+    const LoopLaunch ll = loop_take(ps, st, (size_t)num_cus(), groups, 0);   // (one workgroup per CU)
+    hipLaunchKernelGGL(k, dim3(ll.grid), dim3(C::WG_THREADS), G::LDS_BYTES, st, d_x, d_y, (const cx<float>*)d_Hc,
+                       nblk, step, inputLen, lastOut, ps->d_tw.as<cx<float>>(), ps->d_twr.as<cx<float>>(), ll.ctr,
                        fb.nsig, fb.xstride, fb.ystride);
     PF_CHECK(hipGetLastError());
     return 0;
@@ -55,8 +53,7 @@ static int fir_split1(Setup* ps, const float* d_Hc, const float* d_x, float* d_y
     typedef SplitOneT<W> S;
     ps = for_device(ps);
     auto k = fastconv_split1_kernel<W>;
-    int rc = allow_big_lds(k, S::LDS_BYTES);
-    if (rc) return rc;
+    int rc = 0;
     if (!ab_cache) {
         // the folded coefficients of this filter: built ONCE and COMPLETE before the pointer is published - null stream + synchronisation,
         // like every other lazily built table (fc_ensure_big, split_sub_table).  Built on the caller's stream (round 4) a second call on
@@ -72,11 +69,9 @@ static int fir_split1(Setup* ps, const float* d_Hc, const float* d_x, float* d_y
     }
     const cx<float>* tw512 = nullptr;
     if ((rc = split_sub_table(&tw512, S::M))) return rc;
-    int per_cu = 0;
-    if ((rc = cached_occupancy(reinterpret_cast<const void*>(k), S::WG, S::LDS_BYTES, &per_cu))) return rc;
-    const size_t groups = (size_t)nblk * fb.nsig;
-    size_t grid = (size_t)num_cus() * per_cu;
-    if (grid > groups) grid = groups;
+    size_t resident = 0;
+    if ((rc = loop_resident(k, S::WG, S::LDS_BYTES, &resident))) return rc;
+    const size_t grid = loop_grid(resident, (size_t)nblk * fb.nsig, 0).grid;   // (a static stride: no counters)
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(S::WG), S::LDS_BYTES, st, d_x, d_y, ab_cache.as<vec4<float>>(), nblk, step, inputLen,
                        lastOut, ps->d_tw.as<cx<float>>(), tw512, fb.nsig, fb.xstride, fb.ystride, env().fir_xcd);
     PF_CHECK(hipGetLastError());
@@ -100,19 +95,17 @@ static int fir_split(Setup* ps, const float* d_Hc, const float* d_x, float* d_y,
     typedef SplitFirT<W> S;
     ps = for_device(ps);
     auto k = fastconv_split_kernel<PSYNC, SPREAD, W>;
-    int rc = allow_big_lds(k, S::LDS_BYTES);
-    if (rc) return rc;
     const cx<float>* tw1024 = nullptr;
-    if ((rc = split_sub_table(&tw1024))) return rc;
-    int per_cu = 0;
-    if ((rc = cached_occupancy(reinterpret_cast<const void*>(k), S::WG, S::LDS_BYTES, &per_cu))) return rc;
+    int rc = split_sub_table(&tw1024);
+    if (rc) return rc;
+    size_t resident = 0;
+    if ((rc = loop_resident(k, S::WG, S::LDS_BYTES, &resident))) return rc;
     const size_t groups = (size_t)nblk * fb.nsig;
-    size_t grid = (size_t)num_cus() * per_cu;
-    if (grid > groups) grid = groups;
+    const LoopGrid g = loop_grid(resident, groups, 0);
     // (the per-XCD ranges of the in-order case are pulled by the workgroups of that XCD only: every XCD needs one - ADVICE r05)
-    const int xmode = (env().fir_xcd && grid >= 8 && groups < 0xfffffff0ull) ? 1 : 0;
-    unsigned* ctr = groups <= grid ? nullptr : take_counters(ps, st, xmode ? 5 : 1);   // (per-XCD counters: nine words)
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(S::WG), S::LDS_BYTES, st, d_x, d_y, (const cx<float>*)d_Hc,
+    const int xmode = (env().fir_xcd && g.grid >= 8 && groups < 0xfffffff0ull) ? 1 : 0;
+    unsigned* ctr = g.needs_counters ? take_counters(ps, st, xmode ? 5 : 1) : nullptr;   // (per-XCD counters: nine words)
+    hipLaunchKernelGGL(k, dim3((unsigned)g.grid), dim3(S::WG), S::LDS_BYTES, st, d_x, d_y, (const cx<float>*)d_Hc,
                        nblk, step, inputLen, lastOut, ps->d_tw.as<cx<float>>(), tw1024, ps->d_twr.as<cx<float>>(), ctr,
                        fb.nsig, fb.xstride, fb.ystride, xmode);
     PF_CHECK(hipGetLastError());
@@ -126,8 +119,7 @@ static int fir32(Setup* ps, const float* d_Hc, const float* d_x, float* d_y, int
                  hipStream_t st, const FcBatch& fb, DevBuf& hp_cache) {
     ps = for_device(ps);
     auto k = fastconv_fused32_kernel<PREF>;
-    int rc = allow_big_lds(k, Fir32::LDS_BYTES);
-    if (rc) return rc;
+    int rc = 0;
     if (!hp_cache) {
         DevBuf hp;
         if ((rc = hp.grow(sizeof(float) * 4 * (size_t)Fir32::n))) return rc;
@@ -137,15 +129,14 @@ static int fir32(Setup* ps, const float* d_Hc, const float* d_x, float* d_y, int
         if (e != hipSuccess) return fail(e, "fir32_coef_kernel");
         hp_cache = std::move(hp);
     }
-    int per_cu = 0;
-    if ((rc = cached_occupancy(reinterpret_cast<const void*>(k), Fir32::WG, Fir32::LDS_BYTES, &per_cu))) return rc;
+    size_t resident = 0;
+    if ((rc = loop_resident(k, Fir32::WG, Fir32::LDS_BYTES, &resident))) return rc;
     const size_t groups = (size_t)nblk * fb.nsig;
-    size_t grid = (size_t)num_cus() * per_cu;
-    if (grid > groups) grid = groups;
+    const LoopGrid g = loop_grid(resident, groups, 0);
     // (the per-XCD ranges need every XCD to have a workgroup: ADVICE r05)
-    const int xmode = (env().fir_xcd && grid >= 8 && groups < 0xfffffff0ull) ? 1 : 0;
-    unsigned* ctr = groups <= grid ? nullptr : take_counters(ps, st, xmode ? 5 : 1);
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(Fir32::WG), Fir32::LDS_BYTES, st, d_x, d_y, hp_cache.as<vec4<float>>(),
+    const int xmode = (env().fir_xcd && g.grid >= 8 && groups < 0xfffffff0ull) ? 1 : 0;
+    unsigned* ctr = g.needs_counters ? take_counters(ps, st, xmode ? 5 : 1) : nullptr;
+    hipLaunchKernelGGL(k, dim3((unsigned)g.grid), dim3(Fir32::WG), Fir32::LDS_BYTES, st, d_x, d_y, hp_cache.as<vec4<float>>(),
                        nblk, step, inputLen, lastOut, ps->d_tw.as<cx<float>>(), ps->d_twr.as<cx<float>>(), ctr,
                        fb.nsig, fb.xstride, fb.ystride, xmode);
     PF_CHECK(hipGetLastError());

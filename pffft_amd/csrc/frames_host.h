@@ -6,7 +6,7 @@
 #include <algorithm>
 
 #include "../../include/pffft_hip.h"
-#include "pf_host.h"
+#include "pf_launch.h"
 #include "fft_frames.h"
 
 namespace pf {
@@ -15,24 +15,13 @@ namespace pf {
 // chunks on the stream.
 constexpr size_t FRAMES_CAP_BYTES = (size_t)256 << 20;
 
-static int bad(const char* what, hipError_t e = hipErrorInvalidValue) {
-    g_last_error = std::string("pffft_hip: ") + what;
-    return (int)e;
-}
-
 static unsigned stream_grid(size_t items) {
     return (unsigned)std::max<size_t>(1, std::min<size_t>((items + 255) / 256, (size_t)num_cus() * 16));
 }
 
 // the frame matrix of `st` (frames.mu held by the caller), grown to `bytes`: outside graph capture only
 static int frames_buffer(Setup* s, hipStream_t st, size_t bytes, void** buf) {
-    StreamScratch::Entry& sc = s->frames.acquire(st);
-    if (sc.buf[0].bytes() < bytes && stream_capturing(st))
-        return bad("the frame matrix of this stream would have to grow during graph capture: run the call once on this stream before capturing",
-                   hipErrorStreamCaptureUnsupported);
-    if (int rc = s->frames.grow(sc, 0, bytes)) return rc;
-    *buf = sc.buf[0].get();
-    return 0;
+    return scratch_buffer(s->frames, st, bytes, "the frame matrix", buf);
 }
 
 template <typename T, int MODE>

@@ -8,17 +8,12 @@
 #include "../../include/pffft_hip.h"
 #include "frames_host.h"
 
-struct PFFFT_Setup : pf::Setup {};
-struct PFFFTD_Setup : pf::Setup {};
-
-#define PF_EXPORT extern "C" __attribute__((visibility("default")))
-
 namespace pf {
 
 // ------------------------------------------------------------------------------------------------ fused analysis
 typedef void (*FramesFn)(const float*, size_t, unsigned, size_t, const float*, float*, size_t, unsigned, const cx<float>*,
                          const cx<float>*, unsigned*);
-struct FramesSel { FramesFn fn = nullptr; size_t lds = 0; int wg = 0, t_per_wg = 0; };
+typedef KernelSel<FramesFn> FramesSel;
 
 // Window values: resident in registers (WMODE 1; 32 VGPRs) - the resource remarks of the three configurations show no scratch and the
 // occupancy of the unframed kernel with them.  WMODE 2 (LDS table) is the twin kept for configurations where they would not.
@@ -42,9 +37,11 @@ static FramesSel frames_sel(int output, bool windowed) {
 // The configuration the framed kernel runs on must be the one transform_batch runs on for the same (direction, layout) - the results are
 // equal bit for bit only then -, so it is read from the setup's stored route: real float forward on TiledPick C512 / C1024 / C2048
 // (N = 1024 / 2048 / 4096).  Everything else has no framed kernel.
+static const Route& frames_route(const Setup* s, int output) { return s->route[PFFFT_FORWARD][output == FR_INTERNAL ? 0 : 1]; }
+
 static bool frames_fusable_setup(const Setup* s, int output, FramesSel* e, bool windowed) {
     if (s->is_double || s->transform != PFFFT_REAL || s->kernel != K_TILED) return false;
-    const Route& r = s->route[PFFFT_FORWARD][output == FR_INTERNAL ? 0 : 1];
+    const Route& r = frames_route(s, output);
     if (r.fam != FAM_TILED) return false;
     const std::string cfg = r.tiled.cfg;
     if (s->n == 512 && cfg == "TiledPick::C512") { if (e) *e = frames_sel<TiledPick<float>::C512>(output, windowed); return true; }
@@ -71,33 +68,15 @@ static bool frames_route_fused(const Setup* s, size_t hop, size_t signal_stride,
     return sel.is(AB_FRAMES_FUSED) || frames_fused_default(s->n, output);
 }
 
-static int launch_frames_fused(Setup* s, const FramesSel& e, const float* signal, size_t signal_stride, size_t nframes, size_t hop,
+// The launch rule of the transform kernel: the `oneshot` of the stored route whose configuration `e` was read from.  It equals
+// env().oneshot for every setup that has a framed kernel today (real float, n = 512 to 2048); the PSD and DCT entries do the same.
+static int launch_frames_fused(Setup* s, const FramesSel& e, int oneshot, const float* signal, size_t signal_stride, size_t nframes, size_t hop,
                                const float* window, float* out, size_t out_stride, size_t batch, hipStream_t st) {
-    int rc = allow_big_lds(e.fn, e.lds);
-    if (rc) return rc;
-    int per_cu = 0;
-    if ((rc = cached_occupancy(reinterpret_cast<const void*>(e.fn), e.wg, e.lds, &per_cu))) return rc;
-    const size_t groups = (batch + e.t_per_wg - 1) / e.t_per_wg;
-    size_t grid = (size_t)num_cus() * per_cu;
-    const int oneshot = env().oneshot;    // the launch rule of launch_tiled
-    if (oneshot > 0 && groups <= (size_t)oneshot * grid) grid = groups;
-    if (grid > groups) grid = groups;
-    unsigned* ctr = groups <= grid ? nullptr : take_counters(s, st);
-    hipLaunchKernelGGL(e.fn, dim3((unsigned)grid), dim3(e.wg), e.lds, st, signal, signal_stride, (unsigned)nframes, hop, window, out,
-                       out_stride, (unsigned)batch, s->d_tw.as<cx<float>>(), s->d_twr.as<cx<float>>(), ctr);
+    LoopLaunch ll;
+    if (int rc = loop_launch(s, st, e.fn, e.wg, e.lds, (batch + e.t_per_wg - 1) / e.t_per_wg, oneshot, &ll)) return rc;
+    hipLaunchKernelGGL(e.fn, dim3(ll.grid), dim3(e.wg), e.lds, st, signal, signal_stride, (unsigned)nframes, hop, window, out,
+                       out_stride, (unsigned)batch, s->d_tw.as<cx<float>>(), s->d_twr.as<cx<float>>(), ll.ctr);
     PF_CHECK(hipGetLastError());
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------------ shared pieces
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-template <typename T>
-static int check_setup(const Setup* s) {
-    if (!s || s->magic != MAGIC || s->is_double != (sizeof(T) == 8)) {
-        g_last_error = "pffft_hip: bad setup handle";
-        return (int)hipErrorInvalidHandle;
-    }
     return 0;
 }
 
@@ -130,12 +109,13 @@ static int frames_transform_batch(Setup* s, const T* signal, size_t signal_strid
             (output == FR_POWER || aligned16(out)) && frames_fusable_setup(s, output, &e, window != nullptr)) {
             // (the kernel counts frames in 32 bits: longer batches of ONE signal go out in slices; several signals that long are composed)
             constexpr size_t SLICE = (size_t)3 << 30;
+            const int oneshot = frames_route(s, output).oneshot;
             if (batch <= SLICE)
-                return launch_frames_fused(s, e, signal, signal_stride, nframes, hop_s, window, out, out_stride, batch, st);
+                return launch_frames_fused(s, e, oneshot, signal, signal_stride, nframes, hop_s, window, out, out_stride, batch, st);
             if (nsignals == 1) {
                 for (size_t b0 = 0; b0 < batch; b0 += SLICE) {
                     const size_t nb = std::min(batch - b0, SLICE);
-                    if ((rc = launch_frames_fused(s, e, signal + b0 * hop_s, 0, nb, hop_s, window, out + b0 * out_stride, out_stride, nb, st))) return rc;
+                    if ((rc = launch_frames_fused(s, e, oneshot, signal + b0 * hop_s, 0, nb, hop_s, window, out + b0 * out_stride, out_stride, nb, st))) return rc;
                 }
                 return 0;
             }

@@ -30,6 +30,16 @@ int fail(hipError_t e, const char* what);
         if (_e != hipSuccess) return fail(_e, #expr);    \
     } while (0)
 
+// a refused argument / state: the text behind pffft_hip_last_error(), the code the entry returns
+inline int bad(const char* what, hipError_t e = hipErrorInvalidValue) {
+    g_last_error = std::string("pffft_hip: ") + what;
+    return (int)e;
+}
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// the C ABI of include/pffft_hip.h (exports.map lists the names)
+#define PF_EXPORT extern "C" __attribute__((visibility("default")))
+
 int num_cus();
 
 // is `st` recording into a HIP graph right now (hipStreamIsCapturing; errors read as "no")
@@ -123,6 +133,28 @@ Setup* for_device(Setup* s);
 // devices `s` holds state on right now (its own binding first): fills out[0 .. max), returns the count (pffft_hip_setup_devices)
 int setup_devices(Setup* s, int* out, int max);
 
+// every entry that takes a setup of the scalar type T checks the handle first
+template <typename T>
+static int check_setup(const Setup* s) {
+    if (!s || s->magic != MAGIC || s->is_double != (sizeof(T) == 8)) {
+        g_last_error = "pffft_hip: bad setup handle";
+        return (int)hipErrorInvalidHandle;
+    }
+    return 0;
+}
+
+// Buffer 0 of `pool`'s entry for `st` (pool.mu held by the caller), at least `bytes`.  It never grows while the stream records a HIP
+// graph: a replay would run on the pointer it froze.  `what` names the buffer in the error text ("the frame matrix").
+inline int scratch_buffer(StreamScratch& pool, hipStream_t st, size_t bytes, const char* what, void** buf) {
+    StreamScratch::Entry& sc = pool.acquire(st);
+    if (sc.buf[0].bytes() < bytes && stream_capturing(st))
+        return bad((std::string(what) + " of this stream would have to grow during graph capture: run the call once on this stream before "
+                    "capturing").c_str(), hipErrorStreamCaptureUnsupported);
+    if (int rc = pool.grow(sc, 0, bytes)) return rc;
+    *buf = sc.buf[0].get();
+    return 0;
+}
+
 // pffft_hip.hip, for frames_tu.hip: pffft(d)_hip_transform_batch on a checked setup, and the lazy device initialisation of a resolved one
 int transform_batch_any(Setup* s, const void* in, void* out, size_t batch, int dir, int ordered, hipStream_t st);
 int ensure_device_any(Setup* s);
@@ -173,3 +205,7 @@ int tile_plan_override(long long n, bool is_double, int l1, int g1, int l2, int 
 int tile_plan_layouts(long long n, bool is_double, int mode);   // bit 0: internal layout out of the last pass, bit 1: into the first   // 0 / 2 / 3 passes (pffft_hip_tile_plan)
 
 }  // namespace pf
+
+// the opaque handles of include/pffft_hip.h
+struct PFFFT_Setup : pf::Setup {};
+struct PFFFTD_Setup : pf::Setup {};

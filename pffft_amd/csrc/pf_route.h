@@ -104,10 +104,16 @@ enum LaunchRule : uint8_t {
 };
 const char* launch_rule_name(LaunchRule r);
 
-struct TiledSel {            // a register-tiled configuration (fft_tiled.h), type-erased
-    const void* fn = nullptr;
+// one kernel instantiation picked at run time: its pointer (type-erased over the configuration), dynamic LDS bytes, workgroup threads
+// and vectors per workgroup
+template <class Fn>
+struct KernelSel {
+    Fn fn = nullptr;
     size_t lds = 0;
     int wg = 0, t_per_wg = 0;
+};
+
+struct TiledSel : KernelSel<const void*> {   // a register-tiled configuration (fft_tiled.h), erased over the scalar type too
     const char* cfg = "";
 };
 

@@ -10,11 +10,6 @@
 #include "frames_host.h"
 #include "fft_pfb.h"
 
-struct PFFFT_Setup : pf::Setup {};
-struct PFFFTD_Setup : pf::Setup {};
-
-#define PF_EXPORT extern "C" __attribute__((visibility("default")))
-
 static_assert(pf::PFB_FUSED_MAX_TAPS == PFFFT_HIP_PFB_FUSED_MAX_TAPS, "the header's constant is the kernel's");
 
 namespace pf {
@@ -86,10 +81,7 @@ static int launch_fold(const T* signal, size_t signal_stride, size_t nframes, si
 template <typename T>
 static int pfb_transform_batch(Setup* s, const T* signal, size_t signal_stride, size_t nsignals, size_t nframes, size_t hop,
                                const T* prototype, size_t taps, T* out, size_t out_stride, int output, hipStream_t st) {
-    if (!s || s->magic != MAGIC || s->is_double != (sizeof(T) == 8)) {
-        g_last_error = "pffft_hip: bad setup handle";
-        return (int)hipErrorInvalidHandle;
-    }
+    if (int rc = check_setup<T>(s)) return rc;
     if (hop == 0) return bad("pfb: hop == 0");
     if (taps == 0) return bad("pfb: taps == 0");
     if (!prototype) return bad("pfb: NULL prototype");
@@ -188,10 +180,7 @@ static int launch_syn(SynForm form, size_t spp, const T* y, size_t fbase, size_t
 template <typename T>
 static int pfb_synthesis_batch(Setup* s, const T* spectra, size_t spectra_stride, size_t nsignals, size_t nframes, size_t hop,
                                const T* prototype, size_t taps, T scaling, T* signal, size_t signal_stride, int ordered, hipStream_t st) {
-    if (!s || s->magic != MAGIC || s->is_double != (sizeof(T) == 8)) {
-        g_last_error = "pffft_hip: bad setup handle";
-        return (int)hipErrorInvalidHandle;
-    }
+    if (int rc = check_setup<T>(s)) return rc;
     if (hop == 0) return bad("pfb synthesis: hop == 0");
     if (taps == 0) return bad("pfb synthesis: taps == 0");
     if (!prototype) return bad("pfb synthesis: NULL prototype");

@@ -185,18 +185,13 @@ template <class C>
 static int fc_launch_fused(FastConv* s, const float* d_x, float* d_y, int nblk, int step, int inputLen, int lastOut,
                            hipStream_t st, const FcBatch& fb, PFFFT_Setup* pst = nullptr, const float* d_Hc = nullptr) {
     auto k = fastconv_fused_kernel<C>;
-    int rc = allow_big_lds(k, C::LDS_BYTES);
-    if (rc) return rc;
-    int per_cu = 0;
-    if ((rc = cached_occupancy(reinterpret_cast<const void*>(k), C::WG_THREADS, C::LDS_BYTES, &per_cu))) return rc;
-    size_t groups = ((size_t)nblk * fb.nsig + C::T_PER_WG - 1) / C::T_PER_WG;
-    size_t grid = (size_t)num_cus() * per_cu;
-    if (grid > groups) grid = groups;
+    size_t resident = 0;
+    if (int rc = loop_resident(k, C::WG_THREADS, C::LDS_BYTES, &resident)) return rc;
     Setup* ps = for_device(pst ? pst : s->st);
     if (!d_Hc) d_Hc = s->d_Hc.as<float>();
-    unsigned* ctr = groups <= grid ? nullptr : take_counters(ps, st);
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(C::WG_THREADS), C::LDS_BYTES, st, d_x, d_y, (const cx<float>*)d_Hc,
-                       nblk, step, inputLen, lastOut, ps->d_tw.as<cx<float>>(), ps->d_twr.as<cx<float>>(), ctr,
+    const LoopLaunch ll = loop_take(ps, st, resident, ((size_t)nblk * fb.nsig + C::T_PER_WG - 1) / C::T_PER_WG, 0);
+    hipLaunchKernelGGL(k, dim3(ll.grid), dim3(C::WG_THREADS), C::LDS_BYTES, st, d_x, d_y, (const cx<float>*)d_Hc,
+                       nblk, step, inputLen, lastOut, ps->d_tw.as<cx<float>>(), ps->d_twr.as<cx<float>>(), ll.ctr,
                        fb.nsig, fb.xstride, fb.ystride);
     PF_CHECK(hipGetLastError());
     return 0;

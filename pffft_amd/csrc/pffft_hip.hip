@@ -17,6 +17,7 @@
 
 #include "../../include/pffft_hip.h"
 #include "pf_host.h"
+#include "pf_launch.h"
 #include "fft_c1024.h"
 #include "fft_generic.h"
 #include "fft_tiled.h"
@@ -671,22 +672,15 @@ template <typename T>
 static int launch_tiled(Setup* s, const Route& r, const T* in, T* out, size_t batch, int dir, int ordered, hipStream_t st) {
     const TiledSel& e = r.tiled;
     TiledFn<T> fn = reinterpret_cast<TiledFn<T>>(const_cast<void*>(e.fn));
-    int rc = allow_big_lds(fn, e.lds);
-    if (rc) return rc;
-    int per_cu = 0;
-    if ((rc = cached_occupancy(e.fn, e.wg, e.lds, &per_cu))) return rc;
-    size_t groups = (batch + e.t_per_wg - 1) / e.t_per_wg;
-    size_t grid = (size_t)num_cus() * per_cu;
     // LR_INORDER: launches of up to r.oneshot groups per resident workgroup run as ONE group per workgroup in hardware dispatch order instead of
-    // the persistent in-order loop, which pays for itself only over a long run of groups (tools/r4_small_batch.py, us per call, loop ->
+    // the persistent in-order loop (pf_launch.h), which pays for itself only over a long run of groups (tools/r4_small_batch.py, us per call, loop ->
     // dispatch order: C3's kernel at 64 / 128 MiB of vectors 46 / 72 -> 30 / 60, N = 4096 complex 44 / 69 -> 24 / 49, N = 256 at 32 MiB 25 -> 14,
     // N = 1024 double at 64 MiB 34 -> 27; from 8 groups per workgroup on the loop wins: N = 1024 double at 256 MiB 98 against 110)
-    if (r.oneshot > 0 && groups <= (size_t)r.oneshot * grid && groups < 0x7fffffffull) grid = groups;
-    if (grid > groups) grid = groups;
+    LoopLaunch ll;
+    if (int rc = loop_launch(s, st, fn, e.wg, e.lds, (batch + e.t_per_wg - 1) / e.t_per_wg, r.oneshot, &ll)) return rc;
     const int flags = (((dir == PFFFT_BACKWARD) && !ordered) ? 1 : 0) | (((dir == PFFFT_FORWARD) && !ordered) ? 2 : 0);
-    unsigned* ctr = groups <= grid ? nullptr : take_counters(s, st);
-    hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(e.wg), e.lds, st, in, out, (unsigned)batch, flags,
-                       s->d_tw.as<cx<T>>(), s->d_twr.as<cx<T>>(), ctr);
+    hipLaunchKernelGGL(fn, dim3(ll.grid), dim3(e.wg), e.lds, st, in, out, (unsigned)batch, flags,
+                       s->d_tw.as<cx<T>>(), s->d_twr.as<cx<T>>(), ll.ctr);
     PF_CHECK(hipGetLastError());
     return 0;
 }
@@ -785,14 +779,11 @@ static int launch_stock(Setup* s, const Route& r, const T* in, T* out, size_t ba
     // the same bodies on the run-time plan (0.3 of the roofline: issue-bound).  Every legal size has a compile-time plan
     // (tests/test_generated_sources.py), so the product build does not carry these kernels (2 MB); AB_STOCK_RUNTIME forces them here.
     auto kf = k.wl ? fft_stock_wl_kernel<T> : fft_stock_kernel<T>;
-    int rc = allow_big_lds(kf, k.lds);
-    if (rc) return rc;
-    int per_cu = 0;
-    if ((rc = cached_occupancy(reinterpret_cast<const void*>(kf), k.threads, k.lds, &per_cu))) return rc;
-    size_t grid = (size_t)num_cus() * per_cu;
-    if (grid > groups) grid = groups;
-    unsigned* ctr = (groups <= grid || !dyn) ? nullptr : take_counters(s, st);
-    hipLaunchKernelGGL(kf, dim3((unsigned)grid), dim3(k.threads), k.lds, st, in, out, batch, sp, k.flags, twp, s->d_twr.as<cx<T>>(), ctr, chunk_for(grid));
+    size_t resident = 0;
+    if (int rc = loop_resident(kf, k.threads, k.lds, &resident)) return rc;
+    const LoopGrid g = loop_grid(resident, groups, 0);
+    unsigned* ctr = (g.needs_counters && dyn) ? take_counters(s, st) : nullptr;   // (the static stride reads no counter)
+    hipLaunchKernelGGL(kf, dim3((unsigned)g.grid), dim3(k.threads), k.lds, st, in, out, batch, sp, k.flags, twp, s->d_twr.as<cx<T>>(), ctr, chunk_for(g.grid));
     PF_CHECK(hipGetLastError());
     return 0;
 #else
@@ -1131,10 +1122,7 @@ static void plan_routes(Setup* s) {
 
 template <typename T>
 static int transform_batch(Setup* s, const T* in, T* out, size_t batch, int dir, int ordered, hipStream_t st) {
-    if (!s || s->magic != MAGIC || s->is_double != (sizeof(T) == 8)) {
-        g_last_error = "pffft_hip: bad setup handle";
-        return (int)hipErrorInvalidHandle;
-    }
+    if (int rc = check_setup<T>(s)) return rc;
     if ((dir != PFFFT_FORWARD && dir != PFFFT_BACKWARD)) { g_last_error = "pffft_hip: bad direction"; return (int)hipErrorInvalidValue; }
     if (batch == 0) return 0;
     s = for_device(s);        // the object that holds this setup's tables on the calling thread's device
@@ -1469,10 +1457,7 @@ __global__ void vec_add_kernel(const T* __restrict__ x, T* __restrict__ out, siz
 template <typename T>
 static int convolve_batch(Setup* s, const T* in, const T* H, T* out, T scaling, size_t batch, int accumulate, int h_broadcast,
                           hipStream_t st) {
-    if (!s || s->magic != MAGIC || s->is_double != (sizeof(T) == 8)) {
-        g_last_error = "pffft_hip: bad setup handle";
-        return (int)hipErrorInvalidHandle;
-    }
+    if (int rc = check_setup<T>(s)) return rc;
     if (batch == 0) return 0;
     s = for_device(s);
     int rc = ensure_device<T>(s);
@@ -1518,10 +1503,7 @@ static bool zero_copy_enabled() { return env().zero_copy; }
 // run `fn(d_in..., d_out)` with up to 3 inputs + 1 output vector of `bytes` bytes each
 template <typename T, typename F>
 static int legacy_run(Setup* s, const T* const* ins, int nin, T* out, bool out_is_inout, F&& fn) {
-    if (!s || s->magic != MAGIC || s->is_double != (sizeof(T) == 8)) {
-        g_last_error = "pffft_hip: bad setup handle";
-        return (int)hipErrorInvalidHandle;
-    }
+    if (int rc = check_setup<T>(s)) return rc;
     s = for_device(s);        // (the staging buffers of the calling thread's device)
     const size_t bytes = s->vec_scalars * sizeof(T);
     // the staging buffers belong to the setup; the mutex keeps concurrent callers correct
@@ -1652,11 +1634,6 @@ static int validate_layout(FILE* dbg) {
 // ------------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------------
-struct PFFFT_Setup : pf::Setup {};
-struct PFFFTD_Setup : pf::Setup {};
-
-#define PF_EXPORT extern "C" __attribute__((visibility("default")))
-
 #define PF_DEFINE_API(PFX, SETUP, T, ISD, ARCHSTR)                                                                  \
     PF_EXPORT SETUP* PFX##_new_setup(int N, pffft_transform_t tr) {                                                 \
         return static_cast<SETUP*>(pf::new_setup(N, (int)tr, ISD));                                                 \

@@ -9,11 +9,6 @@
 #include "frames_host.h"
 #include "fft_psd.h"
 
-struct PFFFT_Setup : pf::Setup {};
-struct PFFFTD_Setup : pf::Setup {};
-
-#define PF_EXPORT extern "C" __attribute__((visibility("default")))
-
 static_assert(pf::PSD_RUN == PFFFT_HIP_PSD_RUN, "the run length is part of the contract");
 
 namespace pf {
@@ -27,7 +22,7 @@ constexpr size_t PSD_SLICE = (size_t)3 << 30;
 // ------------------------------------------------------------------------------------------------ fused
 typedef void (*PsdFn)(const float*, size_t, unsigned, unsigned, size_t, const float*, float*, size_t, size_t, unsigned, float,
                       const cx<float>*, const cx<float>*, unsigned*);
-struct PsdSel { PsdFn fn = nullptr; size_t lds = 0; int wg = 0, t_per_wg = 0; };
+typedef KernelSel<PsdFn> PsdSel;
 
 // Window values: resident in registers (WMODE 1), as in the frame kernel.  With the E + 1 accumulators on top of them the resource remarks
 // of the three configurations still show no scratch and the occupancy of fft_frames_kernel<C, FR_POWER, 1>, so the LDS
@@ -74,43 +69,19 @@ static bool psd_route_fused(const Setup* s, size_t hop, size_t signal_stride, si
 
 static int launch_psd_fused(Setup* s, const PsdSel& e, const float* signal, size_t signal_stride, size_t G, size_t navg, size_t hop,
                             const float* window, float* dst, size_t dst_stride, size_t row0, size_t nruns, float scale, hipStream_t st) {
-    int rc = allow_big_lds(e.fn, e.lds);
-    if (rc) return rc;
-    int per_cu = 0;
-    if ((rc = cached_occupancy(reinterpret_cast<const void*>(e.fn), e.wg, e.lds, &per_cu))) return rc;
-    const size_t groups = (nruns + e.t_per_wg - 1) / e.t_per_wg;
-    size_t grid = (size_t)num_cus() * per_cu;
-    const int oneshot = env().oneshot;    // the launch rule of launch_tiled
-    if (oneshot > 0 && groups <= (size_t)oneshot * grid) grid = groups;
-    if (grid > groups) grid = groups;
-    unsigned* ctr = groups <= grid ? nullptr : take_counters(s, st);
-    hipLaunchKernelGGL(e.fn, dim3((unsigned)grid), dim3(e.wg), e.lds, st, signal, signal_stride, (unsigned)G, (unsigned)navg, hop, window, dst,
-                       dst_stride, row0, (unsigned)nruns, scale, s->d_tw.as<cx<float>>(), s->d_twr.as<cx<float>>(), ctr);
+    // the launch rule of the transform kernel: the `oneshot` of the stored route that psd_fusable_setup read `e` from (frames_tu.hip)
+    LoopLaunch ll;
+    if (int rc = loop_launch(s, st, e.fn, e.wg, e.lds, (nruns + e.t_per_wg - 1) / e.t_per_wg, s->route[PFFFT_FORWARD][1].oneshot, &ll)) return rc;
+    hipLaunchKernelGGL(e.fn, dim3(ll.grid), dim3(e.wg), e.lds, st, signal, signal_stride, (unsigned)G, (unsigned)navg, hop, window, dst,
+                       dst_stride, row0, (unsigned)nruns, scale, s->d_tw.as<cx<float>>(), s->d_twr.as<cx<float>>(), ll.ctr);
     PF_CHECK(hipGetLastError());
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------------ shared pieces
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// the partial buffer of `st` (psd.mu held by the caller), grown to `bytes`: outside graph capture only
-static int psd_buffer(Setup* s, hipStream_t st, size_t bytes, void** buf) {
-    StreamScratch::Entry& sc = s->psd.acquire(st);
-    if (sc.buf[0].bytes() < bytes && stream_capturing(st))
-        return bad("the partial buffer of this stream would have to grow during graph capture: run the call once on this stream before capturing",
-                   hipErrorStreamCaptureUnsupported);
-    if (int rc = s->psd.grow(sc, 0, bytes)) return rc;
-    *buf = sc.buf[0].get();
     return 0;
 }
 
 template <typename T>
 static int psd_batch(Setup* s, const T* signal, size_t signal_stride, size_t nsignals, size_t nframes, size_t hop, const T* window,
                      size_t navg, T scaling, T* out, size_t out_stride, hipStream_t st) {
-    if (!s || s->magic != MAGIC || s->is_double != (sizeof(T) == 8)) {
-        g_last_error = "pffft_hip: bad setup handle";
-        return (int)hipErrorInvalidHandle;
-    }
+    if (int rc = check_setup<T>(s)) return rc;
     if (hop == 0) return bad("psd: hop == 0");
     if (nsignals == 0 || nframes == 0) return 0;
     if (navg == 0) navg = nframes;
@@ -155,7 +126,7 @@ static int psd_batch(Setup* s, const T* signal, size_t signal_stride, size_t nsi
     T* X = nullptr;
     if (rpg > 1) {
         lkp.lock();
-        if ((rc = psd_buffer(s, st, vstep * rpg * P * sizeof(T), &buf))) return rc;
+        if ((rc = scratch_buffer(s->psd, st, vstep * rpg * P * sizeof(T), "the partial buffer", &buf))) return rc;
         part = (T*)buf;
     }
     if (!fused) {

@@ -10,8 +10,6 @@
 #include "bluestein_host.h"
 #include "fft_zoom.h"
 
-#define PF_EXPORT extern "C" __attribute__((visibility("default")))
-
 namespace pf {
 
 constexpr uint32_t ZOOM_MAGIC = 0x50465A4Du;   // "PFZM"
@@ -140,11 +138,6 @@ struct ZoomSetup {
     DevBuf d_H;                    // spectrum of the filter b in the inner setup's internal layout
     StreamScratch pad;             // batch x M image of the composed route: one per stream, pad.mu held while a call enqueues
 };
-
-static int bad(const char* what, hipError_t e = hipErrorInvalidValue) {
-    g_last_error = std::string("pffft_hip: ") + what;
-    return (int)e;
-}
 
 static ZoomSetup* zoom_checked(const void* p) {
     const ZoomSetup* z = static_cast<const ZoomSetup*>(p);

@@ -467,7 +467,7 @@ def test_frames_fused_loops_bit_for_bit(N):
     w = uniform((N,), N + 9, torch.float32)
     for output, line in (("ordered", lines[0]), ("internal", lines[1])):
         m = ls.loop_shape(line, max(1, pa.route_occupancy(s, pa.FORWARD, output == "ordered")), cus(), ls.core_vector_bytes(head)).m
-        # (launch_frames_fused reads the library-wide oneshot itself, not the route's: the two agree as long as no real size has one of its own)
+        # (launch_frames_fused launches under the oneshot of this very route: the library-wide value for every real size that has a framed kernel)
         assert m == 4, line
         B = ls.fused_long_batch(cus(), ls.core_vector_bytes(head), m)
         assert pa.frames_route(s, hop, 0, 0, output) == "fused"
