@@ -1,9 +1,6 @@
 // libpffft_hip.so, translation unit of the any-length transforms, complex and real (include/pffft_hip.h: pffft[d]_hip_any_*): Bluestein's
 // algorithm on the library's own convolution.  Plan (route, convolution length) at setup, tables on first use, the fused kernel's launch and the
 // composed route through a per-stream scratch image.  Kernels: fft_any.h.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
 #include <memory>
 
 #include "bluestein_host.h"
@@ -16,18 +13,14 @@ constexpr int ANY_MAX_N = 1 << 25;             // M <= 2^26, the library's large
 
 enum AnyRoute { ANY_DIRECT = 0, ANY_FUSED = 1, ANY_COMPOSED = 2 };
 
-// One setup serves ONE device, like PFFASTCONV_Setup: the tables are built on the device that is current at the first call, and a call
-// from a thread whose current device is another one is refused.
-struct AnySetup {
-    uint32_t magic = ANY_MAGIC;
-    int N = 0, is_double = 0;
+// The owned inner setup has length N (direct) or M.  One setup serves ONE device (bind_device_once).
+struct AnySetup : InnerOwner<ANY_MAGIC> {
+    static constexpr const char* KIND = "any-length";
+    int N = 0;
     int is_real = 0;               // pffft[d]_hip_any_new_real_setup: rows of N reals <-> H = N/2 + 1 complex bins
     AnyRoute route = ANY_DIRECT;   // the default route, fixed at setup
     int M = 0;                     // convolution length; 0 on the direct route
-    Setup* inner = nullptr;        // length N (direct) or M: a PFFFT_Setup / PFFFTD_Setup, owned
-    std::mutex mu;                 // guards the lazy tables
-    bool ready = false;
-    int device = -1;
+    DeviceBinding bound;
     DevBuf d_chirp;                // w[n], n < N (where the fused kernel is legal: M entries, zero from N on)
     DevBuf d_H;                    // spectrum of the filter b in the inner setup's internal layout (real setups: of b_f, the forward one)
     DevBuf d_Hr;                   // real setups: spectrum of b_r, the backward filter (the index reversal of b_f)
@@ -36,11 +29,6 @@ struct AnySetup {
     int bins() const { return is_real ? N / 2 + 1 : N; }
 };
 
-static AnySetup* any_checked(const void* p) {
-    const AnySetup* a = static_cast<const AnySetup*>(p);
-    return a && a->magic == ANY_MAGIC ? const_cast<AnySetup*>(a) : nullptr;
-}
-
 // ------------------------------------------------------------------------------------------------ plan
 // The fused kernel exists for float and these convolution lengths (M2 = next power of two >= 2N - 1), and it is the default in all of
 // them: per vector it moves 2 N 8 bytes in one launch where the composed route moves 2 N 8 + 4 M 8 in three (the pad image written, read
@@ -48,60 +36,27 @@ static AnySetup* any_checked(const void* p) {
 // device; DESIGN.md §3.12 has the figures.
 static bool any_fused_len(int M) { return M == 512 || M == 1024 || M == 2048 || M == 4096; }
 
-// Composed route: the nearest legal size at or above 2N - 1 (M <= 2^26 for N <= 2^25)
-static int any_composed_len(int N) { return pffft_nearest_transform_size(2 * N - 1, PFFFT_COMPLEX, 1); }
-
-static AnySetup* any_new_setup(int N, int transform, int is_double) {
-    if (transform != PFFFT_COMPLEX || N < 1 || N > ANY_MAX_N) return nullptr;
+// Complex setups: k - n runs over [-(N-1), N-1], so the convolution needs M >= 2N - 1.  Real setups: the bins k < H = N/2 + 1 only, so
+// k - n runs over [-(N-1), N/2] and M >= N + N/2 suffices; the fused cells are then N = 172 ... 2731 (M2 = 512 ... 4096).  The composed
+// route takes the nearest legal size at or above that (M <= 2^26 for N <= 2^25); a setup that can run fused runs BOTH routes on M2, the
+// next power of two: one filter spectrum, one answer to pffft_hip_any_conv_size.
+static AnySetup* any_new_setup(int N, int transform, int is_double, int is_real) {
+    if (transform != (is_real ? PFFFT_REAL : PFFFT_COMPLEX) || N < 1 || N > ANY_MAX_N) return nullptr;
     std::unique_ptr<AnySetup> a(new AnySetup);
-    a->N = N; a->is_double = is_double;
+    a->N = N; a->is_real = is_real;
     int len = N;
-    if (pffft_is_valid_size(N, PFFFT_COMPLEX)) {
+    if (pffft_is_valid_size(N, (pffft_transform_t)transform)) {
         a->route = ANY_DIRECT;
     } else {
-        long long p2 = 16;
-        while (p2 < 2ll * N - 1) p2 *= 2;
-        const bool fused = !is_double && any_fused_len((int)p2);
-        // (a setup that can run fused runs BOTH routes on M2: one filter spectrum, one answer to pffft_hip_any_conv_size)
-        a->M = len = fused ? (int)p2 : any_composed_len(N);
-        a->route = fused ? ANY_FUSED : ANY_COMPOSED;
-    }
-    a->inner = is_double ? static_cast<Setup*>(pffftd_new_setup(len, PFFFT_COMPLEX)) : static_cast<Setup*>(pffft_new_setup(len, PFFFT_COMPLEX));
-    if (!a->inner) return nullptr;
-    return a.release();
-}
-
-// Real setups: the bins k < H = N/2 + 1 only, so k - n runs over [-(N-1), N/2] and M >= N + N/2 suffices.  The fused cells are then
-// N = 172 ... 2731 (M2 = 512 ... 4096); like the complex setup, one that can run fused uses M2 on both routes.
-static AnySetup* any_new_real_setup(int N, int is_double) {
-    if (N < 1 || N > ANY_MAX_N) return nullptr;
-    std::unique_ptr<AnySetup> a(new AnySetup);
-    a->N = N; a->is_double = is_double; a->is_real = 1;
-    int len = N, tr = PFFFT_REAL;
-    if (pffft_is_valid_size(N, PFFFT_REAL)) {
-        a->route = ANY_DIRECT;
-    } else {
-        const long long need = (long long)N + N / 2;
+        const long long need = is_real ? (long long)N + N / 2 : 2ll * N - 1;
         long long p2 = 16;
         while (p2 < need) p2 *= 2;
         const bool fused = !is_double && any_fused_len((int)p2);
         a->M = len = fused ? (int)p2 : pffft_nearest_transform_size((int)need, PFFFT_COMPLEX, 1);
         a->route = fused ? ANY_FUSED : ANY_COMPOSED;
-        tr = PFFFT_COMPLEX;
+        transform = PFFFT_COMPLEX;
     }
-    a->inner = is_double ? static_cast<Setup*>(pffftd_new_setup(len, (pffft_transform_t)tr)) : static_cast<Setup*>(pffft_new_setup(len, (pffft_transform_t)tr));
-    if (!a->inner) return nullptr;
-    return a.release();
-}
-
-static void any_destroy_setup(AnySetup* a) {
-    if (!a || a->magic != ANY_MAGIC) return;
-    a->magic = 0;
-    if (a->inner) {
-        if (a->is_double) pffftd_destroy_setup(static_cast<PFFFTD_Setup*>(a->inner));
-        else pffft_destroy_setup(static_cast<PFFFT_Setup*>(a->inner));
-    }
-    delete a;
+    return a->new_inner(len, transform, is_double) ? a.release() : nullptr;
 }
 
 // the route of a call under the calling thread's selector
@@ -161,21 +116,9 @@ static int any_build_tables(AnySetup* a) {
     return any_filter_spectrum<T>(a, b, a->d_Hr);
 }
 
-// first call: binds the setup to the current device and builds its tables (allocates and synchronises: not during a stream capture)
 template <typename T>
 static int any_ensure(AnySetup* a, hipStream_t st) {
-    int dev = -1;
-    PF_CHECK(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(a->mu);
-    if (a->ready) return a->device == dev ? 0 : bad("any: this setup holds its tables on another device (one setup serves one device)", hipErrorInvalidDevice);
-    if (stream_capturing(st))
-        return bad("any: the tables of this setup would have to be built during graph capture: run the call once before capturing",
-                   hipErrorStreamCaptureUnsupported);
-    if (a->route != ANY_DIRECT)
-        if (int rc = any_build_tables<T>(a)) return rc;
-    a->device = dev;
-    a->ready = true;
-    return 0;
+    return bind_device_once(a->bound, "any: ", st, [&] { return a->route != ANY_DIRECT ? any_build_tables<T>(a) : 0; });
 }
 
 // ------------------------------------------------------------------------------------------------ the two routes (bluestein_host.h)
@@ -195,13 +138,13 @@ static int any_composed(AnySetup* a, const T* in, T* out, size_t batch, int cj, 
     return bluestein_composed<T>(
         a->inner, a->pad, (const T*)a->d_H.as<T>(), M, batch, st,
         [&](cx<T>* X, size_t v0, size_t cnt) {
-            hipLaunchKernelGGL((any_pad_kernel<T>), dim3(bluestein_grid(cnt * M)), dim3(256), 0, st, reinterpret_cast<const cx<T>*>(in) + v0 * N, X,
+            hipLaunchKernelGGL((any_pad_kernel<T>), dim3(stream_grid(cnt * M)), dim3(256), 0, st, reinterpret_cast<const cx<T>*>(in) + v0 * N, X,
                                w, cnt, N, M, cj);
             PF_CHECK(hipGetLastError());
             return 0;
         },
         [&](cx<T>* X, size_t v0, size_t cnt) {
-            hipLaunchKernelGGL((any_crop_kernel<T>), dim3(bluestein_grid(cnt * N)), dim3(256), 0, st, (const cx<T>*)X,
+            hipLaunchKernelGGL((any_crop_kernel<T>), dim3(stream_grid(cnt * N)), dim3(256), 0, st, (const cx<T>*)X,
                                reinterpret_cast<cx<T>*>(out) + v0 * N, w, cnt, N, M, cj);
             PF_CHECK(hipGetLastError());
             return 0;
@@ -229,12 +172,12 @@ static int any_real_composed(AnySetup* a, const T* in, T* out, size_t batch, int
     return bluestein_composed<T>(
         a->inner, a->pad, (const T*)(back ? a->d_Hr : a->d_H).template as<T>(), M, batch, st,
         [&](cx<T>* X, size_t v0, size_t cnt) {
-            hipLaunchKernelGGL((any_real_pad_kernel<T>), dim3(bluestein_grid(cnt * M)), dim3(256), 0, st, in + v0 * rin, X, w, cnt, N, H, M, back);
+            hipLaunchKernelGGL((any_real_pad_kernel<T>), dim3(stream_grid(cnt * M)), dim3(256), 0, st, in + v0 * rin, X, w, cnt, N, H, M, back);
             PF_CHECK(hipGetLastError());
             return 0;
         },
         [&](cx<T>* X, size_t v0, size_t cnt) {
-            hipLaunchKernelGGL((any_real_crop_kernel<T>), dim3(bluestein_grid(cnt * (back ? N : H))), dim3(256), 0, st, (const cx<T>*)X,
+            hipLaunchKernelGGL((any_real_crop_kernel<T>), dim3(stream_grid(cnt * (back ? N : H))), dim3(256), 0, st, (const cx<T>*)X,
                                out + v0 * rout, w, cnt, N, H, M, back);
             PF_CHECK(hipGetLastError());
             return 0;
@@ -245,27 +188,20 @@ static int any_real_composed(AnySetup* a, const T* in, T* out, size_t batch, int
 template <typename T>
 static int any_real_direct(AnySetup* a, const T* in, T* out, size_t batch, int back, hipStream_t st) {
     const size_t N = (size_t)a->N, H = (size_t)a->bins();
-    const size_t chunk = std::max<size_t>(1, std::min(batch, BLUESTEIN_CAP_BYTES / (N * sizeof(T))));
-    std::lock_guard<std::mutex> lk(a->pad.mu);
-    void* p = nullptr;
-    int rc = scratch_buffer(a->pad, st, chunk * N * sizeof(T), "the scratch image", &p);
-    if (rc) return rc;
-    T* S = static_cast<T*>(p);
-    for (size_t v0 = 0; v0 < batch; v0 += chunk) {
-        const size_t cnt = std::min(batch - v0, chunk);
+    return chunked_scratch<T>(a->pad, st, batch, N * sizeof(T), "the scratch image", [&](T* S, size_t v0, size_t cnt) {
         if (!back) {
-            if ((rc = transform_batch_any(a->inner, in + v0 * N, S, cnt, PFFFT_FORWARD, 1, st))) return rc;
-            hipLaunchKernelGGL((any_real_unpack_kernel<T>), dim3(bluestein_grid(cnt * H)), dim3(256), 0, st, (const T*)S,
+            if (int rc = transform_batch_any(a->inner, in + v0 * N, S, cnt, PFFFT_FORWARD, 1, st)) return rc;
+            hipLaunchKernelGGL((any_real_unpack_kernel<T>), dim3(stream_grid(cnt * H)), dim3(256), 0, st, (const T*)S,
                                reinterpret_cast<cx<T>*>(out) + v0 * H, cnt, N);
             PF_CHECK(hipGetLastError());
         } else {
-            hipLaunchKernelGGL((any_real_pack_kernel<T>), dim3(bluestein_grid(cnt * H)), dim3(256), 0, st, reinterpret_cast<const cx<T>*>(in) + v0 * H, S,
+            hipLaunchKernelGGL((any_real_pack_kernel<T>), dim3(stream_grid(cnt * H)), dim3(256), 0, st, reinterpret_cast<const cx<T>*>(in) + v0 * H, S,
                                cnt, N);
             PF_CHECK(hipGetLastError());
-            if ((rc = transform_batch_any(a->inner, S, out + v0 * N, cnt, PFFFT_BACKWARD, 1, st))) return rc;
+            return transform_batch_any(a->inner, S, out + v0 * N, cnt, PFFFT_BACKWARD, 1, st);
         }
-    }
-    return 0;
+        return 0;
+    });
 }
 
 template <typename T>
@@ -288,11 +224,8 @@ static int any_real_transform_batch(AnySetup* a, const T* in, T* out, size_t bat
 // ------------------------------------------------------------------------------------------------ the entry
 template <typename T>
 static int any_transform_batch(void* setup, const T* in, T* out, size_t batch, int dir, hipStream_t st) {
-    AnySetup* a = any_checked(setup);
-    if (!a || a->is_double != (sizeof(T) == 8)) {
-        g_last_error = "pffft_hip: bad any-length setup handle";
-        return (int)hipErrorInvalidHandle;
-    }
+    AnySetup* a = typed_handle<AnySetup, T>(setup);
+    if (!a) return (int)hipErrorInvalidHandle;
     if (dir != PFFFT_FORWARD && dir != PFFFT_BACKWARD) return bad("any: bad direction");
     if (batch && (!in || !out)) return bad("any: NULL in / out");
     if (a->is_real) return any_real_transform_batch<T>(a, in, out, batch, dir, st);
@@ -313,15 +246,19 @@ static int any_transform_batch(void* setup, const T* in, T* out, size_t batch, i
 }  // namespace pf
 
 PF_EXPORT PFFFT_HIP_AnySetup* pffft_hip_any_new_setup(int N, pffft_transform_t tr) {
-    return reinterpret_cast<PFFFT_HIP_AnySetup*>(pf::any_new_setup(N, (int)tr, 0));
+    return reinterpret_cast<PFFFT_HIP_AnySetup*>(pf::any_new_setup(N, (int)tr, 0, 0));
 }
 PF_EXPORT PFFFTD_HIP_AnySetup* pffftd_hip_any_new_setup(int N, pffft_transform_t tr) {
-    return reinterpret_cast<PFFFTD_HIP_AnySetup*>(pf::any_new_setup(N, (int)tr, 1));
+    return reinterpret_cast<PFFFTD_HIP_AnySetup*>(pf::any_new_setup(N, (int)tr, 1, 0));
 }
-PF_EXPORT PFFFT_HIP_AnySetup* pffft_hip_any_new_real_setup(int N) { return reinterpret_cast<PFFFT_HIP_AnySetup*>(pf::any_new_real_setup(N, 0)); }
-PF_EXPORT PFFFTD_HIP_AnySetup* pffftd_hip_any_new_real_setup(int N) { return reinterpret_cast<PFFFTD_HIP_AnySetup*>(pf::any_new_real_setup(N, 1)); }
-PF_EXPORT void pffft_hip_any_destroy_setup(PFFFT_HIP_AnySetup* s) { pf::any_destroy_setup(reinterpret_cast<pf::AnySetup*>(s)); }
-PF_EXPORT void pffftd_hip_any_destroy_setup(PFFFTD_HIP_AnySetup* s) { pf::any_destroy_setup(reinterpret_cast<pf::AnySetup*>(s)); }
+PF_EXPORT PFFFT_HIP_AnySetup* pffft_hip_any_new_real_setup(int N) {
+    return reinterpret_cast<PFFFT_HIP_AnySetup*>(pf::any_new_setup(N, PFFFT_REAL, 0, 1));
+}
+PF_EXPORT PFFFTD_HIP_AnySetup* pffftd_hip_any_new_real_setup(int N) {
+    return reinterpret_cast<PFFFTD_HIP_AnySetup*>(pf::any_new_setup(N, PFFFT_REAL, 1, 1));
+}
+PF_EXPORT void pffft_hip_any_destroy_setup(PFFFT_HIP_AnySetup* s) { pf::destroy_handle<pf::AnySetup>(s); }
+PF_EXPORT void pffftd_hip_any_destroy_setup(PFFFTD_HIP_AnySetup* s) { pf::destroy_handle<pf::AnySetup>(s); }
 PF_EXPORT int pffft_hip_any_transform_batch(PFFFT_HIP_AnySetup* s, const float* in, float* out, size_t batch, pffft_direction_t d, void* stream) {
     return pf::any_transform_batch<float>(s, in, out, batch, (int)d, (hipStream_t)stream);
 }
@@ -330,19 +267,19 @@ PF_EXPORT int pffftd_hip_any_transform_batch(PFFFTD_HIP_AnySetup* s, const doubl
     return pf::any_transform_batch<double>(s, in, out, batch, (int)d, (hipStream_t)stream);
 }
 PF_EXPORT int pffft_hip_any_conv_size(const void* setup) {
-    const pf::AnySetup* a = pf::any_checked(setup);
+    const pf::AnySetup* a = pf::checked_handle<pf::AnySetup>(setup);
     return a ? a->M : -1;
 }
 PF_EXPORT int pffft_hip_any_is_real(const void* setup) {
-    const pf::AnySetup* a = pf::any_checked(setup);
+    const pf::AnySetup* a = pf::checked_handle<pf::AnySetup>(setup);
     return a ? a->is_real : -1;
 }
 PF_EXPORT int pffft_hip_any_bins(const void* setup) {
-    const pf::AnySetup* a = pf::any_checked(setup);
+    const pf::AnySetup* a = pf::checked_handle<pf::AnySetup>(setup);
     return a ? a->bins() : -1;
 }
 PF_EXPORT const char* pffft_hip_any_route(const void* setup) {
-    const pf::AnySetup* a = pf::any_checked(setup);
+    const pf::AnySetup* a = pf::checked_handle<pf::AnySetup>(setup);
     if (!a) return "";
     switch (pf::any_route_now(a, pf::ab())) {
         case pf::ANY_DIRECT: return "direct";
@@ -351,7 +288,7 @@ PF_EXPORT const char* pffft_hip_any_route(const void* setup) {
     }
 }
 PF_EXPORT int pffft_hip_any_chirp(const void* setup, void* host_out) {
-    const pf::AnySetup* a = pf::any_checked(setup);
+    const pf::AnySetup* a = pf::checked_handle<pf::AnySetup>(setup);
     if (!a || !host_out) { pf::g_last_error = "pffft_hip: bad any-length setup handle / NULL output"; return (int)hipErrorInvalidValue; }
     const unsigned long long N = (unsigned long long)a->N;
     if (a->is_double) {

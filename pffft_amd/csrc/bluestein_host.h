@@ -1,12 +1,11 @@
 // Host code shared by the translation units that run Bluestein's algorithm on the library's own convolution (any_tu.hip, zoom_tu.hip):
 // the handle types of the inner setups, the spectrum of the fixed filter, the launch of fft_conv_kernel with a loader / store policy
-// (the fused route) and the pad -> convolve_batch -> crop sequence through a per-stream scratch image (the composed route).
+// (the fused route) and the pad -> convolve_batch -> crop sequence through a per-stream scratch image (the composed route).  The handle
+// base, the slices and the chunked scratch are pf_compose.h's.
 #pragma once
-#include <algorithm>
 #include <vector>
 
-#include "../../include/pffft_hip.h"
-#include "pf_launch.h"
+#include "pf_compose.h"
 #include "fft_conv.h"
 
 namespace pf {
@@ -54,8 +53,6 @@ static int bluestein_filter_spectrum(Setup* inner, size_t M, std::vector<cx<doub
 }
 
 // ------------------------------------------------------------------------------------------------ the fused route
-template <class C> struct CfgTag { typedef C type; };
-
 // fft_conv_kernel<C, 0, IO> on `batch` rows under the launch rule of the convolution kernel (conv_tu.hip); `s` is the resolved inner
 // setup of length M, H the filter spectrum in its internal layout
 template <class C, class IO>
@@ -70,8 +67,8 @@ static int bluestein_fused_launch(Setup* s, const IO& io, const float* H, size_t
 }
 
 // The fused route of a float setup whose convolution length M is one of the fused lengths: the inner setup must hold its tables on the
-// calling thread's device; the batch goes out in slices on the same stream (the kernel counts rows in 32 bits).  launch(CfgTag<C>(),
-// first row, rows) forms the policy object of that slice and calls bluestein_fused_launch<C>.
+// calling thread's device; the batch goes out in slices on the same stream (for_slices).  launch(CfgTag<C>(), first row, rows) forms the
+// policy object of that slice and calls bluestein_fused_launch<C>.
 template <class F>
 static int bluestein_fused(Setup* inner, int M, size_t batch, F&& launch) {
     typedef ConvPick<float> P;
@@ -82,54 +79,33 @@ static int bluestein_fused(Setup* inner, int M, size_t batch, F&& launch) {
     }
     int rc = ensure_device_any(s);
     if (rc) return rc;
-    constexpr size_t SLICE = (size_t)3 << 30;
-    for (size_t b0 = 0; b0 < batch; b0 += SLICE) {
-        const size_t nb = std::min(batch - b0, SLICE);
+    return for_slices(batch, [&](size_t b0, size_t nb) {
         switch (M) {
-            case 512: rc = launch(CfgTag<P::C512>(), b0, nb); break;
-            case 1024: rc = launch(CfgTag<P::C1024>(), b0, nb); break;
-            case 2048: rc = launch(CfgTag<P::C2048>(), b0, nb); break;
-            case 4096: rc = launch(CfgTag<P::C4096>(), b0, nb); break;
-            default:
-                g_last_error = "pffft_hip: no fused kernel for this convolution length";
-                return (int)hipErrorInvalidValue;
+            case 512: return launch(CfgTag<P::C512>(), b0, nb);
+            case 1024: return launch(CfgTag<P::C1024>(), b0, nb);
+            case 2048: return launch(CfgTag<P::C2048>(), b0, nb);
+            case 4096: return launch(CfgTag<P::C4096>(), b0, nb);
+            default: return bad("no fused kernel for this convolution length");
         }
-        if (rc) return rc;
-    }
-    return 0;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------ the composed route
-constexpr size_t BLUESTEIN_CAP_BYTES = (size_t)256 << 20;   // the scratch image of one launch sequence; longer batches go in chunks
-
 // pad kernel -> pffft[d]_hip_convolve_batch on `inner` (length M, one broadcast filter spectrum H, scaled by 1 / M) -> crop kernel, in
-// chunks of at most 256 MiB of scratch (one row where a row is longer).  pad_k(X, first row, rows) and crop_k(X, first row, rows) launch
-// the two ends on `st` and return 0 or an error.
+// chunks of at most SCRATCH_CAP_BYTES of scratch (one row where a row is longer).  pad_k(X, first row, rows) and crop_k(X, first row, rows)
+// launch the two ends on `st` and return 0 or an error.
 template <typename T, class PadK, class CropK>
 static int bluestein_composed(Setup* inner, StreamScratch& pad, const T* H, size_t M, size_t batch, hipStream_t st, PadK&& pad_k, CropK&& crop_k) {
-    const size_t chunk = std::max<size_t>(1, std::min(batch, BLUESTEIN_CAP_BYTES / (M * sizeof(cx<T>))));
-    std::lock_guard<std::mutex> lk(pad.mu);
-    void* p = nullptr;
-    int rc = scratch_buffer(pad, st, chunk * M * sizeof(cx<T>), "the scratch image", &p);
-    if (rc) return rc;
-    cx<T>* X = static_cast<cx<T>*>(p);
     const T scaling = (T)1 / (T)M;
-    for (size_t v0 = 0; v0 < batch; v0 += chunk) {
-        const size_t cnt = std::min(batch - v0, chunk);
-        if ((rc = pad_k(X, v0, cnt))) return rc;
+    return chunked_scratch<cx<T>>(pad, st, batch, M * sizeof(cx<T>), "the scratch image", [&](cx<T>* X, size_t v0, size_t cnt) {
+        int rc = pad_k(X, v0, cnt);
+        if (rc) return rc;
         if constexpr (sizeof(T) == 8)
             rc = pffftd_hip_convolve_batch(static_cast<PFFFTD_Setup*>(inner), (const double*)X, H, (double*)X, scaling, cnt, 0, 1, st);
         else
             rc = pffft_hip_convolve_batch(static_cast<PFFFT_Setup*>(inner), (const float*)X, H, (float*)X, scaling, cnt, 0, 1, st);
-        if (rc) return rc;
-        if ((rc = crop_k(X, v0, cnt))) return rc;
-    }
-    return 0;
-}
-
-// grid of the grid-stride pad / crop kernels (256 threads)
-static unsigned bluestein_grid(size_t items) {
-    return (unsigned)std::max<size_t>(1, std::min<size_t>((items + 255) / 256, (size_t)num_cus() * 16));
+        return rc ? rc : crop_k(X, v0, cnt);
+    });
 }
 
 }  // namespace pf

@@ -1,35 +1,24 @@
 // libpffft_hip.so, translation unit of the cosine / sine transforms (include/pffft_hip.h: pffft[d]_hip_dct_*): types II and III by
 // Makhoul's algorithm on ONE real transform of the same length.  The handle owns an ordinary real setup of N and the folded table t_k;
 // the fused kernel's instantiations and launch, and the composed route through a per-stream scratch image.  Kernels: fft_dct.h.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
 #include <cmath>
 #include <memory>
 
-#include "../../include/pffft_hip.h"
-#include "pf_launch.h"
+#include "pf_compose.h"
 #include "fft_dct.h"
 
 namespace pf {
 
 constexpr uint32_t DCT_MAGIC = 0x50464443u;   // "PFDC"
-constexpr size_t DCT_CAP_BYTES = (size_t)256 << 20;   // the scratch image of one launch sequence; longer batches go in chunks
 
-struct DctSetup {
-    uint32_t magic = DCT_MAGIC;
-    int N = 0, kind = 0, norm = 0, is_double = 0;
-    Setup* inner = nullptr;        // a real PFFFT_Setup / PFFFTD_Setup of N, owned
+struct DctSetup : InnerOwner<DCT_MAGIC> {   // the owned inner setup: a real one of N
+    static constexpr const char* KIND = "dct";
+    int N = 0, kind = 0, norm = 0;
     std::mutex mu;                 // guards the lazy tables
     // t_k, k = 0 ... N/2, per object that holds the inner setup's device state (for_device): one table per device the setup is used on
     std::map<const Setup*, DevBuf> d_tab;
     StreamScratch scratch;         // batch x N image of the composed route: one per stream, scratch.mu held while a call enqueues
 };
-
-static DctSetup* dct_checked(const void* p) {
-    const DctSetup* z = static_cast<const DctSetup*>(p);
-    return z && z->magic == DCT_MAGIC ? const_cast<DctSetup*>(z) : nullptr;
-}
 
 // ------------------------------------------------------------------------------------------------ the folded table
 // t_k = 2 s_k w_k (type II) / s'_k conj(w_k) (type III), w_k = exp(-j pi k / 2N) = W_{4N}^k; norm none: s = s' = 1; ortho:
@@ -75,21 +64,14 @@ static DctSel dct_sel(int kind) {
     return e;
 }
 
-// The configuration the fused kernel runs on must be the one transform_batch runs on for the same direction in the canonical layout - the
-// results are equal bit for bit only then -, so it is read from the inner setup's stored route: real float on TiledPick C512 / C1024 /
-// C2048 (N = 1024 / 2048 / 4096), forward for type II, backward for type III.  Everything else has no fused kernel.
+// The fused kernel runs on the configuration of the inner setup's route in the canonical layout (visit_tiled_cfg), forward for type II,
+// backward for type III.  Everything else has no fused kernel.
 static const Route& dct_route(const Setup* s, int kind) { return s->route[dct_type3(kind) ? PFFFT_BACKWARD : PFFFT_FORWARD][1]; }
 
 static bool dct_fusable(const DctSetup* z, DctSel* e) {
-    const Setup* s = z->inner;
-    if (s->is_double || s->kernel != K_TILED) return false;
-    const Route& r = dct_route(s, z->kind);
-    if (r.fam != FAM_TILED) return false;
-    const std::string cfg = r.tiled.cfg;
-    if (s->n == 512 && cfg == "TiledPick::C512") { if (e) *e = dct_sel<TiledPick<float>::C512>(z->kind); return true; }
-    if (s->n == 1024 && cfg == "TiledPick::C1024") { if (e) *e = dct_sel<TiledPick<float>::C1024>(z->kind); return true; }
-    if (s->n == 2048 && cfg == "TiledPick::C2048") { if (e) *e = dct_sel<TiledPick<float>::C2048>(z->kind); return true; }
-    return false;
+    return visit_tiled_cfg(z->inner, dct_route(z->inner, z->kind), [&](auto tag) {
+        if (e) *e = dct_sel<typename decltype(tag)::type>(z->kind);
+    });
 }
 
 // (size, kind) cells where the fused kernel is the default: a cell is in it where tools/dct_bench.py holds the fused kernel faster than
@@ -109,20 +91,8 @@ static DctSetup* dct_new_setup(int N, int kind, int norm, int is_double) {
     if (N < 1 || kind < PFFFT_HIP_DCT2 || kind > PFFFT_HIP_DST3 || (norm != PFFFT_HIP_DCT_NORM_NONE && norm != PFFFT_HIP_DCT_NORM_ORTHO))
         return nullptr;
     std::unique_ptr<DctSetup> z(new DctSetup);
-    z->N = N; z->kind = kind; z->norm = norm; z->is_double = is_double;
-    z->inner = is_double ? static_cast<Setup*>(pffftd_new_setup(N, PFFFT_REAL)) : static_cast<Setup*>(pffft_new_setup(N, PFFFT_REAL));
-    if (!z->inner) return nullptr;
-    return z.release();
-}
-
-static void dct_destroy_setup(DctSetup* z) {
-    if (!z || z->magic != DCT_MAGIC) return;
-    z->magic = 0;
-    if (z->inner) {
-        if (z->is_double) pffftd_destroy_setup(static_cast<PFFFTD_Setup*>(z->inner));
-        else pffft_destroy_setup(static_cast<PFFFT_Setup*>(z->inner));
-    }
-    delete z;
+    z->N = N; z->kind = kind; z->norm = norm;
+    return z->new_inner(N, PFFFT_REAL, is_double) ? z.release() : nullptr;
 }
 
 // ------------------------------------------------------------------------------------------------ the two routes
@@ -131,42 +101,29 @@ static int dct_fused(Setup* s, const DctSel& e, int oneshot, const float* in, fl
     size_t resident = 0;
     if (int rc = loop_resident(e.fn, e.wg, e.lds, &resident)) return rc;
     const size_t N = (size_t)s->N;
-    constexpr size_t SLICE = (size_t)3 << 30;   // (the kernel counts rows in 32 bits: longer batches go out in slices on the stream)
-    for (size_t b0 = 0; b0 < batch; b0 += SLICE) {
-        const size_t nb = std::min(batch - b0, SLICE);
+    return for_slices(batch, [&](size_t b0, size_t nb) {
         const LoopLaunch ll = loop_take(s, st, resident, (nb + e.t_per_wg - 1) / e.t_per_wg, oneshot);
         hipLaunchKernelGGL(e.fn, dim3(ll.grid), dim3(e.wg), e.lds, st, in + b0 * N, out + b0 * N, (unsigned)nb, tab,
                            s->d_tw.as<cx<float>>(), s->d_twr.as<cx<float>>(), ll.ctr);
         PF_CHECK(hipGetLastError());
-    }
-    return 0;
-}
-
-static unsigned dct_grid(size_t items) {
-    return (unsigned)std::max<size_t>(1, std::min<size_t>((items + 255) / 256, (size_t)num_cus() * 16));
+        return 0;
+    });
 }
 
 template <typename T, int KIND>
 static int dct_composed_kind(DctSetup* z, Setup* s, const T* in, T* out, size_t batch, const cx<T>* tab, hipStream_t st) {
     constexpr bool III = dct_type3(KIND);
     const size_t N = (size_t)z->N;
-    const size_t chunk = std::max<size_t>(1, std::min(batch, DCT_CAP_BYTES / (N * sizeof(T))));
-    std::lock_guard<std::mutex> lk(z->scratch.mu);
-    void* buf = nullptr;
-    int rc = scratch_buffer(z->scratch, st, chunk * N * sizeof(T), "dct: the scratch image", &buf);
-    if (rc) return rc;
-    T* X = static_cast<T*>(buf);
-    for (size_t v0 = 0; v0 < batch; v0 += chunk) {
-        const size_t cnt = std::min(batch - v0, chunk);
-        hipLaunchKernelGGL((dct_pre_kernel<T, KIND>), dim3(dct_grid(cnt * (III ? N / 8 : N / 4))), dim3(256), 0, st, in + v0 * N, X, tab, cnt,
+    return chunked_scratch<T>(z->scratch, st, batch, N * sizeof(T), "dct: the scratch image", [&](T* X, size_t v0, size_t cnt) {
+        hipLaunchKernelGGL((dct_pre_kernel<T, KIND>), dim3(stream_grid(cnt * (III ? N / 8 : N / 4))), dim3(256), 0, st, in + v0 * N, X, tab, cnt,
                            (unsigned)N);
         PF_CHECK(hipGetLastError());
-        if ((rc = transform_batch_any(s, X, X, cnt, III ? PFFFT_BACKWARD : PFFFT_FORWARD, 1, st))) return rc;
-        hipLaunchKernelGGL((dct_post_kernel<T, KIND>), dim3(dct_grid(cnt * (III ? N / 4 : N / 8))), dim3(256), 0, st, (const T*)X, out + v0 * N,
+        if (int rc = transform_batch_any(s, X, X, cnt, III ? PFFFT_BACKWARD : PFFFT_FORWARD, 1, st)) return rc;
+        hipLaunchKernelGGL((dct_post_kernel<T, KIND>), dim3(stream_grid(cnt * (III ? N / 4 : N / 8))), dim3(256), 0, st, (const T*)X, out + v0 * N,
                            tab, cnt, (unsigned)N);
         PF_CHECK(hipGetLastError());
-    }
-    return 0;
+        return 0;
+    });
 }
 
 template <typename T>
@@ -182,11 +139,8 @@ static int dct_composed(DctSetup* z, Setup* s, const T* in, T* out, size_t batch
 // ------------------------------------------------------------------------------------------------ the entry
 template <typename T>
 static int dct_transform_batch(void* setup, const T* in, T* out, size_t batch, hipStream_t st) {
-    DctSetup* z = dct_checked(setup);
-    if (!z || z->is_double != (sizeof(T) == 8)) {
-        g_last_error = "pffft_hip: bad dct setup handle";
-        return (int)hipErrorInvalidHandle;
-    }
+    DctSetup* z = typed_handle<DctSetup, T>(setup);
+    if (!z) return (int)hipErrorInvalidHandle;
     if (batch == 0) return 0;
     if (!in || !out) return bad("dct: NULL in / out");
     if (((uintptr_t)in | (uintptr_t)out) & 15) return bad("dct: in / out not aligned to 16 bytes");
@@ -214,8 +168,8 @@ PF_EXPORT PFFFT_HIP_DctSetup* pffft_hip_dct_new_setup(int N, pffft_hip_dct_kind_
 PF_EXPORT PFFFTD_HIP_DctSetup* pffftd_hip_dct_new_setup(int N, pffft_hip_dct_kind_t kind, pffft_hip_dct_norm_t norm) {
     return reinterpret_cast<PFFFTD_HIP_DctSetup*>(pf::dct_new_setup(N, (int)kind, (int)norm, 1));
 }
-PF_EXPORT void pffft_hip_dct_destroy_setup(PFFFT_HIP_DctSetup* s) { pf::dct_destroy_setup(reinterpret_cast<pf::DctSetup*>(s)); }
-PF_EXPORT void pffftd_hip_dct_destroy_setup(PFFFTD_HIP_DctSetup* s) { pf::dct_destroy_setup(reinterpret_cast<pf::DctSetup*>(s)); }
+PF_EXPORT void pffft_hip_dct_destroy_setup(PFFFT_HIP_DctSetup* s) { pf::destroy_handle<pf::DctSetup>(s); }
+PF_EXPORT void pffftd_hip_dct_destroy_setup(PFFFTD_HIP_DctSetup* s) { pf::destroy_handle<pf::DctSetup>(s); }
 PF_EXPORT int pffft_hip_dct_transform_batch(PFFFT_HIP_DctSetup* s, const float* in, float* out, size_t batch, void* stream) {
     return pf::dct_transform_batch<float>(s, in, out, batch, (hipStream_t)stream);
 }
@@ -223,12 +177,12 @@ PF_EXPORT int pffftd_hip_dct_transform_batch(PFFFTD_HIP_DctSetup* s, const doubl
     return pf::dct_transform_batch<double>(s, in, out, batch, (hipStream_t)stream);
 }
 PF_EXPORT const char* pffft_hip_dct_route(const void* setup) {
-    const pf::DctSetup* z = pf::dct_checked(setup);
+    const pf::DctSetup* z = pf::checked_handle<pf::DctSetup>(setup);
     if (!z) return "";
     return pf::dct_fused_now(z, pf::ab()) ? "fused" : "composed";
 }
 PF_EXPORT int pffft_hip_dct_table(const void* setup, size_t first, size_t count, void* host_out) {
-    const pf::DctSetup* z = pf::dct_checked(setup);
+    const pf::DctSetup* z = pf::checked_handle<pf::DctSetup>(setup);
     if (!z || !host_out) {
         pf::g_last_error = "pffft_hip: bad dct setup handle / NULL output";
         return (int)hipErrorInvalidValue;

@@ -1,0 +1,305 @@
+// The one host path of the entries that are COMPOSED on top of pf::Setup (frames_tu.hip, psd_tu.hip, pfb_tu.hip, any_tu.hip,
+// zoom_tu.hip, dct_tu.hip): how much scratch one launch sequence may hold, how a batch walks through it, how a fused launch is cut into
+// slices, the frame-matrix routes of analysis and synthesis, the lookup of the register-tiled configuration a fused kernel must share
+// with transform_batch, and the handle that owns an inner setup.  Every decision is written here once; each unit keeps its validation
+// texts, its route decision and its own typed kernel launches.  Every function is internal to the unit that includes it.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "../../include/pffft_hip.h"
+#include "pf_launch.h"
+#include "fft_frames.h"
+
+namespace pf {
+
+// ------------------------------------------------------------------------------------------------ planners, on plain integers
+// The scratch of one composed launch sequence (frame matrix, partial buffer, scratch image) holds at most this many bytes
+// (include/pffft_hip.h): longer batches go through it in chunks on the stream.
+constexpr size_t SCRATCH_CAP_BYTES = (size_t)256 << 20;
+// The fused kernels count rows in 32 bits: longer batches go out in slices of this many rows on the same stream.
+constexpr size_t ROW_SLICE = (size_t)3 << 30;
+
+// rows that fit under the cap: one where a single row is longer
+constexpr size_t cap_rows(size_t row_bytes, size_t cap = SCRATCH_CAP_BYTES) { return cap / row_bytes > 1 ? cap / row_bytes : 1; }
+// rows per chunk of a batch that goes through the scratch
+constexpr size_t chunk_rows(size_t batch, size_t row_bytes, size_t cap = SCRATCH_CAP_BYTES) {
+    return batch < 1 ? 1 : batch < cap_rows(row_bytes, cap) ? batch : cap_rows(row_bytes, cap);
+}
+static_assert(chunk_rows(100, 16384) == 100, "a batch under the cap: one chunk");
+static_assert(chunk_rows(20000, 16384) == 16384, "real float N = 4096: 16384 rows per chunk");
+static_assert(chunk_rows(5, SCRATCH_CAP_BYTES + 1) == 1, "a row longer than the cap goes alone");
+static_assert(chunk_rows(5, SCRATCH_CAP_BYTES / 2) == 2 && chunk_rows(5, SCRATCH_CAP_BYTES / 2 + 1) == 1, "both sides of an exact division");
+
+// body(first row, rows) -> 0 or an error, for consecutive slices of at most ROW_SLICE rows
+template <class Body>
+constexpr int for_slices(size_t rows, Body&& body) {
+    for (size_t b0 = 0; b0 < rows; b0 += ROW_SLICE)
+        if (int rc = body(b0, rows - b0 < ROW_SLICE ? rows - b0 : ROW_SLICE)) return rc;
+    return 0;
+}
+struct SliceWalk { size_t count, last; };
+constexpr SliceWalk slice_walk(size_t rows) {
+    SliceWalk w{0, 0};
+    for_slices(rows, [&](size_t, size_t nb) { ++w.count; w.last = nb; return 0; });
+    return w;
+}
+static_assert(slice_walk(ROW_SLICE).count == 1 && slice_walk(ROW_SLICE).last == ROW_SLICE, "3 x 2^30 rows: one slice");
+static_assert(slice_walk(ROW_SLICE + 1).count == 2 && slice_walk(ROW_SLICE + 1).last == 1, "one row more: a second slice of that row");
+
+// Synthesis beyond the cap goes signal by signal in runs of frames.  A run owns the samples from its first frame's start to the next
+// run's first frame's start (the last run: to the end) and re-transforms the `reach` earlier frames that reach into them, so the matrix
+// holds run + reach rows.  min_run is 0 for the frame entry: reach = ceil(N / hop) - 1 is small against any cap, and a run of one frame is
+// correct.  The filter bank passes min_run = reach = ceil(taps N / hop) - 1, which grows with the taps: a run is then at least `reach` frames
+// long, so that the re-transformed frames never outnumber the new ones, and where reach + 1 rows do not fit under the cap the matrix is
+// as large as that takes (at most 2 reach rows).
+constexpr size_t synth_reach(size_t span, size_t hop) { return (span + hop - 1) / hop - 1; }
+struct RunPlan { size_t run, buffer_rows; };
+constexpr RunPlan synth_plan(size_t nframes, size_t cap_rows_, size_t reach, size_t min_run) {
+    size_t run = cap_rows_ > reach ? cap_rows_ - reach : 1;
+    if (run < min_run) run = min_run;
+    if (run < 1) run = 1;
+    return {run, nframes < run + reach ? nframes : run + reach};
+}
+static_assert(cap_rows(4096 * 4) == 16384 && synth_reach(4096, 1024) == 3 && synth_reach(4 * 4096, 1024) == 15, "real float N = 4096, hop 1024");
+static_assert(synth_plan(20000, 16384, 3, 0).run == 16381 && synth_plan(20000, 16384, 3, 0).buffer_rows == 16384, "... 20 000 frames");
+static_assert(synth_plan(20000, 16384, 15, 15).run == 16369 && synth_plan(20000, 16384, 15, 15).buffer_rows == 16384, "... and taps 4");
+static_assert(synth_plan(100, 2, 5, 0).run == 1 && synth_plan(100, 2, 5, 0).buffer_rows == 6, "cap <= reach, frames: one new frame per run");
+static_assert(synth_plan(100, 2, 5, 5).run == 5 && synth_plan(100, 2, 5, 5).buffer_rows == 10, "cap <= reach, filter bank: 2 reach rows");
+
+// ------------------------------------------------------------------------------------------------ shared launches
+inline int bad_in(const char* prefix, const char* what, hipError_t e = hipErrorInvalidValue) {
+    return bad((std::string(prefix) + what).c_str(), e);
+}
+
+// grid of a grid-stride kernel of 256 threads over `items`
+static unsigned stream_grid(size_t items) {
+    return (unsigned)std::max<size_t>(1, std::min<size_t>((items + 255) / 256, (size_t)num_cus() * 16));
+}
+
+// `batch` rows through the buffer of `st` in `pool`, chunk_rows at a time: body(X, first row, rows) enqueues one chunk and returns 0 or
+// an error.  pool.mu is held until the last chunk is enqueued; `what` names the buffer in the capture refusal ("the frame matrix").
+template <typename X, class Body>
+static int chunked_scratch(StreamScratch& pool, hipStream_t st, size_t batch, size_t row_bytes, const char* what, Body&& body) {
+    const size_t chunk = chunk_rows(batch, row_bytes);
+    std::lock_guard<std::mutex> lk(pool.mu);
+    void* p = nullptr;
+    if (int rc = scratch_buffer(pool, st, chunk * row_bytes, what, &p)) return rc;
+    for (size_t v0 = 0; v0 < batch; v0 += chunk)
+        if (int rc = body(static_cast<X*>(p), v0, std::min(batch - v0, chunk))) return rc;
+    return 0;
+}
+
+template <typename T, int MODE>
+static int launch_rows(const T* src, size_t src_stride, T* dst, size_t dst_stride, size_t count, size_t row, hipStream_t st) {
+    const size_t per = MODE == 0 ? row : MODE == 1 ? row / 2 + 1 : row / 2;
+    hipLaunchKernelGGL((frames_rows_kernel<T, MODE>), dim3(stream_grid(count * per)), dim3(256), 0, st, src, src_stride, dst, dst_stride,
+                       count, (unsigned)row);
+    PF_CHECK(hipGetLastError());
+    return 0;
+}
+
+// dense spectra rows of X -> out: copied (ordered / internal) or as |X|^2 of a real / complex spectrum
+template <typename T>
+static int store_rows(bool power, bool real, const T* X, size_t row, T* dst, size_t dst_stride, size_t count, hipStream_t st) {
+    if (!power) return launch_rows<T, 0>(X, row, dst, dst_stride, count, row, st);
+    return real ? launch_rows<T, 1>(X, row, dst, dst_stride, count, row, st) : launch_rows<T, 2>(X, row, dst, dst_stride, count, row, st);
+}
+
+// frames v0 ... v0 + cnt - 1 (numbered i nframes + f) x window -> rows of X: 16 bytes at a time where signal, stride and hop allow
+template <typename T>
+static int launch_gather(const T* signal, size_t signal_stride, size_t nframes, size_t hop_s, size_t spp, const T* window, T* X, size_t v0,
+                         size_t cnt, size_t row, hipStream_t st) {
+    constexpr int U = 16 / (int)sizeof(T);
+    if (aligned16(signal) && signal_stride % U == 0 && hop_s % U == 0)
+        hipLaunchKernelGGL((frames_gather_kernel<T, U>), dim3(stream_grid(cnt * row / U)), dim3(256), 0, st, signal, signal_stride, nframes,
+                           hop_s, (int)spp, window, X, v0, cnt, (unsigned)row);
+    else
+        hipLaunchKernelGGL((frames_gather_kernel<T, 1>), dim3(stream_grid(cnt * row)), dim3(256), 0, st, signal, signal_stride, nframes,
+                           hop_s, (int)spp, window, X, v0, cnt, (unsigned)row);
+    PF_CHECK(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ analysis (frames, pfb, psd)
+struct FrameDims { bool real; size_t spp, N, row, out_row; };   // out_row: scalars of one output row (|X|^2: N/2 + 1 real, N complex)
+static FrameDims frame_dims(const Setup* s, int output) {
+    const bool real = s->transform == PFFFT_REAL;
+    const size_t N = (size_t)s->N;
+    return {real, real ? (size_t)1 : 2, N, s->vec_scalars, output == FR_POWER ? (real ? N / 2 + 1 : N) : s->vec_scalars};
+}
+
+// What the three analysis entries check and derive alike, in their order; `prefix` ("frames: ") opens every text.  `taps`: the filter
+// bank's, with its prototype (NULL: frames of N samples).  `navg`: the PSD entry's, 0 read as nframes.  Returns ARGS_EMPTY for a call
+// without frames (the entry returns 0), else 0 or the refusal; signal_stride and out_stride come back normalised.
+constexpr int ARGS_EMPTY = -1;
+struct AnalysisArgs : FrameDims { size_t hop_s, batch; };
+template <typename T>
+static int analysis_args(const char* prefix, const Setup* s, const T* signal, size_t* signal_stride, size_t nsignals, size_t nframes,
+                         size_t hop, const T* out, size_t* out_stride, int output, AnalysisArgs* a, const size_t* taps = nullptr,
+                         const T* prototype = nullptr, size_t* navg = nullptr) {
+    if (int rc = check_setup<T>(s)) return rc;
+    if (hop == 0) return bad_in(prefix, "hop == 0");
+    if (taps && *taps == 0) return bad_in(prefix, "taps == 0");
+    if (taps && !prototype) return bad_in(prefix, "NULL prototype");
+    if (output != FR_INTERNAL && output != FR_ORDERED && output != FR_POWER) return bad_in(prefix, "unknown output");
+    if (nsignals == 0 || nframes == 0) return ARGS_EMPTY;
+    if (navg) {
+        if (*navg == 0) *navg = nframes;
+        if (nframes % *navg) return bad_in(prefix, "nframes is no multiple of navg");
+    }
+    static_cast<FrameDims&>(*a) = frame_dims(s, output);
+    if (*out_stride == 0) *out_stride = a->out_row;
+    if (*out_stride < a->out_row) return bad_in(prefix, "out_stride smaller than one output row");
+    const size_t sig_scalars = ((nframes - 1) * hop + (taps ? *taps : 1) * a->N) * a->spp;
+    if (nsignals > 1 && *signal_stride < sig_scalars) return bad_in(prefix, "signal_stride smaller than one signal's samples");
+    if (!signal || !out) return bad_in(prefix, "NULL signal / out");
+    a->hop_s = hop * a->spp;
+    a->batch = nsignals * nframes;
+    if (nsignals == 1) *signal_stride = 0;   // (one signal: the stride is not read)
+    return 0;
+}
+
+// The composed analysis: head(X, first frame, frames) fills rows of the frame matrix (chunks of at most SCRATCH_CAP_BYTES), then
+// transform_batch, then rows -> out where `out` is not the dense spectrum.
+template <typename T, class Head>
+static int analysis_composed(Setup* s, const AnalysisArgs& a, T* out, size_t out_stride, int output, hipStream_t st, Head&& head) {
+    const bool direct = output != FR_POWER && out_stride == a.row;
+    return chunked_scratch<T>(s->frames, st, a.batch, a.row * sizeof(T), "the frame matrix", [&](T* X, size_t v0, size_t cnt) {
+        if (int rc = head(X, v0, cnt)) return rc;
+        T* dst = out + v0 * out_stride;
+        if (int rc = transform_batch_any(s, X, direct ? dst : X, cnt, PFFFT_FORWARD, output == FR_INTERNAL ? 0 : 1, st)) return rc;
+        return direct ? 0 : store_rows<T>(output == FR_POWER, a.real, X, a.row, dst, out_stride, cnt, st);
+    });
+}
+
+// ------------------------------------------------------------------------------------------------ synthesis (frames, pfb)
+// spectra rows r0 ... r0 + cnt - 1 -> backward-transformed dense rows in X
+template <typename T>
+static int frames_backward(Setup* s, const T* spectra, size_t spectra_stride, size_t r0, size_t cnt, T* X, int ordered, hipStream_t st) {
+    const size_t row = s->vec_scalars;
+    const T* src = spectra + r0 * spectra_stride;
+    if (spectra_stride != row) {
+        int rc = launch_rows<T, 0>(src, spectra_stride, X, row, cnt, row, st);
+        if (rc) return rc;
+        src = X;
+    }
+    return transform_batch_any(s, src, X, cnt, PFFFT_BACKWARD, ordered ? 1 : 0, st);
+}
+
+// Checked spectra of frames that span `span` samples -> signals: every frame at once where the batch fits under the cap, else by
+// synth_plan.  gather(X, first frame in X, frame pitch of a signal in X, frames end, signal, signal_stride, signals, first sample, samples
+// end) launches the entry's overlap-add of the rows of X on `st`.
+template <typename T, class Gather>
+static int synthesis_runs(Setup* s, const T* spectra, size_t spectra_stride, size_t nsignals, size_t nframes, size_t hop, size_t span,
+                          size_t min_run, int ordered, T* signal, size_t signal_stride, hipStream_t st, Gather&& gather) {
+    s = for_device(s);
+    int rc = ensure_device_any(s);
+    if (rc) return rc;
+    const size_t row = s->vec_scalars, samples = (nframes - 1) * hop + span, batch = nsignals * nframes, cap = cap_rows(row * sizeof(T));
+    std::lock_guard<std::mutex> lk(s->frames.mu);
+    void* buf = nullptr;
+    if (batch <= cap) {   // every frame at once, one gather
+        if ((rc = scratch_buffer(s->frames, st, batch * row * sizeof(T), "the frame matrix", &buf))) return rc;
+        if ((rc = frames_backward<T>(s, spectra, spectra_stride, 0, batch, (T*)buf, ordered, st))) return rc;
+        return gather((const T*)buf, 0, nframes, nframes, signal, signal_stride, nsignals, 0, samples);
+    }
+    const size_t reach = synth_reach(span, hop);
+    const RunPlan p = synth_plan(nframes, cap, reach, min_run);
+    if ((rc = scratch_buffer(s->frames, st, p.buffer_rows * row * sizeof(T), "the frame matrix", &buf))) return rc;
+    for (size_t i = 0; i < nsignals; ++i)
+        for (size_t fa = 0; fa < nframes; fa += p.run) {
+            const size_t fb = std::min(nframes, fa + p.run), f0 = fa > reach ? fa - reach : 0;
+            if ((rc = frames_backward<T>(s, spectra, spectra_stride, i * nframes + f0, fb - f0, (T*)buf, ordered, st))) return rc;
+            if ((rc = gather((const T*)buf, f0, 0, fb, signal + i * signal_stride, 0, 1, fa * hop, fb == nframes ? samples : fb * hop))) return rc;
+        }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ the framed register-tiled configuration
+template <class C> struct CfgTag { typedef C type; };
+
+// A kernel that frames, folds or accumulates around the register-tiled transform equals transform_batch bit for bit only on the
+// configuration transform_batch runs on for the same (direction, layout), so that is read from the setup's stored route `r`: real float on
+// TiledPick C512 / C1024 / C2048 (N = 1024 / 2048 / 4096).  visit(CfgTag<C>()) and true, or false: no such kernel.
+template <class Visit>
+static bool visit_tiled_cfg(const Setup* s, const Route& r, Visit&& visit) {
+    if (s->is_double || s->transform != PFFFT_REAL || s->kernel != K_TILED || r.fam != FAM_TILED) return false;
+    const std::string cfg = r.tiled.cfg;
+    if (s->n == 512 && cfg == "TiledPick::C512") { visit(CfgTag<TiledPick<float>::C512>()); return true; }
+    if (s->n == 1024 && cfg == "TiledPick::C1024") { visit(CfgTag<TiledPick<float>::C1024>()); return true; }
+    if (s->n == 2048 && cfg == "TiledPick::C2048") { visit(CfgTag<TiledPick<float>::C2048>()); return true; }
+    return false;
+}
+
+// ------------------------------------------------------------------------------------------------ handles that own an inner setup
+// Base of the any-length, zoom and DCT handles: the magic word first, the owned PFFFT_Setup / PFFFTD_Setup.  A handle type H names itself
+// in H::KIND for the refusal text.
+template <uint32_t MAGIC_>
+struct InnerOwner {
+    static constexpr uint32_t HANDLE_MAGIC = MAGIC_;
+    uint32_t magic = MAGIC_;
+    int is_double = 0;
+    Setup* inner = nullptr;
+    ~InnerOwner() { drop_inner(); }
+    bool new_inner(int len, int transform, int dbl) {
+        is_double = dbl;
+        inner = dbl ? static_cast<Setup*>(pffftd_new_setup(len, (pffft_transform_t)transform))
+                    : static_cast<Setup*>(pffft_new_setup(len, (pffft_transform_t)transform));
+        return inner != nullptr;
+    }
+    void drop_inner() {
+        if (!inner) return;
+        if (is_double) pffftd_destroy_setup(static_cast<PFFFTD_Setup*>(inner));
+        else pffft_destroy_setup(static_cast<PFFFT_Setup*>(inner));
+        inner = nullptr;
+    }
+};
+
+template <class H>
+static H* checked_handle(const void* p) {
+    const H* h = static_cast<const H*>(p);
+    return h && h->magic == H::HANDLE_MAGIC ? const_cast<H*>(h) : nullptr;
+}
+// ... of the scalar type T, or NULL with the refusal text set: the entry returns hipErrorInvalidHandle
+template <class H, typename T>
+static H* typed_handle(const void* p) {
+    H* h = checked_handle<H>(p);
+    if (h && h->is_double == (sizeof(T) == 8)) return h;
+    g_last_error = std::string("pffft_hip: bad ") + H::KIND + " setup handle";
+    return nullptr;
+}
+template <class H>
+static void destroy_handle(void* p) {
+    H* h = checked_handle<H>(p);
+    if (!h) return;
+    h->magic = 0;
+    h->drop_inner();   // (before the handle's own tables and scratch go)
+    delete h;
+}
+
+// A handle that serves ONE device, like PFFASTCONV_Setup: the first call binds it to the current device and builds its tables with
+// build() (allocates and synchronises: not during a stream capture); a call from a thread whose current device is another one is refused.
+struct DeviceBinding {
+    std::mutex mu;   // guards the lazy tables
+    bool ready = false;
+    int device = -1;
+};
+template <class Build>
+static int bind_device_once(DeviceBinding& b, const char* prefix, hipStream_t st, Build&& build) {
+    int dev = -1;
+    PF_CHECK(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(b.mu);
+    if (b.ready)
+        return b.device == dev ? 0 : bad_in(prefix, "this setup holds its tables on another device (one setup serves one device)", hipErrorInvalidDevice);
+    if (stream_capturing(st))
+        return bad_in(prefix, "the tables of this setup would have to be built during graph capture: run the call once before capturing",
+                      hipErrorStreamCaptureUnsupported);
+    if (int rc = build()) return rc;
+    b.device = dev;
+    b.ready = true;
+    return 0;
+}
+
+}  // namespace pf

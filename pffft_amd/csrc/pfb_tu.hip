@@ -1,13 +1,8 @@
 // libpffft_hip.so, translation unit of the polyphase filter bank (include/pffft_hip.h: pffft_hip_pfb_transform_batch,
 // pffft_hip_pfb_route, pffft_hip_pfb_synthesis_batch): validation, route decision, the fused complex N = 1024 kernel's launch and the
-// composed routes through the per-stream frame matrix (pf::Setup::frames and its helpers: frames_host.h, shared with the frame entries of
+// composed routes through the per-stream frame matrix (pf::Setup::frames and its helpers: pf_compose.h, shared with the frame entries of
 // frames_tu.hip).  Kernels: fft_pfb.h.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-
-#include "../../include/pffft_hip.h"
-#include "frames_host.h"
+#include "pf_compose.h"
 #include "fft_pfb.h"
 
 static_assert(pf::PFB_FUSED_MAX_TAPS == PFFFT_HIP_PFB_FUSED_MAX_TAPS, "the header's constant is the kernel's");
@@ -60,7 +55,7 @@ static int launch_pfb_c1024(Setup* s, const float* signal, size_t signal_stride,
     return 0;
 }
 
-// ------------------------------------------------------------------------------------------------ composed pieces (frames_host.h: the
+// ------------------------------------------------------------------------------------------------ composed pieces (pf_compose.h: the
 // frame matrix, the row kernel's launch)
 template <typename T, int U>
 static int launch_fold(const T* signal, size_t signal_stride, size_t nframes, size_t hop_s, int spp, const T* prototype, size_t taps, T* X,
@@ -81,70 +76,28 @@ static int launch_fold(const T* signal, size_t signal_stride, size_t nframes, si
 template <typename T>
 static int pfb_transform_batch(Setup* s, const T* signal, size_t signal_stride, size_t nsignals, size_t nframes, size_t hop,
                                const T* prototype, size_t taps, T* out, size_t out_stride, int output, hipStream_t st) {
-    if (int rc = check_setup<T>(s)) return rc;
-    if (hop == 0) return bad("pfb: hop == 0");
-    if (taps == 0) return bad("pfb: taps == 0");
-    if (!prototype) return bad("pfb: NULL prototype");
-    if (output != FR_INTERNAL && output != FR_ORDERED && output != FR_POWER) return bad("pfb: unknown output");
-    if (nsignals == 0 || nframes == 0) return 0;
-    const bool real = s->transform == PFFFT_REAL;
-    const size_t spp = real ? 1 : 2, N = (size_t)s->N, row = s->vec_scalars;
-    const size_t out_row = output == FR_POWER ? (real ? N / 2 + 1 : N) : row;
-    if (out_stride == 0) out_stride = out_row;
-    if (out_stride < out_row) return bad("pfb: out_stride smaller than one output row");
-    const size_t sig_scalars = ((nframes - 1) * hop + taps * N) * spp;
-    if (nsignals > 1 && signal_stride < sig_scalars) return bad("pfb: signal_stride smaller than one signal's samples");
-    if (!signal || !out) return bad("pfb: NULL signal / out");
-    const size_t hop_s = hop * spp, batch = nsignals * nframes;
-    if (nsignals == 1) signal_stride = 0;   // (one signal: the stride is not read)
+    AnalysisArgs a;
+    if (int rc = analysis_args<T>("pfb: ", s, signal, &signal_stride, nsignals, nframes, hop, out, &out_stride, output, &a, &taps, prototype))
+        return rc == ARGS_EMPTY ? 0 : rc;
 
     s = for_device(s);
-    int rc = ensure_device_any(s);
-    if (rc) return rc;
+    if (int rc = ensure_device_any(s)) return rc;
     const AbSel sel = ab();
     if constexpr (sizeof(T) == 4) {
+        // (the kernel counts frames in 32 bits: longer batches of ONE signal go out in slices; several signals that long are composed)
         if (pfb_route_fused(s, hop, taps, signal_stride, out_stride, output, sel) && aligned_to(signal, 16) && aligned_to(out, 16) &&
-            aligned_to(prototype, 8)) {
-            // (the kernel counts frames in 32 bits: longer batches of ONE signal go out in slices; several signals that long are composed)
-            constexpr size_t SLICE = (size_t)3 << 30;
-            if (batch <= SLICE)
-                return launch_pfb_c1024(s, signal, signal_stride, nframes, hop, prototype, taps, out, out_stride, batch, output, st);
-            if (nsignals == 1) {
-                for (size_t b0 = 0; b0 < batch; b0 += SLICE) {
-                    const size_t nb = std::min(batch - b0, SLICE);
-                    if ((rc = launch_pfb_c1024(s, signal + b0 * hop_s, 0, nb, hop, prototype, taps, out + b0 * out_stride, out_stride, nb,
-                                               output, st)))
-                        return rc;
-                }
-                return 0;
-            }
-        }
+            aligned_to(prototype, 8) && (a.batch <= ROW_SLICE || nsignals == 1))
+            return for_slices(a.batch, [&](size_t b0, size_t nb) {
+                return launch_pfb_c1024(s, signal + b0 * a.hop_s, signal_stride, nsignals == 1 ? nb : nframes, hop, prototype, taps,
+                                        out + b0 * out_stride, out_stride, nb, output, st);
+            });
     }
-
-    // composed: folded frames -> frame matrix (chunks of at most FRAMES_CAP_BYTES), transform_batch, then rows -> out where `out` is not the
-    // dense spectrum
-    const size_t chunk = std::max<size_t>(1, std::min(batch, FRAMES_CAP_BYTES / (row * sizeof(T))));
-    const bool direct = output != FR_POWER && out_stride == row;
-    std::lock_guard<std::mutex> lk(s->frames.mu);
-    void* buf = nullptr;
-    if ((rc = frames_buffer(s, st, chunk * row * sizeof(T), &buf))) return rc;
-    T* X = (T*)buf;
     constexpr int U = 16 / (int)sizeof(T);
-    const bool wide = aligned_to(signal, 16) && signal_stride % U == 0 && hop_s % U == 0 && row % U == 0;
-    for (size_t v0 = 0; v0 < batch; v0 += chunk) {
-        const size_t cnt = std::min(batch - v0, chunk);
-        rc = wide ? launch_fold<T, U>(signal, signal_stride, nframes, hop_s, (int)spp, prototype, taps, X, v0, cnt, row, st)
-                  : launch_fold<T, 1>(signal, signal_stride, nframes, hop_s, (int)spp, prototype, taps, X, v0, cnt, row, st);
-        if (rc) return rc;
-        T* dst = out + v0 * out_stride;
-        if ((rc = transform_batch_any(s, X, direct ? dst : X, cnt, PFFFT_FORWARD, output == FR_INTERNAL ? 0 : 1, st))) return rc;
-        if (direct) continue;
-        if (output != FR_POWER) rc = launch_rows<T, 0>(X, row, dst, out_stride, cnt, row, st);
-        else if (real) rc = launch_rows<T, 1>(X, row, dst, out_stride, cnt, row, st);
-        else rc = launch_rows<T, 2>(X, row, dst, out_stride, cnt, row, st);
-        if (rc) return rc;
-    }
-    return 0;
+    const bool wide = aligned_to(signal, 16) && signal_stride % U == 0 && a.hop_s % U == 0 && a.row % U == 0;
+    return analysis_composed<T>(s, a, out, out_stride, output, st, [&](T* X, size_t v0, size_t cnt) {
+        return wide ? launch_fold<T, U>(signal, signal_stride, nframes, a.hop_s, (int)a.spp, prototype, taps, X, v0, cnt, a.row, st)
+                    : launch_fold<T, 1>(signal, signal_stride, nframes, a.hop_s, (int)a.spp, prototype, taps, X, v0, cnt, a.row, st);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------ synthesis
@@ -194,9 +147,6 @@ static int pfb_synthesis_batch(Setup* s, const T* spectra, size_t spectra_stride
     if (!spectra || !signal) return bad("pfb synthesis: NULL spectra / signal");
     if (nsignals == 1) signal_stride = 0;   // (one signal: the stride is not read)
 
-    s = for_device(s);
-    int rc = ensure_device_any(s);
-    if (rc) return rc;
     const AbSel sel = ab();
     constexpr size_t U = 16 / sizeof(T);
     SynForm form;
@@ -205,32 +155,10 @@ static int pfb_synthesis_batch(Setup* s, const T* spectra, size_t spectra_stride
     form.wide = !sel.is(AB_PFB_SYN_SCALAR) && (hop * spp) % U == 0 && signal_stride % U == 0 && row % U == 0 && aligned_to(signal, 16) &&
                 aligned_to(prototype, real ? 16 : sizeof(T) * (U / 2));
     form.xcd = sel.is(AB_PFB_SYN_XCD) || (PFB_SYN_XCD_DEFAULT && !sel.is(AB_PFB_SYN_PLAIN));
-    const size_t batch = nsignals * nframes, cap_rows = std::max<size_t>(1, FRAMES_CAP_BYTES / (row * sizeof(T)));
-    std::lock_guard<std::mutex> lk(s->frames.mu);
-    void* buf = nullptr;
-    if (batch <= cap_rows) {   // every frame at once, one gather
-        if ((rc = frames_buffer(s, st, batch * row * sizeof(T), &buf))) return rc;
-        T* X = (T*)buf;
-        if ((rc = frames_backward<T>(s, spectra, spectra_stride, 0, batch, X, ordered, st))) return rc;
-        return launch_syn<T>(form, spp, X, 0, nframes, nframes, hop, N, span, prototype, scaling, signal, signal_stride, nsignals, 0, samples, st);
-    }
-    // beyond the cap: signal by signal, each in runs of frames.  A run owns the samples from its first frame's start to the next run's
-    // first frame's start (the last run: to the end) and re-transforms the up to `reach` earlier frames that reach into them; a run is at
-    // least `reach` frames long, so that the re-transformed frames never outnumber the new ones - where reach + 1 rows alone do not fit
-    // under the cap the matrix is as large as that takes (at most 2 reach rows).
-    const size_t reach = (span + hop - 1) / hop - 1;
-    const size_t run = std::max<size_t>(std::max<size_t>(cap_rows > reach ? cap_rows - reach : 1, reach), 1);
-    if ((rc = frames_buffer(s, st, std::min(nframes, run + reach) * row * sizeof(T), &buf))) return rc;
-    T* X = (T*)buf;
-    for (size_t i = 0; i < nsignals; ++i)
-        for (size_t fa = 0; fa < nframes; fa += run) {
-            const size_t fb = std::min(nframes, fa + run), f0 = fa > reach ? fa - reach : 0;
-            if ((rc = frames_backward<T>(s, spectra, spectra_stride, i * nframes + f0, fb - f0, X, ordered, st))) return rc;
-            const size_t s0 = fa * hop, s1 = fb == nframes ? samples : fb * hop;
-            if ((rc = launch_syn<T>(form, spp, X, f0, 0, fb, hop, N, span, prototype, scaling, signal + i * signal_stride, 0, 1, s0, s1, st)))
-                return rc;
-        }
-    return 0;
+    return synthesis_runs<T>(s, spectra, spectra_stride, nsignals, nframes, hop, span, synth_reach(span, hop), ordered, signal, signal_stride, st,
+                             [&](const T* X, size_t fbase, size_t fpitch, size_t fend, T* sig, size_t sig_stride, size_t nsig, size_t s0, size_t s1) {
+                                 return launch_syn<T>(form, spp, X, fbase, fpitch, fend, hop, N, span, prototype, scaling, sig, sig_stride, nsig, s0, s1, st);
+                             });
 }
 
 }  // namespace pf
@@ -251,8 +179,7 @@ PF_EXPORT int pffftd_hip_pfb_transform_batch(PFFFTD_Setup* s, const double* sign
 PF_EXPORT const char* pffft_hip_pfb_route(const void* setup, size_t hop, size_t taps, size_t signal_stride, size_t out_stride, int output) {
     const pf::Setup* s = static_cast<const pf::Setup*>(setup);
     if (!s || s->magic != pf::MAGIC || hop == 0 || taps == 0 || output < 0 || output > 2) return "";
-    const bool real = s->transform == PFFFT_REAL;
-    if (out_stride == 0) out_stride = output == pf::FR_POWER ? (real ? (size_t)s->N / 2 + 1 : (size_t)s->N) : s->vec_scalars;
+    if (out_stride == 0) out_stride = pf::frame_dims(s, output).out_row;
     return pf::pfb_route_fused(s, hop, taps, signal_stride, out_stride, output, pf::ab()) ? "fused" : "composed";
 }
 

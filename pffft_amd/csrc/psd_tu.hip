@@ -1,23 +1,12 @@
 // libpffft_hip.so, translation unit of the averaged-power-spectrum entries (include/pffft_hip.h: pffft_hip_frames_psd_batch,
 // pffft_hip_frames_psd_route): validation, route decision, the fused kernel's instantiations and the composed route through the per-stream
-// frame matrix.  Kernels: fft_psd.h; the frame matrix and the framing kernel: frames_host.h / fft_frames.h.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-
-#include "../../include/pffft_hip.h"
-#include "frames_host.h"
+// frame matrix.  Kernels: fft_psd.h; the frame matrix and the framing kernel: pf_compose.h / fft_frames.h.
+#include "pf_compose.h"
 #include "fft_psd.h"
 
 static_assert(pf::PSD_RUN == PFFFT_HIP_PSD_RUN, "the run length is part of the contract");
 
 namespace pf {
-
-// The partial buffer of one call holds at most this many bytes (one group's partials where a group needs more): the call goes through it in
-// whole groups.
-constexpr size_t PSD_CAP_BYTES = (size_t)256 << 20;
-// runs of one fused launch (the kernel counts them in 32 bits)
-constexpr size_t PSD_SLICE = (size_t)3 << 30;
 
 // ------------------------------------------------------------------------------------------------ fused
 typedef void (*PsdFn)(const float*, size_t, unsigned, unsigned, size_t, const float*, float*, size_t, size_t, unsigned, float,
@@ -41,14 +30,9 @@ static PsdSel psd_sel(bool windowed) {
 // The frame entry's rule: p_f equals the POWER output of pffft_hip_frames_transform_batch bit for bit only on the configuration
 // transform_batch(ordered = 1) runs on, so that is read from the setup's stored route.
 static bool psd_fusable_setup(const Setup* s, PsdSel* e, bool windowed) {
-    if (s->is_double || s->transform != PFFFT_REAL || s->kernel != K_TILED) return false;
-    const Route& r = s->route[PFFFT_FORWARD][1];
-    if (r.fam != FAM_TILED) return false;
-    const std::string cfg = r.tiled.cfg;
-    if (s->n == 512 && cfg == "TiledPick::C512") { if (e) *e = psd_sel<TiledPick<float>::C512>(windowed); return true; }
-    if (s->n == 1024 && cfg == "TiledPick::C1024") { if (e) *e = psd_sel<TiledPick<float>::C1024>(windowed); return true; }
-    if (s->n == 2048 && cfg == "TiledPick::C2048") { if (e) *e = psd_sel<TiledPick<float>::C2048>(windowed); return true; }
-    return false;
+    return visit_tiled_cfg(s, s->route[PFFFT_FORWARD][1], [&](auto tag) {
+        if (e) *e = psd_sel<typename decltype(tag)::type>(windowed);
+    });
 }
 
 // sizes where the fused kernel is the default: all three until a measurement says otherwise (tests/test_gpu_psd.py times every cell; a size
@@ -81,24 +65,13 @@ static int launch_psd_fused(Setup* s, const PsdSel& e, const float* signal, size
 template <typename T>
 static int psd_batch(Setup* s, const T* signal, size_t signal_stride, size_t nsignals, size_t nframes, size_t hop, const T* window,
                      size_t navg, T scaling, T* out, size_t out_stride, hipStream_t st) {
-    if (int rc = check_setup<T>(s)) return rc;
-    if (hop == 0) return bad("psd: hop == 0");
-    if (nsignals == 0 || nframes == 0) return 0;
-    if (navg == 0) navg = nframes;
-    if (nframes % navg) return bad("psd: nframes is no multiple of navg");
-    const bool real = s->transform == PFFFT_REAL;
-    const size_t spp = real ? 1 : 2, N = (size_t)s->N, row = s->vec_scalars;
-    const size_t P = real ? N / 2 + 1 : N;
-    if (out_stride == 0) out_stride = P;
-    if (out_stride < P) return bad("psd: out_stride smaller than one output row");
-    const size_t sig_scalars = ((nframes - 1) * hop + N) * spp;
-    if (nsignals > 1 && signal_stride < sig_scalars) return bad("psd: signal_stride smaller than one signal's samples");
-    if (!signal || !out) return bad("psd: NULL signal / out");
-    const size_t hop_s = hop * spp, G = nframes / navg, V = nsignals * G;   // V output rows; row v = i G + g
-    const size_t rpg = (navg + PSD_RUN - 1) / PSD_RUN;                       // runs per group
-    if (nsignals == 1) signal_stride = 0;   // (one signal: the stride is not read)
-
-    int rc;
+    AnalysisArgs a;
+    int rc = analysis_args<T>("psd: ", s, signal, &signal_stride, nsignals, nframes, hop, out, &out_stride, FR_POWER, &a, nullptr, nullptr, &navg);
+    if (rc) return rc == ARGS_EMPTY ? 0 : rc;
+    const bool real = a.real;
+    const size_t spp = a.spp, row = a.row, P = a.out_row, hop_s = a.hop_s;
+    const size_t G = nframes / navg, V = nsignals * G;     // V output rows; row v = i G + g
+    const size_t rpg = (navg + PSD_RUN - 1) / PSD_RUN;     // runs per group
     s = for_device(s);
     if ((rc = ensure_device_any(s))) return rc;
     const AbSel sel = ab();
@@ -111,13 +84,12 @@ static int psd_batch(Setup* s, const T* signal, size_t signal_stride, size_t nsi
     // Averages of one run are scaled and stored by the run itself.  Longer ones go through the partial buffer in whole groups: `vstep`
     // output rows per pass, then the reduction of those rows.
     size_t vstep = V;
-    if (rpg > 1) vstep = std::max<size_t>(1, PSD_CAP_BYTES / (rpg * P * sizeof(T)));
-    if (fused) vstep = std::min(vstep, std::max<size_t>(1, PSD_SLICE / rpg));
+    if (rpg > 1) vstep = cap_rows(rpg * P * sizeof(T));
+    if (fused) vstep = std::min(vstep, std::max<size_t>(1, ROW_SLICE / rpg));   // (the kernel counts the runs of a launch in 32 bits)
     vstep = std::min(vstep, V);
     // composed: the frames of whole runs through the frame matrix (as large as one run needs where a run exceeds the cap)
     const size_t lfull = std::min<size_t>(navg, PSD_RUN);
-    const size_t cap_rows = std::max<size_t>(1, FRAMES_CAP_BYTES / (row * sizeof(T)));
-    const size_t crun = std::max<size_t>(1, cap_rows / lfull);
+    const size_t crun = std::max<size_t>(1, cap_rows(row * sizeof(T)) / lfull);
     auto first_frame = [&](size_t r) { return (r / rpg) * navg + (r % rpg) * PSD_RUN; };   // in the numbering v = i nframes + f
 
     std::unique_lock<std::mutex> lkp(s->psd.mu, std::defer_lock), lkf(s->frames.mu, std::defer_lock);
@@ -132,11 +104,9 @@ static int psd_batch(Setup* s, const T* signal, size_t signal_stride, size_t nsi
     if (!fused) {
         lkf.lock();
         const size_t rows_x = std::min(V * navg, std::min(crun, vstep * rpg) * lfull);
-        if ((rc = frames_buffer(s, st, rows_x * row * sizeof(T), &buf))) return rc;
+        if ((rc = scratch_buffer(s->frames, st, rows_x * row * sizeof(T), "the frame matrix", &buf))) return rc;
         X = (T*)buf;
     }
-    constexpr int U = 16 / (int)sizeof(T);
-    const bool wide = aligned16(signal) && signal_stride % U == 0 && hop_s % U == 0;
     for (size_t v0 = 0; v0 < V; v0 += vstep) {
         const size_t rows = std::min(V - v0, vstep), ra = v0 * rpg, rb = (v0 + rows) * rpg;
         T* dst = rpg == 1 ? out + v0 * out_stride : part;
@@ -148,13 +118,7 @@ static int psd_batch(Setup* s, const T* signal, size_t signal_stride, size_t nsi
         } else {
             for (size_t r = ra; r < rb; r += crun) {
                 const size_t cnt = std::min(rb - r, crun), fa = first_frame(r), nfr = first_frame(r + cnt) - fa;
-                if (wide)
-                    hipLaunchKernelGGL((frames_gather_kernel<T, U>), dim3(stream_grid(nfr * row / U)), dim3(256), 0, st, signal, signal_stride,
-                                       nframes, hop_s, (int)spp, window, X, fa, nfr, (unsigned)row);
-                else
-                    hipLaunchKernelGGL((frames_gather_kernel<T, 1>), dim3(stream_grid(nfr * row)), dim3(256), 0, st, signal, signal_stride,
-                                       nframes, hop_s, (int)spp, window, X, fa, nfr, (unsigned)row);
-                PF_CHECK(hipGetLastError());
+                if ((rc = launch_gather<T>(signal, signal_stride, nframes, hop_s, spp, window, X, fa, nfr, row, st))) return rc;
                 if ((rc = transform_batch_any(s, X, X, nfr, PFFFT_FORWARD, 1, st))) return rc;
                 if (real)
                     hipLaunchKernelGGL((psd_runs_kernel<T, 1>), dim3(stream_grid(cnt * P)), dim3(256), 0, st, X, (unsigned)row, r, cnt, navg, rpg,

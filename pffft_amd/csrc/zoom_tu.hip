@@ -1,9 +1,6 @@
 // libpffft_hip.so, translation unit of the zoom transforms (include/pffft_hip.h: pffft[d]_hip_zoom_*): K spectral lines from f0 in steps
 // of df, by Bluestein's algorithm on the library's own convolution.  Plan (route, convolution length) at setup, tables on first use from
 // exactly reduced phases, the fused kernel's launch and the composed route through a per-stream scratch image.  Kernels: fft_zoom.h.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
 #include <cmath>
 #include <memory>
 
@@ -120,29 +117,20 @@ struct Phase {
 };
 
 // ------------------------------------------------------------------------------------------------ the setup
-// One setup serves ONE device, like the any-length setups: the tables are built on the device that is current at the first call, and a
-// call from a thread whose current device is another one is refused.
-struct ZoomSetup {
-    uint32_t magic = ZOOM_MAGIC;
-    int N = 0, K = 0, is_double = 0;
+// The owned inner setup has length M.  One setup serves ONE device, like the any-length setups (bind_device_once).
+struct ZoomSetup : InnerOwner<ZOOM_MAGIC> {
+    static constexpr const char* KIND = "zoom";
+    int N = 0, K = 0;
     double f0 = 0, df = 0;
     Phase ph;
     bool fusable = false;          // float and M in the fused set: both routes exist, on the same M
     int M = 0;                     // convolution length
-    Setup* inner = nullptr;        // length M: a PFFFT_Setup / PFFFTD_Setup, owned
-    std::mutex mu;                 // guards the lazy tables
-    bool ready = false;
-    int device = -1;
+    DeviceBinding bound;
     DevBuf d_a;                    // a[n], n < N (fusable: M entries, zero from N on)
     DevBuf d_c;                    // c[k], k < K (fusable: M entries, zero from K on)
     DevBuf d_H;                    // spectrum of the filter b in the inner setup's internal layout
     StreamScratch pad;             // batch x M image of the composed route: one per stream, pad.mu held while a call enqueues
 };
-
-static ZoomSetup* zoom_checked(const void* p) {
-    const ZoomSetup* z = static_cast<const ZoomSetup*>(p);
-    return z && z->magic == ZOOM_MAGIC ? const_cast<ZoomSetup*>(z) : nullptr;
-}
 
 // ------------------------------------------------------------------------------------------------ plan
 // The fused kernel exists for float and these convolution lengths (M2 = next power of two >= N + K - 1).  Per row it moves 8 (N + K)
@@ -164,7 +152,7 @@ static bool zoom_fused_default(int M) {
 static ZoomSetup* zoom_new_setup(int N, int K, double f0, double df, int is_double) {
     if (N < 1 || K < 1 || (long long)N + K - 1 > ZOOM_MAX_CONV || !std::isfinite(f0) || !std::isfinite(df)) return nullptr;
     std::unique_ptr<ZoomSetup> z(new ZoomSetup);
-    z->N = N; z->K = K; z->f0 = f0; z->df = df; z->is_double = is_double;
+    z->N = N; z->K = K; z->f0 = f0; z->df = df;
     z->ph.plan(f0, df);
     const long long need = (long long)N + K - 1;
     long long p2 = 16;
@@ -172,19 +160,7 @@ static ZoomSetup* zoom_new_setup(int N, int K, double f0, double df, int is_doub
     z->fusable = !is_double && zoom_fused_len((int)p2);
     // (a setup that can run fused runs BOTH routes on M2: one filter spectrum, one answer to pffft_hip_zoom_conv_size)
     z->M = z->fusable ? (int)p2 : pffft_nearest_transform_size((int)need, PFFFT_COMPLEX, 1);
-    z->inner = is_double ? static_cast<Setup*>(pffftd_new_setup(z->M, PFFFT_COMPLEX)) : static_cast<Setup*>(pffft_new_setup(z->M, PFFFT_COMPLEX));
-    if (!z->inner) return nullptr;
-    return z.release();
-}
-
-static void zoom_destroy_setup(ZoomSetup* z) {
-    if (!z || z->magic != ZOOM_MAGIC) return;
-    z->magic = 0;
-    if (z->inner) {
-        if (z->is_double) pffftd_destroy_setup(static_cast<PFFFTD_Setup*>(z->inner));
-        else pffft_destroy_setup(static_cast<PFFFT_Setup*>(z->inner));
-    }
-    delete z;
+    return z->new_inner(z->M, PFFFT_COMPLEX, is_double) ? z.release() : nullptr;
 }
 
 // the route of a call under the calling thread's selector
@@ -216,20 +192,9 @@ static int zoom_build_tables(ZoomSetup* z) {
     return bluestein_filter_spectrum<T>(z->inner, M, b, z->d_H);
 }
 
-// first call: binds the setup to the current device and builds its tables (allocates and synchronises: not during a stream capture)
 template <typename T>
 static int zoom_ensure(ZoomSetup* z, hipStream_t st) {
-    int dev = -1;
-    PF_CHECK(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(z->mu);
-    if (z->ready) return z->device == dev ? 0 : bad("zoom: this setup holds its tables on another device (one setup serves one device)", hipErrorInvalidDevice);
-    if (stream_capturing(st))
-        return bad("zoom: the tables of this setup would have to be built during graph capture: run the call once before capturing",
-                   hipErrorStreamCaptureUnsupported);
-    if (int rc = zoom_build_tables<T>(z)) return rc;
-    z->device = dev;
-    z->ready = true;
-    return 0;
+    return bind_device_once(z->bound, "zoom: ", st, [&] { return zoom_build_tables<T>(z); });
 }
 
 // ------------------------------------------------------------------------------------------------ the two routes (bluestein_host.h)
@@ -248,13 +213,13 @@ static int zoom_composed(ZoomSetup* z, const T* in, T* out, size_t batch, int cj
     return bluestein_composed<T>(
         z->inner, z->pad, (const T*)z->d_H.as<T>(), M, batch, st,
         [&](cx<T>* X, size_t v0, size_t cnt) {
-            hipLaunchKernelGGL((zoom_pad_kernel<T>), dim3(bluestein_grid(cnt * M)), dim3(256), 0, st, reinterpret_cast<const cx<T>*>(in) + v0 * N, X,
+            hipLaunchKernelGGL((zoom_pad_kernel<T>), dim3(stream_grid(cnt * M)), dim3(256), 0, st, reinterpret_cast<const cx<T>*>(in) + v0 * N, X,
                                z->d_a.as<cx<T>>(), cnt, N, M, cj);
             PF_CHECK(hipGetLastError());
             return 0;
         },
         [&](cx<T>* X, size_t v0, size_t cnt) {
-            hipLaunchKernelGGL((zoom_crop_kernel<T>), dim3(bluestein_grid(cnt * K)), dim3(256), 0, st, (const cx<T>*)X,
+            hipLaunchKernelGGL((zoom_crop_kernel<T>), dim3(stream_grid(cnt * K)), dim3(256), 0, st, (const cx<T>*)X,
                                reinterpret_cast<cx<T>*>(out) + v0 * K, z->d_c.as<cx<T>>(), cnt, K, M, cj);
             PF_CHECK(hipGetLastError());
             return 0;
@@ -264,11 +229,8 @@ static int zoom_composed(ZoomSetup* z, const T* in, T* out, size_t batch, int cj
 // ------------------------------------------------------------------------------------------------ the entry
 template <typename T>
 static int zoom_transform_batch(void* setup, const T* in, T* out, size_t batch, int dir, hipStream_t st) {
-    ZoomSetup* z = zoom_checked(setup);
-    if (!z || z->is_double != (sizeof(T) == 8)) {
-        g_last_error = "pffft_hip: bad zoom setup handle";
-        return (int)hipErrorInvalidHandle;
-    }
+    ZoomSetup* z = typed_handle<ZoomSetup, T>(setup);
+    if (!z) return (int)hipErrorInvalidHandle;
     if (dir != PFFFT_FORWARD && dir != PFFFT_BACKWARD) return bad("zoom: bad direction");
     if (batch && (!in || !out)) return bad("zoom: NULL in / out");
     if (((uintptr_t)in | (uintptr_t)out) & (2 * sizeof(T) - 1)) return bad("zoom: in / out not aligned to one complex value");
@@ -300,8 +262,8 @@ PF_EXPORT PFFFT_HIP_ZoomSetup* pffft_hip_zoom_new_setup(int N, int K, double f0,
 PF_EXPORT PFFFTD_HIP_ZoomSetup* pffftd_hip_zoom_new_setup(int N, int K, double f0, double df) {
     return reinterpret_cast<PFFFTD_HIP_ZoomSetup*>(pf::zoom_new_setup(N, K, f0, df, 1));
 }
-PF_EXPORT void pffft_hip_zoom_destroy_setup(PFFFT_HIP_ZoomSetup* s) { pf::zoom_destroy_setup(reinterpret_cast<pf::ZoomSetup*>(s)); }
-PF_EXPORT void pffftd_hip_zoom_destroy_setup(PFFFTD_HIP_ZoomSetup* s) { pf::zoom_destroy_setup(reinterpret_cast<pf::ZoomSetup*>(s)); }
+PF_EXPORT void pffft_hip_zoom_destroy_setup(PFFFT_HIP_ZoomSetup* s) { pf::destroy_handle<pf::ZoomSetup>(s); }
+PF_EXPORT void pffftd_hip_zoom_destroy_setup(PFFFTD_HIP_ZoomSetup* s) { pf::destroy_handle<pf::ZoomSetup>(s); }
 PF_EXPORT int pffft_hip_zoom_transform_batch(PFFFT_HIP_ZoomSetup* s, const float* in, float* out, size_t batch, pffft_direction_t d, void* stream) {
     return pf::zoom_transform_batch<float>(s, in, out, batch, (int)d, (hipStream_t)stream);
 }
@@ -310,16 +272,16 @@ PF_EXPORT int pffftd_hip_zoom_transform_batch(PFFFTD_HIP_ZoomSetup* s, const dou
     return pf::zoom_transform_batch<double>(s, in, out, batch, (int)d, (hipStream_t)stream);
 }
 PF_EXPORT int pffft_hip_zoom_conv_size(const void* setup) {
-    const pf::ZoomSetup* z = pf::zoom_checked(setup);
+    const pf::ZoomSetup* z = pf::checked_handle<pf::ZoomSetup>(setup);
     return z ? z->M : -1;
 }
 PF_EXPORT const char* pffft_hip_zoom_route(const void* setup) {
-    const pf::ZoomSetup* z = pf::zoom_checked(setup);
+    const pf::ZoomSetup* z = pf::checked_handle<pf::ZoomSetup>(setup);
     if (!z) return "";
     return pf::zoom_fused_now(z, pf::ab()) ? "fused" : "composed";
 }
 PF_EXPORT int pffft_hip_zoom_table(const void* setup, int which, size_t first, size_t count, void* host_out) {
-    const pf::ZoomSetup* z = pf::zoom_checked(setup);
+    const pf::ZoomSetup* z = pf::checked_handle<pf::ZoomSetup>(setup);
     if (!z || !host_out || (which != 0 && which != 1)) {
         pf::g_last_error = "pffft_hip: bad zoom setup handle / table / NULL output";
         return (int)hipErrorInvalidValue;
