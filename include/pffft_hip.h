@@ -507,7 +507,7 @@ int pffft_hip_zoom_table(const void *setup, int which, size_t first, size_t coun
  *               the canonical layout in place there, a table / permutation kernel into out.  The scratch holds at most 256 MiB (longer
  *               batches go through it in chunks on the stream); a call that would have to grow it - or build the table of a first call -
  *               on a capturing stream returns hipErrorStreamCaptureUnsupported before any launch: run the call once before capturing.
- * Types I and IV, strided rows and lengths pffft_new_setup refuses are not offered. */
+ * Type I, strided rows and lengths pffft_new_setup refuses are not offered (type IV: pffft[d]_hip_mdct_dct4_batch below). */
 typedef enum { PFFFT_HIP_DCT2, PFFFT_HIP_DCT3, PFFFT_HIP_DST2, PFFFT_HIP_DST3 } pffft_hip_dct_kind_t;
 typedef enum { PFFFT_HIP_DCT_NORM_NONE, PFFFT_HIP_DCT_NORM_ORTHO } pffft_hip_dct_norm_t;
 typedef struct PFFFT_HIP_DctSetup PFFFT_HIP_DctSetup;
@@ -524,6 +524,67 @@ int pffftd_hip_dct_transform_batch(PFFFTD_HIP_DctSetup *, const double *in, doub
  * NULL host_out. */
 const char *pffft_hip_dct_route(const void *setup);
 int pffft_hip_dct_table(const void *setup, size_t first, size_t count, void *host_out);
+
+/* MDCT / IMDCT FRAMES and the type-IV cosine transform (the lapped transform of audio and spectral codecs): frames of 2M samples at hop
+ * M, M coefficients per frame, perfect reconstruction through time-domain alias cancellation (TDAC).  M = coefficients per frame,
+ * h = n = M/2.  Legal M: M/2 is a length pffft[d]_new_setup(M/2, PFFFT_COMPLEX) takes (so M is a multiple of 32); NULL for any other M.
+ * Creating a setup touches no device; the handle owns a complex setup of M/2, whose per-device behaviour carries over.
+ * The core is the type-IV cosine sum without a factor, on ONE complex transform of half the length:
+ *     C4(u)[k] = sum_{i<M} u[i] cos(pi (2k+1)(2i+1) / 4M)
+ *     z[m] = (u[2m] + j u[M-1-2m]) a_m;  Z = the forward complex transform of length n, exactly as pffft_hip_transform_batch(...,
+ *     PFFFT_FORWARD, ordered = 1) transforms a vector;  y_k = Z_k b_k;  C4[2k] = Re y_k, C4[M-1-2k] = -Im y_k
+ * with a_m = exp(-j pi (4m+1) / 4M) and b_k = exp(-j pi k / M), m, k < n, evaluated in long double from exactly reduced integer phases
+ * and rounded once.  Every route forms both complex products with the same operations (one product and one fused multiply-add per
+ * component), so the routes agree bit for bit.
+ *   pffft[d]_hip_mdct_dct4_batch: dense rows of M reals in and out, out == in IS LEGAL (any other overlap is refused).  out = 2 C4(in) -
+ *     scipy.fft.dct(type=4, norm=None); the doubling is the last operation and exact.  dct4(dct4(x)) = 2M x.
+ *   pffft[d]_hip_mdct_transform_batch: signal i (at signal + i signal_stride) holds (nframes + 1) M samples.  Frame f of it is
+ *     p[j] = window[j] x_i[f M + j], j < 2M (window: 2M reals, NULL: no product; each product rounded once).  Fold, i < h:
+ *     u[i] = (-p[3h-1-i]) - p[3h+i], u[h+i] = p[i] - p[M-1-i] (one rounded subtraction each, no fused multiply-add with the window
+ *     product).  Row v = i nframes + f at coefs + v coefs_stride (0 = dense, M) is C4(u):
+ *     X[k] = sum_{j<2M} p[j] cos(pi/M (j + 1/2 + M/2)(k + 1/2)), the textbook MDCT without a factor.
+ *   pffft[d]_hip_mdct_overlap_add_batch: per frame v = C4(X_f), v1 = v[0..h), v2 = v[h..M), y_f = (v2, -reverse(v2), -reverse(v1), -v1)
+ *     = sum_k X[k] cos(...) (2M values).  Every sample s < (nframes + 1) M is WRITTEN as scaling (sum_f window[s - f M] y_f[s - f M])
+ *     over the at most two frames that cover it, f ascending, each product and each addition rounded once, the sum started from its
+ *     first term (window NULL: the terms are y_f themselves).  With a Princen-Bradley window (w[j]^2 + w[j+M]^2 = 1) and scaling = 2/M
+ *     the samples M ... nframes M - 1 reproduce the input; the first and the last M samples carry one aliased term.
+ * All pointers are device pointers aligned to 16 bytes; signal, window and coefs must not overlap; calls are asynchronous on `stream`;
+ * 0, else a hipError_t with its text in pffft_hip_last_error().  A call without rows or signals returns 0; nframes == 0 is refused.
+ * Routes (pffft_hip_mdct_route names the one an entry takes under the calling thread's selector):
+ *   "fused"     float, M = 512 / 1024: ONE kernel - the register-tiled complex transform of M/2 between two round trips of linear
+ *               16-byte accesses through its own LDS image; the frame entry loads the four quarter frames, windows and folds them in
+ *               registers.  4M bytes read from HBM and 4M written per frame or row.  The frame entry also needs signal_stride and
+ *               coefs_stride to be multiples of 4 scalars, the overlap-add coefs_stride (its core runs the kernel into the scratch image,
+ *               the gather follows).  Which (M, entry) cells run it by default is a measured table;
+ *               pffft_hip_set_variant(141) runs it wherever it is legal, 140 never.
+ *   "composed"  every setup: a fold / table kernel into a per-stream scratch image of rows x M, pffft[d]_hip_transform_batch in the
+ *               canonical layout in place there, a table / scatter kernel into the result; the overlap-add gathers from the image.  The
+ *               scratch holds at most 256 MiB (longer batches go through it in chunks on the stream, the overlap-add in runs of frames
+ *               that re-transform the one frame reaching into a run); a call that would have to grow it - or build the tables of a first
+ *               call - on a capturing stream returns hipErrorStreamCaptureUnsupported before any launch: run the call once before capturing.
+ * DST-IV, type I, window-shape switching between frames, strided samples and lengths pffft_new_setup refuses are not offered. */
+typedef struct PFFFT_HIP_MdctSetup PFFFT_HIP_MdctSetup;
+typedef struct PFFFTD_HIP_MdctSetup PFFFTD_HIP_MdctSetup;
+PFFFT_HIP_MdctSetup *pffft_hip_mdct_new_setup(int M);
+PFFFTD_HIP_MdctSetup *pffftd_hip_mdct_new_setup(int M);
+void pffft_hip_mdct_destroy_setup(PFFFT_HIP_MdctSetup *);     /* NULL-safe */
+void pffftd_hip_mdct_destroy_setup(PFFFTD_HIP_MdctSetup *);
+int pffft_hip_mdct_dct4_batch(PFFFT_HIP_MdctSetup *, const float *in, float *out, size_t rows, void *stream);
+int pffftd_hip_mdct_dct4_batch(PFFFTD_HIP_MdctSetup *, const double *in, double *out, size_t rows, void *stream);
+int pffft_hip_mdct_transform_batch(PFFFT_HIP_MdctSetup *, const float *signal, size_t signal_stride, size_t nsignals, size_t nframes,
+                                   const float *window, float *coefs, size_t coefs_stride, void *stream);
+int pffftd_hip_mdct_transform_batch(PFFFTD_HIP_MdctSetup *, const double *signal, size_t signal_stride, size_t nsignals, size_t nframes,
+                                    const double *window, double *coefs, size_t coefs_stride, void *stream);
+int pffft_hip_mdct_overlap_add_batch(PFFFT_HIP_MdctSetup *, const float *coefs, size_t coefs_stride, size_t nsignals, size_t nframes,
+                                     const float *window, float scaling, float *signal, size_t signal_stride, void *stream);
+int pffftd_hip_mdct_overlap_add_batch(PFFFTD_HIP_MdctSetup *, const double *coefs, size_t coefs_stride, size_t nsignals, size_t nframes,
+                                      const double *window, double scaling, double *signal, size_t signal_stride, void *stream);
+/* Host arithmetic only, handles of both precisions.  pffft_hip_mdct_route: `what` 0 = dct4, 1 = forward, 2 = overlap-add; "fused" /
+ * "composed" under the calling thread's selector, "" for an invalid handle or another `what`.  pffft_hip_mdct_table: `count` values from
+ * index `first` of a (which = 0) or b (which = 1), M/2 values each, as interleaved (re, im) pairs in the setup's type into host_out -
+ * the values of the device's tables.  0; non-zero for an invalid handle, another `which`, a range beyond M/2 values or a NULL host_out. */
+const char *pffft_hip_mdct_route(const void *setup, int what);
+int pffft_hip_mdct_table(const void *setup, int which, size_t first, size_t count, void *host_out);
 
 /* Overlap-save FIR on device-resident signal/output (same block schedule as pffastconv_apply,
  * src/pffastconv.c:204-261): returns the number of output samples written, or -1 on error. */

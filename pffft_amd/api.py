@@ -105,6 +105,16 @@ def lib():
         g("hip_dct_destroy_setup").restype = None; g("hip_dct_destroy_setup").argtypes = [C.c_void_p]
         g("hip_dct_transform_batch").restype = C.c_int
         g("hip_dct_transform_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        g("hip_mdct_new_setup").restype = C.c_void_p; g("hip_mdct_new_setup").argtypes = [C.c_int]
+        g("hip_mdct_destroy_setup").restype = None; g("hip_mdct_destroy_setup").argtypes = [C.c_void_p]
+        g("hip_mdct_dct4_batch").restype = C.c_int
+        g("hip_mdct_dct4_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        g("hip_mdct_transform_batch").restype = C.c_int
+        g("hip_mdct_transform_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                  C.c_size_t, C.c_void_p]
+        g("hip_mdct_overlap_add_batch").restype = C.c_int
+        g("hip_mdct_overlap_add_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, ct, C.c_void_p,
+                                                    C.c_size_t, C.c_void_p]
         getattr(L, f"validate_{pfx}_simd").restype = C.c_int
         getattr(L, f"validate_{pfx}_simd_ex").restype = C.c_int
         getattr(L, f"validate_{pfx}_simd_ex").argtypes = [C.c_void_p]
@@ -141,6 +151,9 @@ def lib():
     L.pffft_hip_dct_route.restype = C.c_char_p; L.pffft_hip_dct_route.argtypes = [C.c_void_p]
     L.pffft_hip_dct_table.restype = C.c_int
     L.pffft_hip_dct_table.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+    L.pffft_hip_mdct_route.restype = C.c_char_p; L.pffft_hip_mdct_route.argtypes = [C.c_void_p, C.c_int]
+    L.pffft_hip_mdct_table.restype = C.c_int
+    L.pffft_hip_mdct_table.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p]
     L.pffft_hip_kernel_name.restype = C.c_char_p; L.pffft_hip_kernel_name.argtypes = [C.c_void_p]
     L.pffft_hip_describe.restype = C.c_int; L.pffft_hip_describe.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.pffft_hip_route_occupancy.restype = C.c_int; L.pffft_hip_route_occupancy.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -830,6 +843,131 @@ class DctSetup:
         _check(fn(self.handle, x.data_ptr(), out.data_ptr(), batch, C.c_void_p(torch.cuda.current_stream().cuda_stream)),
                "hip_dct_transform_batch")
         return out
+
+
+MDCT_WHAT = {"dct4": 0, "mdct": 1, "imdct": 2}      # `what` of pffft_hip_mdct_route
+
+
+class MdctSetup:
+    """PFFFT_HIP_MdctSetup / PFFFTD_HIP_MdctSetup: MDCT / IMDCT frames of 2M samples at hop M (M coefficients per frame) and the type-IV
+    cosine transform of rows of M reals (include/pffft_hip.h).  Raises ValueError where pffft_hip_mdct_new_setup returns NULL.  Every
+    method takes CUDA tensors of the setup's dtype (and returns one), or numpy arrays, which go through the device (and return an array)."""
+
+    def __init__(self, M: int, dtype=np.float32):
+        self.M, self.dtype = int(M), np.dtype(dtype)
+        self._pfx = _pfx(dtype)
+        self._L = lib()
+        self.handle = getattr(self._L, f"{self._pfx}_hip_mdct_new_setup")(self.M)
+        if not self.handle:
+            raise ValueError(f"pffft_hip_mdct_new_setup({M}) returned NULL")
+
+    def close(self):
+        if getattr(self, "handle", None):
+            getattr(self._L, f"{self._pfx}_hip_mdct_destroy_setup")(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def route(self, what) -> str:
+        """pffft_hip_mdct_route: "fused" / "composed" for what = 0 / "dct4", 1 / "mdct", 2 / "imdct" under the calling thread's selector
+        ("" for another `what`).  Host arithmetic only."""
+        return self._L.pffft_hip_mdct_route(self.handle, MDCT_WHAT[what] if what in MDCT_WHAT else int(what)).decode()
+
+    def table(self, which: int, first: int = 0, count=None) -> np.ndarray:
+        """pffft_hip_mdct_table: a_m (which = 0) or b_k (which = 1), M/2 values each, as a complex array of the setup's precision (host
+        arithmetic only)."""
+        if count is None:
+            count = self.M // 2 - first
+        out = np.empty(2 * max(int(count), 0), dtype=self.dtype)
+        rc = self._L.pffft_hip_mdct_table(self.handle, int(which), int(first), int(count), out.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"pffft_hip_mdct_table failed ({rc}): {self._L.pffft_hip_last_error().decode()}")
+        return out.view(np.complex128 if self.dtype == np.float64 else np.complex64)
+
+    def _dev(self, x):
+        """(CUDA tensor of x, x was a numpy array)"""
+        import torch
+        want = torch.float64 if self.dtype == np.float64 else torch.float32
+        if x is None:
+            return None, False
+        if _is_torch(x):
+            assert x.is_cuda and x.dtype == want, "need a CUDA tensor of the setup dtype"
+            return x, False
+        return torch.from_numpy(np.ascontiguousarray(x, dtype=self.dtype)).cuda(), True
+
+    @staticmethod
+    def _stream():
+        import torch
+        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def dct4(self, rows, out=None):
+        """rows: `rows` x M scalars, contiguous; the result (2 C4(rows): scipy.fft.dct(type=4)) has the same shape.  out may be rows."""
+        import torch
+        x, host = self._dev(rows)
+        assert x.is_contiguous() and x.numel() % self.M == 0, "need contiguous whole rows"
+        if out is None:
+            out = torch.empty_like(x)
+        assert out.is_cuda and out.dtype == x.dtype and out.is_contiguous() and out.numel() == x.numel()
+        fn = getattr(self._L, f"{self._pfx}_hip_mdct_dct4_batch")
+        _check(fn(self.handle, x.data_ptr(), out.data_ptr(), x.numel() // self.M, self._stream()), "hip_mdct_dct4_batch")
+        return out.cpu().numpy() if host else out
+
+    def mdct(self, signal, window=None, nframes=None, out=None):
+        """signal: [(nframes + 1) M] or [nsignals, >= (nframes + 1) M] with unit stride along the samples (rows may be pitched); window:
+        2M values or None.  nframes defaults to what the samples hold.  Returns coefficients [nsignals, nframes, M] (out: the same shape, rows may be pitched)."""
+        import torch
+        x, host = self._dev(signal)
+        w, _ = self._dev(window)
+        one = x.dim() == 1
+        if one:
+            x = x.unsqueeze(0)
+        assert x.dim() == 2 and x.stride(1) == 1, "need samples with unit stride"
+        nsig = x.shape[0]
+        if nframes is None:
+            nframes = x.shape[1] // self.M - 1
+        nframes = int(nframes)
+        assert nframes >= 0 and x.shape[1] >= (nframes + 1) * self.M, "a signal holds (nframes + 1) M samples"
+        assert w is None or (w.is_contiguous() and w.numel() == 2 * self.M), "the window has 2M values"
+        if out is None:
+            out = torch.empty((nsig, nframes, self.M), dtype=x.dtype, device=x.device)
+        o3 = out.unsqueeze(0) if out.dim() == 2 else out
+        assert o3.is_cuda and o3.dtype == x.dtype and tuple(o3.shape) == (nsig, nframes, self.M) and o3.stride(2) == 1
+        cstride = o3.stride(1) if nframes > 1 else self.M
+        assert nsig == 1 or o3.stride(0) == nframes * cstride, "rows at one pitch"
+        fn = getattr(self._L, f"{self._pfx}_hip_mdct_transform_batch")
+        _check(fn(self.handle, x.data_ptr(), x.stride(0) if nsig > 1 else 0, nsig, nframes, w.data_ptr() if w is not None else None,
+                  o3.data_ptr(), cstride, self._stream()), "hip_mdct_transform_batch")
+        res = o3[0] if one else o3
+        return res.cpu().numpy() if host else res
+
+    def imdct(self, coefs, window=None, scaling=1.0, out=None):
+        """coefs: [nframes, M] or [nsignals, nframes, M], unit stride along a row (rows may be pitched).  Returns the overlap-added signals
+        [nsignals, (nframes + 1) M] (out: rows may be pitched); scaling = 2 / M with a Princen-Bradley window reconstructs the interior."""
+        import torch
+        X, host = self._dev(coefs)
+        w, _ = self._dev(window)
+        one = X.dim() == 2
+        if one:
+            X = X.unsqueeze(0)
+        assert X.dim() == 3 and X.shape[2] == self.M and X.stride(2) == 1, "need rows of M coefficients with unit stride"
+        nsig, nframes = X.shape[0], X.shape[1]
+        cstride = X.stride(1) if nframes > 1 else self.M
+        assert nsig == 1 or X.stride(0) == nframes * cstride, "rows at one pitch"
+        assert w is None or (w.is_contiguous() and w.numel() == 2 * self.M), "the window has 2M values"
+        samples = (nframes + 1) * self.M
+        if out is None:
+            out = torch.empty((nsig, samples), dtype=X.dtype, device=X.device)
+        o2 = out.unsqueeze(0) if out.dim() == 1 else out
+        assert o2.is_cuda and o2.dtype == X.dtype and o2.dim() == 2 and o2.shape[0] == nsig and o2.shape[1] >= samples and o2.stride(1) == 1
+        fn = getattr(self._L, f"{self._pfx}_hip_mdct_overlap_add_batch")
+        _check(fn(self.handle, X.data_ptr(), cstride, nsig, nframes, w.data_ptr() if w is not None else None, float(scaling),
+                  o2.data_ptr(), o2.stride(0) if nsig > 1 else 0, self._stream()), "hip_mdct_overlap_add_batch")
+        res = o2[0, :samples] if one else o2[:, :samples]
+        return res.cpu().numpy() if host else res
 
 
 class FastConv:

@@ -102,6 +102,13 @@ template <bool TYPE3, typename V> __device__ __forceinline__ V dct_mul(V a, V t,
     const V e = mk<T>(a.x * t.x, TYPE3 ? (T)2 * yy : yy);
     return mk<T>(edge ? e.x : z.x, edge ? e.y : z.y);
 }
+// The two table products of the type-IV cosine transform (fft_mdct.h: z a_m in front of the complex transform, Z b_k behind it), the ONE
+// place they are written: a w, each component one product and one fused multiply-add, on every route and in either precision.
+template <typename V> __device__ __forceinline__ V mdct_mul(V a, V w) {
+    typedef sc<V> T;
+    const T yy = a.y * w.y;
+    return mk<T>(fma_(a.x, w.x, -yy), fma_(a.x, w.y, a.y * w.x));
+}
 // the same for a COMPILE-TIME constant w (the fixed twiddles inside radix 16 / 32 / 9 / 25 / 27): the scalar form lets the
 // compiler keep the constants in scalar registers / literals; an asm operand would pin each one in a VGPR pair.  Same
 // operations as cmul / cmulc.

@@ -233,8 +233,19 @@ static bool visit_tiled_cfg(const Setup* s, const Route& r, Visit&& visit) {
     return false;
 }
 
+// The complex twin: complex float on TiledPick C256 / C512 (N = 256 / 512), the configurations the type-IV cosine kernel of fft_mdct.h
+// is built on (M = 512 / 1024).
+template <class Visit>
+static bool visit_tiled_cfg_complex(const Setup* s, const Route& r, Visit&& visit) {
+    if (s->is_double || s->transform != PFFFT_COMPLEX || s->kernel != K_TILED || r.fam != FAM_TILED) return false;
+    const std::string cfg = r.tiled.cfg;
+    if (s->n == 256 && cfg == "TiledPick::C256") { visit(CfgTag<TiledPick<float>::C256>()); return true; }
+    if (s->n == 512 && cfg == "TiledPick::C512") { visit(CfgTag<TiledPick<float>::C512>()); return true; }
+    return false;
+}
+
 // ------------------------------------------------------------------------------------------------ handles that own an inner setup
-// Base of the any-length, zoom and DCT handles: the magic word first, the owned PFFFT_Setup / PFFFTD_Setup.  A handle type H names itself
+// Base of the any-length, zoom, DCT and MDCT handles: the magic word first, the owned PFFFT_Setup / PFFFTD_Setup.  A handle type H names itself
 // in H::KIND for the refusal text.
 template <uint32_t MAGIC_>
 struct InnerOwner {

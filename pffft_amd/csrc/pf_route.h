@@ -81,6 +81,8 @@ enum AbValue : int {
     AB_ZOOM_FUSED = 137,        // ... the fused zoom kernel wherever it is legal, whatever the measured default of the length is
     AB_DCT_COMPOSED = 138,      // pffft_hip_dct_transform_batch: never the fused kernel (permutation / table kernel + transform_batch + its twin)
     AB_DCT_FUSED = 139,         // ... the fused register-tiled kernel wherever it is legal, whatever the measured default of the (size, kind) is
+    AB_MDCT_COMPOSED = 140,     // pffft_hip_mdct_*_batch: never the fused kernel (fold kernel + transform_batch + table / scatter kernel)
+    AB_MDCT_FUSED = 141,        // ... the fused register-tiled kernel wherever it is legal, whatever the measured default of the (size, entry) is
     AB_FAKE_DEVICE = 130,      // the calling thread counts as being on ANOTHER device than its current one (key + 64): exercises the per-device
                                 // replicas of a shared setup on a box with one GPU (tests/test_gpu_round6.py)
 };
