@@ -317,22 +317,26 @@ def _aligned(a, dtype):
     return out
 
 
-class Setup:
-    """PFFFT_Setup / PFFFTD_Setup.  Raises ValueError where pffft_new_setup returns NULL
-    (src/pffft_priv_impl.h:1066-1078,1105-1109)."""
+class _Handle:
+    """What the handle classes share: the library, the precision prefix of its entries, one constructor tail, close() / __del__, and the
+    checks of torch arguments.  A class names its C constructor and destructor (after the prefix) in _new / _destroy."""
 
-    def __init__(self, N: int, transform: int, dtype=np.float32):
-        self.N, self.transform_type, self.dtype = int(N), int(transform), np.dtype(dtype)
-        self._pfx = _pfx(dtype)
-        self._L = lib()
-        self.handle = getattr(self._L, f"{self._pfx}_new_setup")(self.N, self.transform_type)
+    _new = _destroy = ""
+    handle = None
+
+    def _fn(self, name):
+        return getattr(self._L, f"{self._pfx}_{name}")
+
+    def _open(self, pfx, *args, shown):
+        """handle = <pfx>_<_new>(*args); `shown` is the call as the ValueError words it where the library returns NULL."""
+        self._pfx, self._L = pfx, lib()
+        self.handle = self._fn(self._new)(*args)
         if not self.handle:
-            raise ValueError(f"pffft_new_setup({N}, {transform}) returned NULL")
-        self.vec_scalars = self.N * (2 if transform == COMPLEX else 1)
+            raise ValueError(f"{shown} returned NULL")
 
     def close(self):
         if getattr(self, "handle", None):
-            getattr(self._L, f"{self._pfx}_destroy_setup")(self.handle)
+            self._fn(self._destroy)(self.handle)
             self.handle = None
 
     def __del__(self):
@@ -341,15 +345,52 @@ class Setup:
         except Exception:
             pass
 
-    # ---------------- device (torch CUDA tensors): batched entries ----------------
-    def _stream(self):
+    @staticmethod
+    def _stream():
         import torch
         return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
-    def _tcheck(self, t):
+    def _torch_dtype(self):
         import torch
-        want = torch.float64 if self.dtype == np.float64 else torch.float32
-        assert t.is_cuda and t.dtype == want and t.is_contiguous(), "need contiguous CUDA tensor of the setup dtype"
+        return torch.float64 if self.dtype == np.float64 else torch.float32
+
+    def _whole_rows(self, t, row):
+        """The batch of a dense tensor of rows of `row` scalars."""
+        assert t.is_cuda and t.dtype == self._torch_dtype() and t.is_contiguous() and t.numel() % row == 0, \
+            "need a contiguous CUDA tensor of the setup dtype holding whole rows"
+        return t.numel() // row
+
+    def _dense_out(self, out, x, batch, row):
+        """out (None: a new [batch, row] tensor next to x), dense and of that size."""
+        import torch
+        if out is None:
+            out = torch.empty((batch, row), dtype=x.dtype, device=x.device)
+        assert out.is_cuda and out.dtype == x.dtype and out.is_contiguous() and out.numel() == batch * row
+        return out
+
+    def _complex_table(self, fn, *index_args, count, detail=True):
+        """`count` complex values of the setup's precision from the table reader fn(handle, *index_args, out) (host arithmetic only)."""
+        out = np.empty(2 * max(int(count), 0), dtype=self.dtype)
+        rc = getattr(self._L, fn)(self.handle, *index_args, out.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"{fn} failed ({rc})" + (f": {self._L.pffft_hip_last_error().decode()}" if detail else ""))
+        return out.view(np.complex128 if self.dtype == np.float64 else np.complex64)
+
+
+class Setup(_Handle):
+    """PFFFT_Setup / PFFFTD_Setup.  Raises ValueError where pffft_new_setup returns NULL
+    (src/pffft_priv_impl.h:1066-1078,1105-1109)."""
+
+    _new, _destroy = "new_setup", "destroy_setup"
+
+    def __init__(self, N: int, transform: int, dtype=np.float32):
+        self.N, self.transform_type, self.dtype = int(N), int(transform), np.dtype(dtype)
+        self._open(_pfx(dtype), self.N, self.transform_type, shown=f"pffft_new_setup({N}, {transform})")
+        self.vec_scalars = self.N * (2 if transform == COMPLEX else 1)
+
+    # ---------------- device (torch CUDA tensors): batched entries ----------------
+    def _tcheck(self, t):
+        assert t.is_cuda and t.dtype == self._torch_dtype() and t.is_contiguous(), "need contiguous CUDA tensor of the setup dtype"
         assert t.numel() % self.vec_scalars == 0
         return t.numel() // self.vec_scalars
 
@@ -360,9 +401,8 @@ class Setup:
         if out is None:
             out = torch.empty_like(x)
         assert self._tcheck(out) == batch
-        fn = getattr(self._L, f"{self._pfx}_hip_transform_batch")
-        _check(fn(self.handle, x.data_ptr(), out.data_ptr(), batch, direction, int(bool(ordered)), self._stream()),
-               "hip_transform_batch")
+        _check(self._fn("hip_transform_batch")(self.handle, x.data_ptr(), out.data_ptr(), batch, direction, int(bool(ordered)),
+                                               self._stream()), "hip_transform_batch")
         return out
 
     def shift_transform_batch(self, x, rate, phase_rad=0.0, out=None, ordered=False):
@@ -383,16 +423,15 @@ class Setup:
         batch = self._tcheck(x)
         if out is None:
             out = torch.empty_like(x)
-        fn = getattr(self._L, f"{self._pfx}_hip_zreorder_batch")
-        _check(fn(self.handle, x.data_ptr(), out.data_ptr(), batch, direction, self._stream()), "hip_zreorder_batch")
+        _check(self._fn("hip_zreorder_batch")(self.handle, x.data_ptr(), out.data_ptr(), batch, direction, self._stream()),
+               "hip_zreorder_batch")
         return out
 
     def zconvolve_batch(self, a, b, ab, scaling, accumulate=True, b_broadcast=False):
         batch = self._tcheck(a)
         self._tcheck(ab)
-        fn = getattr(self._L, f"{self._pfx}_hip_zconvolve_batch")
-        _check(fn(self.handle, a.data_ptr(), b.data_ptr(), ab.data_ptr(), scaling, batch, int(bool(accumulate)),
-                  int(bool(b_broadcast)), self._stream()), "hip_zconvolve_batch")
+        _check(self._fn("hip_zconvolve_batch")(self.handle, a.data_ptr(), b.data_ptr(), ab.data_ptr(), scaling, batch,
+                                               int(bool(accumulate)), int(bool(b_broadcast)), self._stream()), "hip_zconvolve_batch")
         return ab
 
     def convolve_batch(self, x, H, out=None, scaling=1.0, accumulate=False):
@@ -407,20 +446,73 @@ class Setup:
         bc = H.numel() == self.vec_scalars
         assert bc or H.numel() == x.numel()
         assert H.is_cuda and H.dtype == x.dtype and H.is_contiguous()
-        fn = getattr(self._L, f"{self._pfx}_hip_convolve_batch")
-        _check(fn(self.handle, x.data_ptr(), H.data_ptr(), out.data_ptr(), scaling, batch, int(bool(accumulate)), int(bc),
-                  self._stream()), "hip_convolve_batch")
+        _check(self._fn("hip_convolve_batch")(self.handle, x.data_ptr(), H.data_ptr(), out.data_ptr(), scaling, batch,
+                                              int(bool(accumulate)), int(bc), self._stream()), "hip_convolve_batch")
         return out
 
+    # the frame family: analysis = signal rows -> output rows at a pitch, synthesis = spectrum rows at a pitch -> signal rows
     def _frames_rows(self, t, what):
         """(nsignals, row stride in scalars, scalars per row) of a 1-D signal / 2-D [nsignals, scalars] tensor."""
-        import torch
-        want = torch.float64 if self.dtype == np.float64 else torch.float32
-        assert t.is_cuda and t.dtype == want and t.dim() in (1, 2) and t.stride(-1) == 1, \
+        assert t.is_cuda and t.dtype == self._torch_dtype() and t.dim() in (1, 2) and t.stride(-1) == 1, \
             f"{what}: 1-D or 2-D CUDA tensor of the setup dtype with unit stride along the samples"
         if t.dim() == 1:
             return 1, 0, t.shape[0]
         return t.shape[0], (t.stride(0) if t.shape[0] > 1 else 0), t.shape[1]
+
+    def _spp(self) -> int:
+        return 2 if self.transform_type == COMPLEX else 1
+
+    def _analysis_in(self, signal, hop, nframes, span):
+        """(nsignals, signal stride, nframes) of frames of `span` samples every `hop`; nframes None = what the signal holds."""
+        nsig, sstride, scalars = self._frames_rows(signal, "signal")
+        samples = scalars // self._spp()
+        if nframes is None:
+            assert samples >= span, "the signal holds no frame"
+            nframes = (samples - span) // hop + 1
+        assert nframes == 0 or (nframes - 1) * hop + span <= samples, "the signal is shorter than its frames"
+        return nsig, sstride, nframes
+
+    @staticmethod
+    def _rows_out(out, signal, nsig, rows, row, name):
+        """(out, its row pitch): out [nsignals,] rows, row] next to `signal` (allocated when None), row v of `name` at v * pitch."""
+        import torch
+        if out is None:
+            out = torch.empty((nsig, rows, row) if signal.dim() == 2 else (rows, row), dtype=signal.dtype, device=signal.device)
+        assert out.dtype == signal.dtype and out.is_cuda and out.stride(-1) == 1 and out.shape[-1] == row and out.shape[-2] == rows
+        assert out.dim() == 2 or (out.dim() == 3 and out.shape[0] == nsig)
+        pitch = out.stride(-2) if rows > 1 else (out.stride(0) if out.dim() == 3 and nsig > 1 else row)
+        assert out.dim() == 2 or nsig == 1 or out.stride(0) == rows * pitch, f"{name} is written at v * pitch"
+        return out, pitch
+
+    def _synthesis_in(self, spectra):
+        """(nsignals, nframes, row pitch) of spectra [nsignals,] nframes, N or 2N scalars]."""
+        assert spectra.is_cuda and spectra.dim() in (2, 3) and spectra.stride(-1) == 1 and spectra.shape[-1] == self.vec_scalars
+        nframes = spectra.shape[-2]
+        nsig = spectra.shape[0] if spectra.dim() == 3 else 1
+        pitch = spectra.stride(-2) if nframes > 1 else (spectra.stride(0) if spectra.dim() == 3 and nsig > 1 else self.vec_scalars)
+        assert spectra.dim() == 2 or nsig == 1 or spectra.stride(0) == nframes * pitch
+        return nsig, nframes, pitch
+
+    def _signal_out(self, out, spectra, nsig, scalars):
+        """(out, its signal stride): out [nsignals,] >= scalars] next to `spectra` (allocated when None)."""
+        import torch
+        if out is None:
+            out = torch.empty((nsig, scalars) if spectra.dim() == 3 else (scalars,), dtype=spectra.dtype, device=spectra.device)
+        osig, ostride, oscalars = self._frames_rows(out, "out")
+        assert osig == nsig and oscalars >= scalars
+        return out, ostride
+
+    def _window_ptr(self, window, like):
+        if window is None:
+            return None
+        assert window.is_cuda and window.dtype == like.dtype and window.is_contiguous() and window.numel() == self.N
+        return window.data_ptr()
+
+    def _taps(self, prototype, like):
+        assert prototype.is_cuda and prototype.dtype == like.dtype and prototype.is_contiguous() and prototype.dim() == 1
+        taps = prototype.numel() // self.N
+        assert taps >= 1 and taps * self.N == prototype.numel(), "the prototype holds taps * N coefficients"
+        return taps
 
     def frames_out_row(self, output="internal") -> int:
         """Scalars per output row of frames_transform_batch."""
@@ -432,106 +524,49 @@ class Setup:
         """pffft_hip_frames_transform_batch: frames of N samples every `hop` samples of `signal` (1-D, or 2-D [nsignals, scalars] with
         the row stride taken from the tensor; complex setups: interleaved pairs), times `window` (N scalars, None = none), forward
         transformed.  Returns [nsignals,] nframes, row]; `out` may have padded rows (its stride(-2) is the row pitch)."""
-        import torch
-        spp = 2 if self.transform_type == COMPLEX else 1
-        nsig, sstride, scalars = self._frames_rows(signal, "signal")
-        samples = scalars // spp
-        if nframes is None:
-            assert samples >= self.N, "the signal holds no frame"
-            nframes = (samples - self.N) // hop + 1
-        assert nframes == 0 or (nframes - 1) * hop + self.N <= samples, "the signal is shorter than its frames"
-        row = self.frames_out_row(output)
-        if out is None:
-            out = torch.empty((nsig, nframes, row) if signal.dim() == 2 else (nframes, row), dtype=signal.dtype, device=signal.device)
-        assert out.dtype == signal.dtype and out.is_cuda and out.stride(-1) == 1 and out.shape[-1] == row and out.shape[-2] == nframes
-        assert out.dim() == 2 or (out.dim() == 3 and out.shape[0] == nsig)
-        pitch = out.stride(-2) if nframes > 1 else (out.stride(0) if out.dim() == 3 and nsig > 1 else row)
-        assert out.dim() == 2 or nsig == 1 or out.stride(0) == nframes * pitch, "frame v = i nframes + f is written at v * pitch"
-        if window is not None:
-            assert window.is_cuda and window.dtype == signal.dtype and window.is_contiguous() and window.numel() == self.N
-        fn = getattr(self._L, f"{self._pfx}_hip_frames_transform_batch")
-        _check(fn(self.handle, signal.data_ptr(), sstride, nsig, nframes, hop, window.data_ptr() if window is not None else None,
-                  out.data_ptr(), pitch, FRAMES_OUTPUTS[output], self._stream()), "hip_frames_transform_batch")
+        nsig, sstride, nframes = self._analysis_in(signal, hop, nframes, self.N)
+        out, pitch = self._rows_out(out, signal, nsig, nframes, self.frames_out_row(output), "frame v = i nframes + f")
+        _check(self._fn("hip_frames_transform_batch")(self.handle, signal.data_ptr(), sstride, nsig, nframes, hop,
+                                                      self._window_ptr(window, signal), out.data_ptr(), pitch, FRAMES_OUTPUTS[output],
+                                                      self._stream()), "hip_frames_transform_batch")
         return out
 
     def frames_psd_batch(self, signal, hop, nframes=None, window=None, navg=0, scaling=1.0, out=None):
         """pffft_hip_frames_psd_batch: |X|^2 of the frames of frames_transform_batch, averaged over groups of `navg` consecutive frames
         (0 = every frame of a signal: Welch) in the documented order and multiplied once by `scaling`.  Returns [nsignals,] nframes / navg,
         P]; `out` may have padded rows (its stride(-2) is the row pitch)."""
-        import torch
-        spp = 2 if self.transform_type == COMPLEX else 1
-        nsig, sstride, scalars = self._frames_rows(signal, "signal")
-        samples = scalars // spp
-        if nframes is None:
-            assert samples >= self.N, "the signal holds no frame"
-            nframes = (samples - self.N) // hop + 1
-        assert nframes == 0 or (nframes - 1) * hop + self.N <= samples, "the signal is shorter than its frames"
+        nsig, sstride, nframes = self._analysis_in(signal, hop, nframes, self.N)
         per = navg if navg else nframes
         assert nframes == 0 or nframes % per == 0, "nframes must be a multiple of navg"
         groups = nframes // per if nframes else 0
-        row = self.frames_out_row("power")
-        if out is None:
-            out = torch.empty((nsig, groups, row) if signal.dim() == 2 else (groups, row), dtype=signal.dtype, device=signal.device)
-        assert out.dtype == signal.dtype and out.is_cuda and out.stride(-1) == 1 and out.shape[-1] == row and out.shape[-2] == groups
-        assert out.dim() == 2 or (out.dim() == 3 and out.shape[0] == nsig)
-        pitch = out.stride(-2) if groups > 1 else (out.stride(0) if out.dim() == 3 and nsig > 1 else row)
-        assert out.dim() == 2 or nsig == 1 or out.stride(0) == groups * pitch, "row v = i groups + g is written at v * pitch"
-        if window is not None:
-            assert window.is_cuda and window.dtype == signal.dtype and window.is_contiguous() and window.numel() == self.N
-        fn = getattr(self._L, f"{self._pfx}_hip_frames_psd_batch")
-        _check(fn(self.handle, signal.data_ptr(), sstride, nsig, nframes, hop, window.data_ptr() if window is not None else None,
-                  int(navg), float(scaling), out.data_ptr(), pitch, self._stream()), "hip_frames_psd_batch")
+        out, pitch = self._rows_out(out, signal, nsig, groups, self.frames_out_row("power"), "row v = i groups + g")
+        _check(self._fn("hip_frames_psd_batch")(self.handle, signal.data_ptr(), sstride, nsig, nframes, hop,
+                                                self._window_ptr(window, signal), int(navg), float(scaling), out.data_ptr(), pitch,
+                                                self._stream()), "hip_frames_psd_batch")
         return out
 
     def pfb_transform_batch(self, signal, hop, prototype, nframes=None, out=None, output="internal"):
         """pffft_hip_pfb_transform_batch: polyphase filter-bank analysis.  `prototype` holds taps * N coefficients; frame f folds the
         taps * N samples from f * hop on onto N points (u[j] = sum_p prototype[p N + j] x[f hop + p N + j]) and forward-transforms them.
         Tensor conventions of frames_transform_batch: returns [nsignals,] nframes, row]; `out` may have padded rows."""
-        import torch
-        spp = 2 if self.transform_type == COMPLEX else 1
-        nsig, sstride, scalars = self._frames_rows(signal, "signal")
-        samples = scalars // spp
-        assert prototype.is_cuda and prototype.dtype == signal.dtype and prototype.is_contiguous() and prototype.dim() == 1
-        taps = prototype.numel() // self.N
-        assert taps >= 1 and taps * self.N == prototype.numel(), "the prototype holds taps * N coefficients"
-        span = taps * self.N
-        if nframes is None:
-            assert samples >= span, "the signal holds no frame"
-            nframes = (samples - span) // hop + 1
-        assert nframes == 0 or (nframes - 1) * hop + span <= samples, "the signal is shorter than its frames"
-        row = self.frames_out_row(output)
-        if out is None:
-            out = torch.empty((nsig, nframes, row) if signal.dim() == 2 else (nframes, row), dtype=signal.dtype, device=signal.device)
-        assert out.dtype == signal.dtype and out.is_cuda and out.stride(-1) == 1 and out.shape[-1] == row and out.shape[-2] == nframes
-        assert out.dim() == 2 or (out.dim() == 3 and out.shape[0] == nsig)
-        pitch = out.stride(-2) if nframes > 1 else (out.stride(0) if out.dim() == 3 and nsig > 1 else row)
-        assert out.dim() == 2 or nsig == 1 or out.stride(0) == nframes * pitch, "frame v = i nframes + f is written at v * pitch"
-        fn = getattr(self._L, f"{self._pfx}_hip_pfb_transform_batch")
-        _check(fn(self.handle, signal.data_ptr(), sstride, nsig, nframes, hop, prototype.data_ptr(), taps, out.data_ptr(), pitch,
-                  FRAMES_OUTPUTS[output], self._stream()), "hip_pfb_transform_batch")
+        self._frames_rows(signal, "signal")                 # the signal is checked ahead of the prototype
+        taps = self._taps(prototype, signal)
+        nsig, sstride, nframes = self._analysis_in(signal, hop, nframes, taps * self.N)
+        out, pitch = self._rows_out(out, signal, nsig, nframes, self.frames_out_row(output), "frame v = i nframes + f")
+        _check(self._fn("hip_pfb_transform_batch")(self.handle, signal.data_ptr(), sstride, nsig, nframes, hop, prototype.data_ptr(), taps,
+                                                   out.data_ptr(), pitch, FRAMES_OUTPUTS[output], self._stream()),
+               "hip_pfb_transform_batch")
         return out
 
     def frames_overlap_add_batch(self, spectra, hop, window=None, scaling=1.0, out=None, ordered=False):
         """pffft_hip_frames_overlap_add_batch: spectra [nsignals,] nframes, N or 2N scalars] (stride(-2) = row pitch) are backward
         transformed (unscaled) and overlap-added every `hop` samples: out[s] = scaling * sum_f window[s - f hop] y_f[s - f hop].
         Returns [nsignals,] (nframes - 1) hop + N samples]; normalising by the window's overlap sum is the caller's `scaling`."""
-        import torch
-        spp = 2 if self.transform_type == COMPLEX else 1
-        assert spectra.is_cuda and spectra.dim() in (2, 3) and spectra.stride(-1) == 1 and spectra.shape[-1] == self.vec_scalars
-        nframes = spectra.shape[-2]
-        nsig = spectra.shape[0] if spectra.dim() == 3 else 1
-        pitch = spectra.stride(-2) if nframes > 1 else (spectra.stride(0) if spectra.dim() == 3 and nsig > 1 else self.vec_scalars)
-        assert spectra.dim() == 2 or nsig == 1 or spectra.stride(0) == nframes * pitch
-        scalars = ((nframes - 1) * hop + self.N) * spp if nframes else 0
-        if out is None:
-            out = torch.empty((nsig, scalars) if spectra.dim() == 3 else (scalars,), dtype=spectra.dtype, device=spectra.device)
-        osig, ostride, oscalars = self._frames_rows(out, "out")
-        assert osig == nsig and oscalars >= scalars
-        if window is not None:
-            assert window.is_cuda and window.dtype == spectra.dtype and window.is_contiguous() and window.numel() == self.N
-        fn = getattr(self._L, f"{self._pfx}_hip_frames_overlap_add_batch")
-        _check(fn(self.handle, spectra.data_ptr(), pitch, nsig, nframes, hop, window.data_ptr() if window is not None else None,
-                  float(scaling), out.data_ptr(), ostride, int(bool(ordered)), self._stream()), "hip_frames_overlap_add_batch")
+        nsig, nframes, pitch = self._synthesis_in(spectra)
+        out, ostride = self._signal_out(out, spectra, nsig, ((nframes - 1) * hop + self.N) * self._spp() if nframes else 0)
+        _check(self._fn("hip_frames_overlap_add_batch")(self.handle, spectra.data_ptr(), pitch, nsig, nframes, hop,
+                                                        self._window_ptr(window, spectra), float(scaling), out.data_ptr(), ostride,
+                                                        int(bool(ordered)), self._stream()), "hip_frames_overlap_add_batch")
         return out
 
     def pfb_synthesis_batch(self, spectra, hop, prototype, scaling=1.0, out=None, ordered=False):
@@ -539,24 +574,12 @@ class Setup:
         pitch) are backward transformed (unscaled), periodically extended over the taps * N coefficients of `prototype` and overlap-added
         every `hop` samples: out[s] = scaling * sum_f prototype[s - f hop] y_f[(s - f hop) mod N].  Tensor conventions of
         frames_overlap_add_batch: returns [nsignals,] ((nframes - 1) hop + taps N) spp scalars]; `out` may have a padded row stride."""
-        import torch
-        spp = 2 if self.transform_type == COMPLEX else 1
-        assert spectra.is_cuda and spectra.dim() in (2, 3) and spectra.stride(-1) == 1 and spectra.shape[-1] == self.vec_scalars
-        assert prototype.is_cuda and prototype.dtype == spectra.dtype and prototype.is_contiguous() and prototype.dim() == 1
-        taps = prototype.numel() // self.N
-        assert taps >= 1 and taps * self.N == prototype.numel(), "the prototype holds taps * N coefficients"
-        nframes = spectra.shape[-2]
-        nsig = spectra.shape[0] if spectra.dim() == 3 else 1
-        pitch = spectra.stride(-2) if nframes > 1 else (spectra.stride(0) if spectra.dim() == 3 and nsig > 1 else self.vec_scalars)
-        assert spectra.dim() == 2 or nsig == 1 or spectra.stride(0) == nframes * pitch
-        scalars = ((nframes - 1) * hop + taps * self.N) * spp if nframes else 0
-        if out is None:
-            out = torch.empty((nsig, scalars) if spectra.dim() == 3 else (scalars,), dtype=spectra.dtype, device=spectra.device)
-        osig, ostride, oscalars = self._frames_rows(out, "out")
-        assert osig == nsig and oscalars >= scalars
-        fn = getattr(self._L, f"{self._pfx}_hip_pfb_synthesis_batch")
-        _check(fn(self.handle, spectra.data_ptr(), pitch, nsig, nframes, hop, prototype.data_ptr(), taps, float(scaling), out.data_ptr(),
-                  ostride, int(bool(ordered)), self._stream()), "hip_pfb_synthesis_batch")
+        nsig, nframes, pitch = self._synthesis_in(spectra)
+        taps = self._taps(prototype, spectra)
+        out, ostride = self._signal_out(out, spectra, nsig, ((nframes - 1) * hop + taps * self.N) * self._spp() if nframes else 0)
+        _check(self._fn("hip_pfb_synthesis_batch")(self.handle, spectra.data_ptr(), pitch, nsig, nframes, hop, prototype.data_ptr(), taps,
+                                                   float(scaling), out.data_ptr(), ostride, int(bool(ordered)), self._stream()),
+               "hip_pfb_synthesis_batch")
         return out
 
     # ---------------- host (numpy): the legacy single-vector entries ----------------
@@ -604,29 +627,10 @@ class Setup:
         return pab
 
 
-class AnySetup:
-    """PFFFT_HIP_AnySetup / PFFFTD_HIP_AnySetup: complex transforms of any length 1 <= N <= 2^25 (include/pffft_hip.h).  Raises ValueError
-    where pffft_hip_any_new_setup returns NULL.  Rows are N interleaved complex values (2N scalars), dense."""
+class _AnyHandle(_Handle):
+    """What AnySetup and AnyRealSetup share: the destroy entry, the convolution length, the route and the chirp."""
 
-    def __init__(self, N: int, transform: int = COMPLEX, dtype=np.float32):
-        self.N, self.transform_type, self.dtype = int(N), int(transform), np.dtype(dtype)
-        self._pfx = _pfx(dtype)
-        self._L = lib()
-        self.handle = getattr(self._L, f"{self._pfx}_hip_any_new_setup")(self.N, self.transform_type)
-        if not self.handle:
-            raise ValueError(f"pffft_hip_any_new_setup({N}, {transform}) returned NULL")
-        self.vec_scalars = 2 * self.N
-
-    def close(self):
-        if getattr(self, "handle", None):
-            getattr(self._L, f"{self._pfx}_hip_any_destroy_setup")(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _destroy = "hip_any_destroy_setup"
 
     @property
     def conv_size(self) -> int:
@@ -637,114 +641,74 @@ class AnySetup:
     def route(self) -> str:
         return any_route(self)
 
+    def _chirp(self) -> np.ndarray:
+        return self._complex_table("pffft_hip_any_chirp", count=self.N, detail=False)
+
+    def _run(self, x, out, batch, direction):
+        _check(self._fn("hip_any_transform_batch")(self.handle, x.data_ptr(), out.data_ptr(), batch, direction, self._stream()),
+               "hip_any_transform_batch")
+        return out
+
+
+class AnySetup(_AnyHandle):
+    """PFFFT_HIP_AnySetup / PFFFTD_HIP_AnySetup: complex transforms of any length 1 <= N <= 2^25 (include/pffft_hip.h).  Raises ValueError
+    where pffft_hip_any_new_setup returns NULL.  Rows are N interleaved complex values (2N scalars), dense."""
+
+    _new = "hip_any_new_setup"
+
+    def __init__(self, N: int, transform: int = COMPLEX, dtype=np.float32):
+        self.N, self.transform_type, self.dtype = int(N), int(transform), np.dtype(dtype)
+        self._open(_pfx(dtype), self.N, self.transform_type, shown=f"pffft_hip_any_new_setup({N}, {transform})")
+        self.vec_scalars = 2 * self.N
+
     def chirp(self) -> np.ndarray:
         """pffft_hip_any_chirp: w[n] = exp(-j pi (n^2 mod 2N) / N) as a complex array of the setup's precision (host arithmetic only)."""
-        out = np.empty(2 * self.N, dtype=self.dtype)
-        rc = self._L.pffft_hip_any_chirp(self.handle, out.ctypes.data)
-        if rc != 0:
-            raise RuntimeError(f"pffft_hip_any_chirp failed ({rc})")
-        return out.view(np.complex128 if self.dtype == np.float64 else np.complex64)
+        return self._chirp()
 
     def transform_batch(self, x, out=None, direction=FORWARD):
         """x: CUDA tensor of the setup's dtype holding `batch` rows of 2N scalars; only the extent has to be dense (a view that starts
         anywhere on the grid of complex values is accepted).  out may be x (in place)."""
         import torch
-        want = torch.float64 if self.dtype == np.float64 else torch.float32
-        assert x.is_cuda and x.dtype == want and x.is_contiguous() and x.numel() % self.vec_scalars == 0, \
-            "need a contiguous CUDA tensor of the setup dtype holding whole rows"
-        batch = x.numel() // self.vec_scalars
+        batch = self._whole_rows(x, self.vec_scalars)
         if out is None:
             out = torch.empty_like(x)
-        assert out.is_cuda and out.dtype == want and out.is_contiguous() and out.numel() == x.numel()
-        fn = getattr(self._L, f"{self._pfx}_hip_any_transform_batch")
-        _check(fn(self.handle, x.data_ptr(), out.data_ptr(), batch, direction, C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-               "hip_any_transform_batch")
-        return out
+        return self._run(x, self._dense_out(out, x, batch, self.vec_scalars), batch, direction)
 
 
-class AnyRealSetup:
+class AnyRealSetup(_AnyHandle):
     """pffft[d]_hip_any_new_real_setup: real transforms of any length 1 <= N <= 2^25 with half-spectrum I/O (include/pffft_hip.h).  FORWARD
     takes rows of N reals to rows of bins = N // 2 + 1 interleaved complex values (numpy's rfft), BACKWARD the reverse, unscaled (irfft . N).
     Raises ValueError where the constructor returns NULL."""
 
+    _new = "hip_any_new_real_setup"
+
     def __init__(self, N: int, dtype=np.float32):
         self.N, self.dtype = int(N), np.dtype(dtype)
-        self._pfx = _pfx(dtype)
-        self._L = lib()
-        self.handle = getattr(self._L, f"{self._pfx}_hip_any_new_real_setup")(self.N)
-        if not self.handle:
-            raise ValueError(f"pffft_hip_any_new_real_setup({N}) returned NULL")
+        self._open(_pfx(dtype), self.N, shown=f"pffft_hip_any_new_real_setup({N})")
         self.bins = int(self._L.pffft_hip_any_bins(self.handle))
-
-    def close(self):
-        if getattr(self, "handle", None):
-            getattr(self._L, f"{self._pfx}_hip_any_destroy_setup")(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def conv_size(self) -> int:
-        """The convolution length M (0 on the direct route)."""
-        return int(self._L.pffft_hip_any_conv_size(self.handle))
-
-    @property
-    def route(self) -> str:
-        return any_route(self)
 
     def chirp(self) -> np.ndarray:
         """pffft_hip_any_chirp: the N chirp values, as for a complex setup of the same N."""
-        out = np.empty(2 * self.N, dtype=self.dtype)
-        rc = self._L.pffft_hip_any_chirp(self.handle, out.ctypes.data)
-        if rc != 0:
-            raise RuntimeError(f"pffft_hip_any_chirp failed ({rc})")
-        return out.view(np.complex128 if self.dtype == np.float64 else np.complex64)
+        return self._chirp()
 
     def transform_batch(self, x, out=None, direction=FORWARD):
         """x: contiguous CUDA tensor of the setup's dtype holding `batch` rows of N scalars (FORWARD) or 2 * bins scalars (BACKWARD); the
         result has `batch` rows of 2 * bins (FORWARD) or N (BACKWARD) scalars.  out must not overlap x."""
-        import torch
-        want = torch.float64 if self.dtype == np.float64 else torch.float32
         rin, rout = (self.N, 2 * self.bins) if direction == FORWARD else (2 * self.bins, self.N)
-        assert x.is_cuda and x.dtype == want and x.is_contiguous() and x.numel() % rin == 0, \
-            "need a contiguous CUDA tensor of the setup dtype holding whole rows"
-        batch = x.numel() // rin
-        if out is None:
-            out = torch.empty((batch, rout), dtype=want, device=x.device)
-        assert out.is_cuda and out.dtype == want and out.is_contiguous() and out.numel() == batch * rout
-        fn = getattr(self._L, f"{self._pfx}_hip_any_transform_batch")
-        _check(fn(self.handle, x.data_ptr(), out.data_ptr(), batch, direction, C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-               "hip_any_transform_batch")
-        return out
+        batch = self._whole_rows(x, rin)
+        return self._run(x, self._dense_out(out, x, batch, rout), batch, direction)
 
 
-class ZoomSetup:
+class ZoomSetup(_Handle):
     """PFFFT_HIP_ZoomSetup / PFFFTD_HIP_ZoomSetup: K spectral lines from f0 in steps of df (cycles per sample) of rows of N complex samples
     (include/pffft_hip.h).  Raises ValueError where pffft_hip_zoom_new_setup returns NULL.  Rows of N interleaved complex values in, rows of
     K out, dense."""
 
+    _new, _destroy = "hip_zoom_new_setup", "hip_zoom_destroy_setup"
+
     def __init__(self, N: int, K: int, f0: float, df: float, dtype=np.float32):
         self.N, self.K, self.f0, self.df, self.dtype = int(N), int(K), float(f0), float(df), np.dtype(dtype)
-        self._pfx = _pfx(dtype)
-        self._L = lib()
-        self.handle = getattr(self._L, f"{self._pfx}_hip_zoom_new_setup")(self.N, self.K, self.f0, self.df)
-        if not self.handle:
-            raise ValueError(f"pffft_hip_zoom_new_setup({N}, {K}, {f0}, {df}) returned NULL")
-
-    def close(self):
-        if getattr(self, "handle", None):
-            getattr(self._L, f"{self._pfx}_hip_zoom_destroy_setup")(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._open(_pfx(dtype), self.N, self.K, self.f0, self.df, shown=f"pffft_hip_zoom_new_setup({N}, {K}, {f0}, {df})")
 
     @property
     def conv_size(self) -> int:
@@ -760,25 +724,14 @@ class ZoomSetup:
         (which = 1, max(N, K) entries) as a complex array of the setup's precision (host arithmetic only)."""
         if count is None:
             count = (self.N if which == 0 else max(self.N, self.K)) - first
-        out = np.empty(2 * max(int(count), 0), dtype=self.dtype)
-        rc = self._L.pffft_hip_zoom_table(self.handle, int(which), int(first), int(count), out.ctypes.data)
-        if rc != 0:
-            raise RuntimeError(f"pffft_hip_zoom_table failed ({rc}): {self._L.pffft_hip_last_error().decode()}")
-        return out.view(np.complex128 if self.dtype == np.float64 else np.complex64)
+        return self._complex_table("pffft_hip_zoom_table", int(which), int(first), int(count), count=count)
 
     def transform_batch(self, x, out=None, direction=FORWARD):
         """x: contiguous CUDA tensor of the setup's dtype holding `batch` rows of 2N scalars; the result has `batch` rows of 2K scalars.
         out must not overlap x."""
-        import torch
-        want = torch.float64 if self.dtype == np.float64 else torch.float32
-        assert x.is_cuda and x.dtype == want and x.is_contiguous() and x.numel() % (2 * self.N) == 0, \
-            "need a contiguous CUDA tensor of the setup dtype holding whole rows"
-        batch = x.numel() // (2 * self.N)
-        if out is None:
-            out = torch.empty((batch, 2 * self.K), dtype=want, device=x.device)
-        assert out.is_cuda and out.dtype == want and out.is_contiguous() and out.numel() == batch * 2 * self.K
-        fn = getattr(self._L, f"{self._pfx}_hip_zoom_transform_batch")
-        _check(fn(self.handle, x.data_ptr(), out.data_ptr(), batch, direction, C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+        batch = self._whole_rows(x, 2 * self.N)
+        out = self._dense_out(out, x, batch, 2 * self.K)
+        _check(self._fn("hip_zoom_transform_batch")(self.handle, x.data_ptr(), out.data_ptr(), batch, direction, self._stream()),
                "hip_zoom_transform_batch")
         return out
 
@@ -787,31 +740,18 @@ DCT_KINDS = {"dct2": 0, "dct3": 1, "dst2": 2, "dst3": 3}      # pffft_hip_dct_ki
 DCT_NORMS = {None: 0, "none": 0, "ortho": 1}                  # pffft_hip_dct_norm_t
 
 
-class DctSetup:
+class DctSetup(_Handle):
     """PFFFT_HIP_DctSetup / PFFFTD_HIP_DctSetup: cosine / sine transforms of type II / III of rows of N reals (include/pffft_hip.h;
     scipy.fft.dct / dst with type = 2 / 3).  kind: "dct2" / "dct3" / "dst2" / "dst3" (or the enum value), norm: None / "ortho".  Raises
     ValueError where pffft_hip_dct_new_setup returns NULL."""
+
+    _new, _destroy = "hip_dct_new_setup", "hip_dct_destroy_setup"
 
     def __init__(self, N: int, kind, norm=None, dtype=np.float32):
         self.N, self.dtype = int(N), np.dtype(dtype)
         self.kind = DCT_KINDS[kind] if kind in DCT_KINDS else int(kind)
         self.norm = DCT_NORMS[norm] if norm in DCT_NORMS else int(norm)
-        self._pfx = _pfx(dtype)
-        self._L = lib()
-        self.handle = getattr(self._L, f"{self._pfx}_hip_dct_new_setup")(self.N, self.kind, self.norm)
-        if not self.handle:
-            raise ValueError(f"pffft_hip_dct_new_setup({N}, {kind}, {norm}) returned NULL")
-
-    def close(self):
-        if getattr(self, "handle", None):
-            getattr(self._L, f"{self._pfx}_hip_dct_destroy_setup")(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._open(_pfx(dtype), self.N, self.kind, self.norm, shown=f"pffft_hip_dct_new_setup({N}, {kind}, {norm})")
 
     @property
     def route(self) -> str:
@@ -823,24 +763,13 @@ class DctSetup:
         (host arithmetic only)."""
         if count is None:
             count = self.N // 2 + 1 - first
-        out = np.empty(2 * max(int(count), 0), dtype=self.dtype)
-        rc = self._L.pffft_hip_dct_table(self.handle, int(first), int(count), out.ctypes.data)
-        if rc != 0:
-            raise RuntimeError(f"pffft_hip_dct_table failed ({rc}): {self._L.pffft_hip_last_error().decode()}")
-        return out.view(np.complex128 if self.dtype == np.float64 else np.complex64)
+        return self._complex_table("pffft_hip_dct_table", int(first), int(count), count=count)
 
     def transform_batch(self, x, out=None):
         """x: contiguous CUDA tensor of the setup's dtype holding `batch` rows of N scalars; the result has the same shape.  out may be x."""
-        import torch
-        want = torch.float64 if self.dtype == np.float64 else torch.float32
-        assert x.is_cuda and x.dtype == want and x.is_contiguous() and x.numel() % self.N == 0, \
-            "need a contiguous CUDA tensor of the setup dtype holding whole rows"
-        batch = x.numel() // self.N
-        if out is None:
-            out = torch.empty((batch, self.N), dtype=want, device=x.device)
-        assert out.is_cuda and out.dtype == want and out.is_contiguous() and out.numel() == batch * self.N
-        fn = getattr(self._L, f"{self._pfx}_hip_dct_transform_batch")
-        _check(fn(self.handle, x.data_ptr(), out.data_ptr(), batch, C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+        batch = self._whole_rows(x, self.N)
+        out = self._dense_out(out, x, batch, self.N)
+        _check(self._fn("hip_dct_transform_batch")(self.handle, x.data_ptr(), out.data_ptr(), batch, self._stream()),
                "hip_dct_transform_batch")
         return out
 
@@ -848,29 +777,16 @@ class DctSetup:
 MDCT_WHAT = {"dct4": 0, "mdct": 1, "imdct": 2}      # `what` of pffft_hip_mdct_route
 
 
-class MdctSetup:
+class MdctSetup(_Handle):
     """PFFFT_HIP_MdctSetup / PFFFTD_HIP_MdctSetup: MDCT / IMDCT frames of 2M samples at hop M (M coefficients per frame) and the type-IV
     cosine transform of rows of M reals (include/pffft_hip.h).  Raises ValueError where pffft_hip_mdct_new_setup returns NULL.  Every
     method takes CUDA tensors of the setup's dtype (and returns one), or numpy arrays, which go through the device (and return an array)."""
 
+    _new, _destroy = "hip_mdct_new_setup", "hip_mdct_destroy_setup"
+
     def __init__(self, M: int, dtype=np.float32):
         self.M, self.dtype = int(M), np.dtype(dtype)
-        self._pfx = _pfx(dtype)
-        self._L = lib()
-        self.handle = getattr(self._L, f"{self._pfx}_hip_mdct_new_setup")(self.M)
-        if not self.handle:
-            raise ValueError(f"pffft_hip_mdct_new_setup({M}) returned NULL")
-
-    def close(self):
-        if getattr(self, "handle", None):
-            getattr(self._L, f"{self._pfx}_hip_mdct_destroy_setup")(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._open(_pfx(dtype), self.M, shown=f"pffft_hip_mdct_new_setup({M})")
 
     def route(self, what) -> str:
         """pffft_hip_mdct_route: "fused" / "composed" for what = 0 / "dct4", 1 / "mdct", 2 / "imdct" under the calling thread's selector
@@ -882,27 +798,17 @@ class MdctSetup:
         arithmetic only)."""
         if count is None:
             count = self.M // 2 - first
-        out = np.empty(2 * max(int(count), 0), dtype=self.dtype)
-        rc = self._L.pffft_hip_mdct_table(self.handle, int(which), int(first), int(count), out.ctypes.data)
-        if rc != 0:
-            raise RuntimeError(f"pffft_hip_mdct_table failed ({rc}): {self._L.pffft_hip_last_error().decode()}")
-        return out.view(np.complex128 if self.dtype == np.float64 else np.complex64)
+        return self._complex_table("pffft_hip_mdct_table", int(which), int(first), int(count), count=count)
 
     def _dev(self, x):
         """(CUDA tensor of x, x was a numpy array)"""
         import torch
-        want = torch.float64 if self.dtype == np.float64 else torch.float32
         if x is None:
             return None, False
         if _is_torch(x):
-            assert x.is_cuda and x.dtype == want, "need a CUDA tensor of the setup dtype"
+            assert x.is_cuda and x.dtype == self._torch_dtype(), "need a CUDA tensor of the setup dtype"
             return x, False
         return torch.from_numpy(np.ascontiguousarray(x, dtype=self.dtype)).cuda(), True
-
-    @staticmethod
-    def _stream():
-        import torch
-        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
     def dct4(self, rows, out=None):
         """rows: `rows` x M scalars, contiguous; the result (2 C4(rows): scipy.fft.dct(type=4)) has the same shape.  out may be rows."""
@@ -912,8 +818,7 @@ class MdctSetup:
         if out is None:
             out = torch.empty_like(x)
         assert out.is_cuda and out.dtype == x.dtype and out.is_contiguous() and out.numel() == x.numel()
-        fn = getattr(self._L, f"{self._pfx}_hip_mdct_dct4_batch")
-        _check(fn(self.handle, x.data_ptr(), out.data_ptr(), x.numel() // self.M, self._stream()), "hip_mdct_dct4_batch")
+        _check(self._fn("hip_mdct_dct4_batch")(self.handle, x.data_ptr(), out.data_ptr(), x.numel() // self.M, self._stream()), "hip_mdct_dct4_batch")
         return out.cpu().numpy() if host else out
 
     def mdct(self, signal, window=None, nframes=None, out=None):
@@ -938,8 +843,7 @@ class MdctSetup:
         assert o3.is_cuda and o3.dtype == x.dtype and tuple(o3.shape) == (nsig, nframes, self.M) and o3.stride(2) == 1
         cstride = o3.stride(1) if nframes > 1 else self.M
         assert nsig == 1 or o3.stride(0) == nframes * cstride, "rows at one pitch"
-        fn = getattr(self._L, f"{self._pfx}_hip_mdct_transform_batch")
-        _check(fn(self.handle, x.data_ptr(), x.stride(0) if nsig > 1 else 0, nsig, nframes, w.data_ptr() if w is not None else None,
+        _check(self._fn("hip_mdct_transform_batch")(self.handle, x.data_ptr(), x.stride(0) if nsig > 1 else 0, nsig, nframes, w.data_ptr() if w is not None else None,
                   o3.data_ptr(), cstride, self._stream()), "hip_mdct_transform_batch")
         res = o3[0] if one else o3
         return res.cpu().numpy() if host else res
@@ -963,36 +867,23 @@ class MdctSetup:
             out = torch.empty((nsig, samples), dtype=X.dtype, device=X.device)
         o2 = out.unsqueeze(0) if out.dim() == 1 else out
         assert o2.is_cuda and o2.dtype == X.dtype and o2.dim() == 2 and o2.shape[0] == nsig and o2.shape[1] >= samples and o2.stride(1) == 1
-        fn = getattr(self._L, f"{self._pfx}_hip_mdct_overlap_add_batch")
-        _check(fn(self.handle, X.data_ptr(), cstride, nsig, nframes, w.data_ptr() if w is not None else None, float(scaling),
+        _check(self._fn("hip_mdct_overlap_add_batch")(self.handle, X.data_ptr(), cstride, nsig, nframes, w.data_ptr() if w is not None else None, float(scaling),
                   o2.data_ptr(), o2.stride(0) if nsig > 1 else 0, self._stream()), "hip_mdct_overlap_add_batch")
         res = o2[0, :samples] if one else o2[:, :samples]
         return res.cpu().numpy() if host else res
 
 
-class FastConv:
+class FastConv(_Handle):
     """PFFASTCONV_Setup (src/pffastconv.c:58-116); `block_len` is updated like *blockLen."""
 
+    _new, _destroy = "new_setup", "destroy_setup"
+
     def __init__(self, taps, block_len: int = 0, flags: int = 0):
-        self._L = lib()
         h = _aligned(taps, np.float32)
         self.filter_len = h.size
         bl = C.c_int(block_len)
-        self.handle = self._L.pffastconv_new_setup(h.ctypes.data, h.size, C.byref(bl), flags)
-        if not self.handle:
-            raise ValueError("pffastconv_new_setup returned NULL")
+        self._open("pffastconv", h.ctypes.data, h.size, C.byref(bl), flags, shown="pffastconv_new_setup")
         self.block_len, self.flags = bl.value, flags
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self._L.pffastconv_destroy_setup(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def apply(self, x, flush: bool = True, out=None):
         """Returns (y[:n_out], n_out) like pffastconv_apply (src/pffastconv.c:133-263)."""
@@ -1002,8 +893,7 @@ class FastConv:
             assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
             n_in = x.numel() // cpl
             y = out if out is not None else torch.empty_like(x)
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            n = self._L.pffastconv_hip_apply_device(self.handle, x.data_ptr(), n_in, y.data_ptr(), int(bool(flush)), st)
+            n = self._L.pffastconv_hip_apply_device(self.handle, x.data_ptr(), n_in, y.data_ptr(), int(bool(flush)), self._stream())
             if n < 0:
                 raise RuntimeError("pffastconv_hip_apply_device failed: " + self._L.pffft_hip_last_error().decode())
             return y[:n * cpl], n
@@ -1024,9 +914,8 @@ class FastConv:
         nsig, fl = x.shape
         y = out if out is not None else torch.empty_like(x)
         assert y.dim() == 2 and y.shape[0] == nsig and y.stride(1) == 1
-        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         n = self._L.pffastconv_hip_apply_batch(self.handle, x.data_ptr(), fl // cpl, x.stride(0) if nsig > 1 else fl,
-                                               y.data_ptr(), y.stride(0) if nsig > 1 else fl, nsig, int(bool(flush)), st)
+                                               y.data_ptr(), y.stride(0) if nsig > 1 else fl, nsig, int(bool(flush)), self._stream())
         if n < 0:
             raise RuntimeError("pffastconv_hip_apply_batch failed: " + self._L.pffft_hip_last_error().decode())
         return y[:, :n * cpl], n

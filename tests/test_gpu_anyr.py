@@ -16,10 +16,11 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pffft_amd as pa  # noqa: E402
+from gpu_kit import kernels_run, kinds_by, mem_free, need_gpu, same_bits, TDT, under  # noqa: E402,F401
 
 AB_ANY_COMPOSED, AB_ANY_FUSED = 132, 133
 DTYPES = [np.float32, np.float64]
-DT = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64}
+DT = TDT
 SIZES = [1, 2, 3, 4, 5, 17, 100, 171, 172, 341, 342, 683, 684, 1000, 1021, 1365, 1366, 2731, 2732, 4093, 10007, 65537, 100003]
 FUSED_SIZES = [N for N in SIZES if rm.expected_route(N, np.float32) == "fused"]
 BATCHES = (1, 7, 1000)
@@ -27,53 +28,10 @@ PEAK = 8e12
 F, B = pa.FORWARD, pa.BACKWARD
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available() or pa.device_count() < 1:
-        pytest.fail("GPU tests need a HIP device: the product has no CPU fallback")
-    torch.cuda.set_device(0)
-    yield
-    pa.set_variant(0)
-
-
-def kernels_run(fn):
-    """(fn(), full names of the device kernels it ran): a kineto trace of the one call."""
-    from torch.profiler import ProfilerActivity, profile
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        out = fn()
-        torch.cuda.synchronize()
-    names = [e.name for e in prof.events()
-             if e.device_type == torch.autograd.DeviceType.CUDA and not e.name.startswith(("Memcpy", "Memset"))]
-    assert names, "the trace recorded no kernel"
-    return out, names
-
-
 def kinds(names):
     """'real' = the convolution kernel with the real policy's ends, 'chirp' = with the complex ones, 'conv' = the dense one, 'pad', 'crop'."""
-    out = []
-    for n in names:
-        if "AnyRealIO" in n:
-            out.append("real")
-        elif "AnyChirpIO" in n:
-            out.append("chirp")
-        elif "any_real_pad_kernel" in n:
-            out.append("pad")
-        elif "any_real_crop_kernel" in n:
-            out.append("crop")
-        elif "fft_conv_kernel" in n:
-            out.append("conv")
-        else:
-            out.append("other")
-    return out
-
-
-def bits(t):
-    return t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int64)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(bits(a), bits(b))
+    return kinds_by((("AnyRealIO", "real"), ("AnyChirpIO", "chirp"), ("any_real_pad_kernel", "pad"), ("any_real_crop_kernel", "crop"),
+                     ("fft_conv_kernel", "conv")), names)
 
 
 def rows_under_1gib(N, M, dtype, want):
@@ -92,13 +50,7 @@ def uniform(batch, N, dtype, seed, direction=F):
 
 
 def run(s, x_t, direction, sel=0, out=None):
-    pa.set_variant(sel)
-    try:
-        y = s.transform_batch(x_t, out, direction)
-        torch.cuda.synchronize()
-    finally:
-        pa.set_variant(0)
-    return y
+    return under(sel, lambda: s.transform_batch(x_t, out, direction))
 
 
 # ------------------------------------------------------------------ truth
@@ -355,11 +307,6 @@ def test_graph_replay_capture_rule_and_two_streams():
     s.close()
 
 
-def _mem_free():
-    torch.cuda.synchronize()
-    return torch.cuda.mem_get_info()[0]
-
-
 @pytest.mark.parametrize("dtype", DTYPES, ids=lambda d: np.dtype(d).name)
 def test_memory_is_back_after_destroy(dtype):
     N, batch = 10007, 600
@@ -373,7 +320,7 @@ def test_memory_is_back_after_destroy(dtype):
             torch.cuda.synchronize()
     warm.close()
     torch.cuda.empty_cache()
-    free0 = _mem_free()
+    free0 = mem_free()
     s = pa.AnyRealSetup(N, dtype)
     M = s.conv_size
     for st in streams:                                                     # two streams: two scratch images
@@ -381,10 +328,10 @@ def test_memory_is_back_after_destroy(dtype):
             s.transform_batch(x_t, y, F)
             torch.cuda.synchronize()
     scratch = batch * M * 2 * np.dtype(dtype).itemsize
-    assert _mem_free() <= free0 - 2 * scratch + (8 << 20), (free0, _mem_free(), scratch)
+    assert mem_free() <= free0 - 2 * scratch + (8 << 20), (free0, mem_free(), scratch)
     s.close()
     torch.cuda.empty_cache()
-    assert _mem_free() >= free0 - (8 << 20), (free0, _mem_free())
+    assert mem_free() >= free0 - (8 << 20), (free0, mem_free())
 
 
 # ------------------------------------------------------------------ time

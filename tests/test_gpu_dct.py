@@ -20,94 +20,27 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pffft_amd as pa  # noqa: E402
+from gpu_kit import best_of, bits, guarded, kinds_by, mem_free, need_gpu, same_bits, SENTINEL, TDT, traced, under, uniform_t  # noqa: E402,F401
 
 SEL_COMPOSED, SEL_FUSED = dm.AB_DCT_COMPOSED, dm.AB_DCT_FUSED
 DTYPES = [np.float32, np.float64]
-DT = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64}
+DT = TDT
 SIZES = (32, 96, 1024, 2048, 4096, 8192, 20480, 65536)
 BATCHES = (1, 7, 1000)
 NORM_ARG = {dm.NORM_NONE: None, dm.NORM_ORTHO: "ortho"}
 PEAK = 8e12
-SENTINEL = -77.0
 SHORT = 256
 # the default route per (N, kind), dct_fused_default of dct_tu.hip (DESIGN.md §3.16 has the measured table): test_default_cells asserts it
 FUSED_DEFAULT = {(N, kind): True for N in dm.FUSED_SIZES for kind in dm.KINDS}
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available() or pa.device_count() < 1:
-        pytest.fail("GPU tests need a HIP device: the product has no CPU fallback")
-    torch.cuda.set_device(0)
-    yield
-    pa.set_variant(0)
-    torch.cuda.empty_cache()
-
-
-def traced(fn):
-    """(fn(), [(kernel name, grid in workgroups or None)]) from a kineto trace of the one call; the grid from its chrome-trace export."""
-    import json
-    import os
-    import tempfile
-    from torch.profiler import ProfilerActivity, profile
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        out = fn()
-        torch.cuda.synchronize()
-    names = [e.name for e in prof.events()
-             if e.device_type == torch.autograd.DeviceType.CUDA and not e.name.startswith(("Memcpy", "Memset"))]
-    assert names, "the trace recorded no kernel"
-    grids = {}
-    with tempfile.TemporaryDirectory() as d:
-        path = os.path.join(d, "trace.json")
-        prof.export_chrome_trace(path)
-        with open(path) as f:
-            events = json.load(f).get("traceEvents", [])
-    for e in events:
-        g = (e.get("args") or {}).get("grid")
-        if e.get("cat") == "kernel" and isinstance(g, list) and len(g) == 3:
-            grids[e["name"]] = int(g[0]) * int(g[1]) * int(g[2])
-    return out, [(n, grids.get(n)) for n in names]
-
-
 def kinds(kernels):
     """The kernels of this feature by kind: 'dct' = the fused kernel, 'pre' / 'post' = the composed route's ends, 'other' = the transform."""
-    out = []
-    for n, _ in kernels:
-        if "fft_dct_kernel" in n:
-            out.append("dct")
-        elif "dct_pre_kernel" in n:
-            out.append("pre")
-        elif "dct_post_kernel" in n:
-            out.append("post")
-        else:
-            out.append("other")
-    return out
-
-
-def bits(t):
-    return t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int64)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(bits(a), bits(b))
-
-
-def uniform_t(shape, seed, tdt):
-    g = torch.Generator(device="cuda"); g.manual_seed(seed)
-    x = torch.empty(shape, device="cuda", dtype=tdt)
-    x.uniform_(-1.0, 1.0, generator=g)
-    return x
+    return kinds_by((("fft_dct_kernel", "dct"), ("dct_pre_kernel", "pre"), ("dct_post_kernel", "post")), [n for n, _ in kernels])
 
 
 def run(s, x_t, sel=0, out=None):
-    pa.set_variant(sel)
-    try:
-        y = s.transform_batch(x_t, out)
-        torch.cuda.synchronize()
-    finally:
-        pa.set_variant(0)
-    return y
+    return under(sel, lambda: s.transform_batch(x_t, out))
 
 
 def sels_of(N, dtype):
@@ -116,12 +49,6 @@ def sels_of(N, dtype):
 
 def setup(N, kind, norm=dm.NORM_NONE, dtype=np.float32):
     return pa.DctSetup(N, dm.KIND_NAMES[kind], norm=NORM_ARG[norm], dtype=dtype)
-
-
-def guarded(rows, row, tdt):
-    """(allocation, its rows 2 ... rows + 2): two sentinel rows in front of the output and two behind."""
-    full = torch.full(((rows + 4) * row,), SENTINEL, device="cuda", dtype=tdt)
-    return full, full[2 * row:(rows + 2) * row].view(rows, row)
 
 
 # ------------------------------------------------------------------ 1. truth
@@ -355,11 +282,6 @@ def test_graph_replay_and_capture_rule():
     s.close()
 
 
-def _mem_free():
-    torch.cuda.synchronize()
-    return torch.cuda.mem_get_info()[0]
-
-
 def test_memory_is_back_after_close():
     """Two streams, two scratch images; after close() the device has what it had, within the allowance tests/test_gpu_zoom.py uses.  The
     warm-up setup runs on the same two streams first (code objects and the runtime's per-queue first-use allocations stay)."""
@@ -379,30 +301,17 @@ def test_memory_is_back_after_close():
     on_both(warm)
     warm.close()
     torch.cuda.empty_cache()
-    free0 = _mem_free()
+    free0 = mem_free()
     s = setup(N, dm.DST2, dtype=dtype)
     on_both(s)
     scratch = batch * N * 8
-    assert _mem_free() <= free0 - 2 * scratch + (8 << 20), (free0, _mem_free(), scratch)
+    assert mem_free() <= free0 - 2 * scratch + (8 << 20), (free0, mem_free(), scratch)
     s.close()
     torch.cuda.empty_cache()
-    assert _mem_free() >= free0 - (8 << 20), (free0, _mem_free())
+    assert mem_free() >= free0 - (8 << 20), (free0, mem_free())
 
 
 # ------------------------------------------------------------------ 8. time
-def _best_of(fn, rounds=3, calls=20):
-    best = math.inf
-    for _ in range(rounds):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(calls):
-            fn()
-        e1.record()
-        e1.synchronize()
-        best = min(best, e0.elapsed_time(e1) * 1e-3 / calls)
-    return best
-
-
 def test_default_cells():
     """The default route of every (size, kind) is the recorded one; where it is fused, the fused kernel is no slower than the composed route:
     one alternating timing in one process, the best of three rounds of 20 calls at batch 2^16."""
@@ -421,7 +330,7 @@ def test_default_cells():
                     torch.cuda.synchronize()
                 for sel in (SEL_FUSED, SEL_COMPOSED, SEL_FUSED, SEL_COMPOSED):
                     pa.set_variant(sel)
-                    t[sel] = min(t.get(sel, math.inf), _best_of(lambda: s.transform_batch(x, y)))
+                    t[sel] = min(t.get(sel, math.inf), best_of(lambda: s.transform_batch(x, y)))
             finally:
                 pa.set_variant(0)
             print(f"DCT CELL N={N} {dm.KIND_NAMES[kind]} batch={batch}: fused {t[SEL_FUSED] * 1e6:.1f} us, composed "

@@ -18,64 +18,12 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pffft_amd as pa  # noqa: E402
+from gpu_kit import kernels_run, make_signal_host, need_gpu, padded_out, same_bits, TDT, windows  # noqa: E402,F401
 
 AB_FRAMES_COMPOSED, AB_FRAMES_FUSED = 124, 125
 SELECTORS = {"default": 0, "composed": AB_FRAMES_COMPOSED, "fused": AB_FRAMES_FUSED}
 FUSED_N = (1024, 2048, 4096)
-DT = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64}
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available() or pa.device_count() < 1:
-        pytest.fail("GPU tests need a HIP device: the product has no CPU fallback")
-    torch.cuda.set_device(0)
-    yield
-    pa.set_variant(0)
-
-
-def kernels_run(fn):
-    """(fn(), names of the device kernels it ran): a kineto trace of the one call (the helper of tests/test_gpu_accuracy.py)."""
-    from torch.profiler import ProfilerActivity, profile
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        out = fn()
-        torch.cuda.synchronize()
-    names = []
-    for e in prof.events():
-        if e.device_type == torch.autograd.DeviceType.CUDA and not e.name.startswith(("Memcpy", "Memset")):
-            names.append(e.name.split("(")[0].split("<")[0].replace("void ", "").replace("pf::", "").strip())
-    assert names, "the trace recorded no kernel"
-    return out, names
-
-
-def bits(t):
-    return t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int64)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(bits(a), bits(b))
-
-
-def windows(N, dtype, seed):
-    rng = np.random.default_rng(seed)
-    return {"hann": fm.hann(N, dtype), "random": rng.uniform(-1, 1, N).astype(dtype), "none": None}
-
-
-def make_signal(nsignals, scalars, pad, dtype, seed):
-    """[nsignals, scalars] view of a [nsignals, scalars + pad] tensor (pad > 0: a padded row stride), and its host copy."""
-    g = torch.Generator(device="cuda"); g.manual_seed(seed)
-    full = torch.empty((nsignals, scalars + pad), device="cuda", dtype=DT[np.dtype(dtype)])
-    full.uniform_(-1.0, 1.0, generator=g)
-    view = full[:, :scalars]
-    host = view.cpu().numpy()
-    return (view[0] if nsignals == 1 else view), host
-
-
-def padded_out(rows, row, pad, tdt):
-    """[rows, row] view with a row pitch of row + pad, pre-filled with a sentinel; the pad columns must keep it."""
-    full = torch.full((rows, row + pad), -77.0, device="cuda", dtype=tdt)
-    return full, full[:, :row]
+DT = TDT
 
 
 def run_analysis(s, sig, hop, nframes, w_t, output, pad):
@@ -99,7 +47,7 @@ def _identity_matrix(s, N, transform, dtype, hops, nframes_list, sel_names, pads
         for nsig in nsignals_list:
             for nframes in nframes_list:
                 scalars = ((nframes - 1) * hop + N) * spp
-                sig, host = make_signal(nsig, scalars, sig_pad if nsig > 1 else 0, dtype, seed + hop + nsig + nframes)
+                sig, host = make_signal_host(nsig, scalars, sig_pad if nsig > 1 else 0, dtype, seed + hop + nsig + nframes)
                 for wname, w in windows(N, dtype, seed + hop).items():
                     fr = torch.from_numpy(fm.frames32(host, N, hop, w, dtype, transform, nframes)).cuda()
                     w_t = None if w is None else torch.from_numpy(w).cuda()
@@ -163,30 +111,30 @@ def test_composed_only_cases_bit_for_bit(case):
 def test_which_kernel_ran(N):
     s = pa.Setup(N, pa.REAL)
     hop, nframes = N // 4, 300
-    sig, _ = make_signal(1, (nframes - 1) * hop + N, 0, np.float32, 3)
+    sig, _ = make_signal_host(1, (nframes - 1) * hop + N, 0, np.float32, 3)
     w_t = torch.from_numpy(fm.hann(N, np.float32)).cuda()
     try:
         for output in ("internal", "ordered", "power"):
             s.frames_transform_batch(sig, hop, nframes, w_t, None, output)      # first use outside the traces
             pa.set_variant(AB_FRAMES_FUSED)
             assert pa.frames_route(s, hop, 0, 0, output) == "fused"
-            _, names = kernels_run(lambda: s.frames_transform_batch(sig, hop, nframes, w_t, None, output))
+            _, names = kernels_run(lambda: s.frames_transform_batch(sig, hop, nframes, w_t, None, output), short=True)
             assert names == ["fft_frames_kernel"], (output, names)
             pa.set_variant(AB_FRAMES_COMPOSED)
             assert pa.frames_route(s, hop, 0, 0, output) == "composed"
-            _, names = kernels_run(lambda: s.frames_transform_batch(sig, hop, nframes, w_t, None, output))
+            _, names = kernels_run(lambda: s.frames_transform_batch(sig, hop, nframes, w_t, None, output), short=True)
             assert sorted(names) == sorted(["frames_gather_kernel", "fft_tiled_kernel"] + (["frames_rows_kernel"] if output == "power" else [])), \
                 (output, names)
             pa.set_variant(0)
             route = pa.frames_route(s, hop, 0, 0, output)
-            _, names = kernels_run(lambda: s.frames_transform_batch(sig, hop, nframes, w_t, None, output))
+            _, names = kernels_run(lambda: s.frames_transform_batch(sig, hop, nframes, w_t, None, output), short=True)
             assert (names == ["fft_frames_kernel"]) if route == "fused" else ("frames_gather_kernel" in names), (route, names)
         # a hop that is no multiple of 16 bytes is composed whatever the selector says
         pa.set_variant(AB_FRAMES_FUSED)
-        _, names = kernels_run(lambda: s.frames_transform_batch(sig, 333, 100, w_t, None, "ordered"))
+        _, names = kernels_run(lambda: s.frames_transform_batch(sig, 333, 100, w_t, None, "ordered"), short=True)
         assert sorted(names) == ["fft_tiled_kernel", "frames_gather_kernel"], names
         # so is a signal that does not start on a 16-byte boundary (the route query assumes aligned pointers: checked at the call)
-        _, names = kernels_run(lambda: s.frames_transform_batch(sig[1:], hop, 100, w_t, None, "ordered"))
+        _, names = kernels_run(lambda: s.frames_transform_batch(sig[1:], hop, 100, w_t, None, "ordered"), short=True)
         assert sorted(names) == ["fft_tiled_kernel", "frames_gather_kernel"], names
     finally:
         pa.set_variant(0)
@@ -206,7 +154,7 @@ def test_truth_and_power(N, sel):
     try:
         for hop in (N // 4, N // 2, N, 4):
             for nsig, nframes in ((1, 1001), (3, 7)):
-                sig, host = make_signal(nsig, (nframes - 1) * hop + N, 8 if nsig > 1 else 0, np.float32, N + hop)
+                sig, host = make_signal_host(nsig, (nframes - 1) * hop + N, 8 if nsig > 1 else 0, np.float32, N + hop)
                 for wname, w in windows(N, np.float32, 7).items():
                     fr = fm.frames32(host, N, hop, w, np.float32, pa.REAL, nframes)
                     w_t = None if w is None else torch.from_numpy(w).cuda()
@@ -240,7 +188,7 @@ def test_power_complex_and_double_composed():
         s = pa.Setup(N, tr, dtype)
         spp = fm.spp_of(tr)
         hop, nframes = N // 4, 33
-        sig, host = make_signal(2, ((nframes - 1) * hop + N) * spp, 6, dtype, N)
+        sig, host = make_signal_host(2, ((nframes - 1) * hop + N) * spp, 6, dtype, N)
         w = fm.hann(N, dtype)
         fr = fm.frames32(host, N, hop, w, dtype, tr, nframes)
         P = fm.power_truth(fr, N, tr)
@@ -312,7 +260,7 @@ def test_hann_round_trip_2_20_samples():
     S = 1 << 20
     nframes = fm.max_frames(S, N, hop)
     s = pa.Setup(N, pa.REAL)
-    sig, host = make_signal(1, S, 0, np.float32, 99)
+    sig, host = make_signal_host(1, S, 0, np.float32, 99)
     w = fm.hann(N, np.float32)
     w_t = torch.from_numpy(w).cuda()
     res = {}
@@ -475,7 +423,7 @@ def test_frames_beyond_the_scratch_cap_go_through_in_chunks():
     s = pa.Setup(N, pa.REAL)
     w = fm.hann(N, np.float32)
     w_t = torch.from_numpy(w).cuda()
-    sig, host = make_signal(1, S, 0, np.float32, 8)
+    sig, host = make_signal_host(1, S, 0, np.float32, 8)
     fr = torch.from_numpy(fm.frames32(host, N, hop, w, np.float32)).cuda()
     want = s.transform_batch(fr, None, pa.FORWARD, False)
     pa.set_variant(AB_FRAMES_COMPOSED)

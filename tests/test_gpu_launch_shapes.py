@@ -30,9 +30,6 @@ TRANSFORM_PARTS = 32 puts two or three sizes into an item.  The chrome-trace exp
 in workgroups (256 for the headline loop, 512 for tiled N = 4096, 16 384 = 16 x 256 x 4 for the Stockham plan of N = 48), so the grid
 assertions below are live: a trace without a grid fails them."""
 import functools
-import json
-import os
-import tempfile
 import time
 
 import numpy as np
@@ -49,82 +46,19 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 import pffft_amd as pa  # noqa: E402
 from pffft_amd import api  # noqa: E402
+from gpu_kit import assert_guards, assert_same_bits, guarded, need_gpu, traced, uniform_t  # noqa: E402,F401
 
 DT = {"f32": (np.float32, torch.float32), "f64": (np.float64, torch.float64)}
 COMBOS = [(pa.FORWARD, True), (pa.FORWARD, False), (pa.BACKWARD, True), (pa.BACKWARD, False)]      # the order of describe()'s lines
 HEADS = ["forward ordered", "forward unordered", "backward ordered", "backward unordered"]
-SENTINEL = -77.0
 SHORT = 256                   # rows per reference call: at most 256 groups, within the resident set of every kernel here (256 CUs and more)
 LIMIT = 4 << 30               # bytes of one long batch
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available() or pa.device_count() < 1:
-        pytest.fail("GPU tests need a HIP device: the product has no CPU fallback")
-    torch.cuda.set_device(0)
-    yield
-    pa.set_variant(0)
-    torch.cuda.empty_cache()
 
 
 def cus():
     n = torch.cuda.get_device_properties(0).multi_processor_count
     assert n >= SHORT, "a 256-row reference call would no longer be one pass of the kernels that run one workgroup per CU"
     return n
-
-
-def uniform(shape, seed, tdt):
-    g = torch.Generator(device="cuda"); g.manual_seed(seed)
-    x = torch.empty(shape, device="cuda", dtype=tdt)
-    x.uniform_(-1.0, 1.0, generator=g)
-    return x
-
-
-def bits(t):
-    return t.view(torch.int32 if t.dtype == torch.float32 else torch.int64)
-
-
-def assert_same_bits(got, want, what):
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    if torch.equal(bits(got), bits(want)):
-        return
-    rows = (bits(got) != bits(want)).reshape(got.shape[0], -1).any(dim=1).nonzero().flatten()
-    raise AssertionError((what, f"{rows.numel()} of {got.shape[0]} rows differ, the first at", rows[:8].tolist(), "the last at", rows[-3:].tolist()))
-
-
-def guarded(rows, row, tdt):
-    """(allocation, its rows 2 ... rows + 2): two sentinel rows in front of the output and two behind."""
-    full = torch.full(((rows + 4) * row,), SENTINEL, device="cuda", dtype=tdt)
-    return full, full[2 * row:(rows + 2) * row].view(rows, row)
-
-
-def assert_guards(full, rows, row, what):
-    assert bool((full[:2 * row] == SENTINEL).all()), (what, "the call wrote in front of its output")
-    assert bool((full[(rows + 2) * row:] == SENTINEL).all()), (what, "the call wrote behind its output")
-
-
-def traced(fn):
-    """(fn(), [(kernel name, grid in workgroups or None)]) from a kineto trace of the one call; the grid from its chrome-trace export."""
-    from torch.profiler import ProfilerActivity, profile
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        out = fn()
-        torch.cuda.synchronize()
-    names = [e.name for e in prof.events()
-             if e.device_type == torch.autograd.DeviceType.CUDA and not e.name.startswith(("Memcpy", "Memset"))]
-    assert names, "the trace recorded no kernel"
-    grids = {}
-    with tempfile.TemporaryDirectory() as d:
-        path = os.path.join(d, "trace.json")
-        prof.export_chrome_trace(path)
-        with open(path) as f:
-            events = json.load(f).get("traceEvents", [])
-    for e in events:
-        g = (e.get("args") or {}).get("grid")
-        if e.get("cat") == "kernel" and isinstance(g, list) and len(g) == 3:
-            grids[e["name"]] = int(g[0]) * int(g[1]) * int(g[2])
-    return out, [(n, grids.get(n)) for n in names]
 
 
 def ran(kernels, part):
@@ -194,7 +128,7 @@ def _transform_cell(s, dt, line, combo, n_cus, seed):
     what = (dt, s.transform_type, s.N, d, o, B)
     nbytes = B * row * np.dtype(dtype).itemsize
     assert nbytes < LIMIT, (what, nbytes, "the long batch of this route no longer fits 4 GiB")
-    x = uniform((B, row), seed, tdt)
+    x = uniform_t((B, row), seed, tdt)
     full, out = guarded(B, row, tdt)
     s.transform_batch(x, out, d, o)
     assert_guards(full, B, row, what)
@@ -287,7 +221,7 @@ def test_the_trace_shows_the_grid_of_a_long_call():
         if kernel is None:      # a Stockham plan: the compile-time kernel of the organisation and first stage the line names
             assert shape.kind == "stockham", lines[0]
             kernel = "fft_stock_" + ("wl_" if "wave-local" in lines[0] else "") + ("df_" if "direct-first-stage" in lines[0] else "") + "ct_kernel"
-        x = uniform((shape.B_long, s.vec_scalars), N, tdt)
+        x = uniform_t((shape.B_long, s.vec_scalars), N, tdt)
         _, kernels = traced(lambda: s.transform_batch(x, None, pa.FORWARD, True))
         assert ran(kernels, kernel), (N, kernels)
         assert_grid_loops(kernels, kernel, shape.vmax, shape.B_long, (dt, tr, N))
@@ -324,7 +258,7 @@ def test_convolve_every_instantiation(dt, tr, N):
     s = pa.Setup(N, tr, dtype)
     row = s.vec_scalars
     scaling = 1.0 / N
-    H = s.transform_batch(uniform((1, row), N + 2, tdt), None, pa.FORWARD, False)[0].contiguous()
+    H = s.transform_batch(uniform_t((1, row), N + 2, tdt), None, pa.FORWARD, False)[0].contiguous()
     Hh = H.cpu().numpy()[None]
 
     def truth(xs):
@@ -335,7 +269,7 @@ def test_convolve_every_instantiation(dt, tr, N):
 
     # short batches, every row
     nmax = max(CONV_SHORT)
-    x, a0 = uniform((nmax, row), N + 1, tdt), uniform((nmax, row), N + 3, tdt)
+    x, a0 = uniform_t((nmax, row), N + 1, tdt), uniform_t((nmax, row), N + 3, tdt)
     want, a0h = truth(x), a0.cpu().numpy().astype(np.float64)
     for b in CONV_SHORT:
         for mode in ("off", "on", "in place"):
@@ -358,7 +292,7 @@ def test_convolve_every_instantiation(dt, tr, N):
     vmax = ls.LDS_PER_CU // core
     B = ls.fused_long_batch(n_cus, core)
     assert B * core < LIMIT
-    x, a0 = uniform((B, row), N + 4, tdt), uniform((B, row), N + 5, tdt)
+    x, a0 = uniform_t((B, row), N + 4, tdt), uniform_t((B, row), N + 5, tdt)
     idx = sampled(B, vmax, N)
     want, a0h = truth(x[idx]), a0[idx].cpu().numpy().astype(np.float64)
     full, out = guarded(B, row, tdt)
@@ -403,7 +337,7 @@ def _any_long(s, N, rin, rout, truth, chirp_kernel, in_place):
     for direction in (pa.FORWARD, pa.BACKWARD):
         ri, ro = (rin, rout) if direction == pa.FORWARD else (rout, rin)
         what = (N, M, direction, B)
-        x = uniform((B, ri), N + direction, torch.float32)
+        x = uniform_t((B, ri), N + direction, torch.float32)
         s.transform_batch(x[:3], None, direction)                         # first use (the tables) outside the trace
         full, out = guarded(B, ro, torch.float32)
         _, kernels = traced(lambda: s.transform_batch(x, out, direction))
@@ -464,14 +398,14 @@ def test_frames_fused_loops_bit_for_bit(N):
     s = pa.Setup(N, pa.REAL, np.float32)
     head, *lines = pa.describe(s).strip().split("\n")
     hop = N // 2
-    w = uniform((N,), N + 9, torch.float32)
+    w = uniform_t((N,), N + 9, torch.float32)
     for output, line in (("ordered", lines[0]), ("internal", lines[1])):
         m = ls.loop_shape(line, max(1, pa.route_occupancy(s, pa.FORWARD, output == "ordered")), cus(), ls.core_vector_bytes(head)).m
         # (launch_frames_fused launches under the oneshot of this very route: the library-wide value for every real size that has a framed kernel)
         assert m == 4, line
         B = ls.fused_long_batch(cus(), ls.core_vector_bytes(head), m)
         assert pa.frames_route(s, hop, 0, 0, output) == "fused"
-        sig = uniform(((B - 1) * hop + N,), N + 10, torch.float32)
+        sig = uniform_t(((B - 1) * hop + N,), N + 10, torch.float32)
         frames = (sig.unfold(0, N, hop) * w).contiguous()                        # same-type product: one rounding
         assert frames.shape == (B, N)
         want = s.transform_batch(frames, None, pa.FORWARD, output == "ordered")
@@ -491,11 +425,11 @@ def test_pfb_fused_loops_bit_for_bit():
     N, taps, hop = 1024, 4, 512
     s = pa.Setup(N, pa.COMPLEX, np.float32)
     head, *lines = pa.describe(s).strip().split("\n")
-    h = uniform((taps * N,), 77, torch.float32)
+    h = uniform_t((taps * N,), 77, torch.float32)
     for output, line in (("ordered", lines[0]), ("internal", lines[1])):
         B = ls.loop_shape(line, 0, cus()).B_long
         assert pa.pfb_route(s, hop, taps, 0, 0, output) == "fused"
-        sig = uniform((2 * ((B - 1) * hop + taps * N),), 78, torch.float32)
+        sig = uniform_t((2 * ((B - 1) * hop + taps * N),), 78, torch.float32)
         acc = None
         for p in range(taps):                                                      # p ascending, one rounding per product and per addition
             t = sig[2 * p * N:].unfold(0, 2 * N, 2 * hop)[:B] * h[p * N:(p + 1) * N].repeat_interleave(2)

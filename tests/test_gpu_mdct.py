@@ -21,92 +21,24 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pffft_amd as pa  # noqa: E402
+from gpu_kit import best_of, bits, kinds_by, mem_free, need_gpu, same_bits, SENTINEL, TDT, traced, under, uniform_t  # noqa: E402,F401
 
 SEL_COMPOSED, SEL_FUSED = mm.AB_MDCT_COMPOSED, mm.AB_MDCT_FUSED
 DTYPES = [np.float32, np.float64]
-DT = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64}
+DT = TDT
 SIZES = (32, 96, 512, 1024, 2048, 40960)
 SHAPES = ((1, 1), (3, 7), (2, 500))          # nsignals x nframes
 PEAK = 8e12
-SENTINEL = -77.0
 SHORT = 256
 # the default route per (M, what), mdct_fused_default of mdct_tu.hip (DESIGN.md §3.19 has the measured table): test_default_cells asserts it
 FUSED_DEFAULT = {(M, what): True for M in mm.FUSED_SIZES for what in mm.WHATS}
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available() or pa.device_count() < 1:
-        pytest.fail("GPU tests need a HIP device: the product has no CPU fallback")
-    torch.cuda.set_device(0)
-    yield
-    pa.set_variant(0)
-    torch.cuda.empty_cache()
-
-
-def traced(fn):
-    """(fn(), [(kernel name, grid in workgroups or None)]) from a kineto trace of the one call; the grid from its chrome-trace export."""
-    import json
-    import os
-    import tempfile
-    from torch.profiler import ProfilerActivity, profile
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        out = fn()
-        torch.cuda.synchronize()
-    names = [e.name for e in prof.events()
-             if e.device_type == torch.autograd.DeviceType.CUDA and not e.name.startswith(("Memcpy", "Memset"))]
-    assert names, "the trace recorded no kernel"
-    grids = {}
-    with tempfile.TemporaryDirectory() as d:
-        path = os.path.join(d, "trace.json")
-        prof.export_chrome_trace(path)
-        with open(path) as f:
-            events = json.load(f).get("traceEvents", [])
-    for e in events:
-        g = (e.get("args") or {}).get("grid")
-        if e.get("cat") == "kernel" and isinstance(g, list) and len(g) == 3:
-            grids[e["name"]] = int(g[0]) * int(g[1]) * int(g[2])
-    return out, [(n, grids.get(n)) for n in names]
-
-
 def kinds(kernels):
     """The kernels of this feature by kind: 'mdct' = the fused kernel, 'fold' / 'post' = the composed route's ends, 'ola' = the
     overlap-add gather, 'other' = the transform."""
-    out = []
-    for n, _ in kernels:
-        for key, kind in (("fft_mdct_kernel", "mdct"), ("mdct_fold_kernel", "fold"), ("mdct_post_kernel", "post"), ("mdct_ola_kernel", "ola")):
-            if key in n:
-                out.append(kind)
-                break
-        else:
-            out.append("other")
-    return out
-
-
-def bits(t):
-    return t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int64)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(bits(a), bits(b))
-
-
-def uniform_t(shape, seed, tdt):
-    g = torch.Generator(device="cuda"); g.manual_seed(seed)
-    x = torch.empty(shape, device="cuda", dtype=tdt)
-    x.uniform_(-1.0, 1.0, generator=g)
-    return x
-
-
-def under(sel, fn):
-    pa.set_variant(sel)
-    try:
-        y = fn()
-        torch.cuda.synchronize()
-    finally:
-        pa.set_variant(0)
-    return y
+    return kinds_by((("fft_mdct_kernel", "mdct"), ("mdct_fold_kernel", "fold"), ("mdct_post_kernel", "post"), ("mdct_ola_kernel", "ola")),
+                    [n for n, _ in kernels])
 
 
 def sels_of(M, dtype):
@@ -512,11 +444,6 @@ def test_graph_replay_and_capture_rule():
     s.close()
 
 
-def _mem_free():
-    torch.cuda.synchronize()
-    return torch.cuda.mem_get_info()[0]
-
-
 def test_memory_is_back_after_close():
     """Two streams, two scratch images; after close() the device has what it had, within the allowance tests/test_gpu_dct.py uses.  The
     warm-up setup runs on the same two streams first (code objects and the runtime's per-queue first-use allocations stay)."""
@@ -536,30 +463,17 @@ def test_memory_is_back_after_close():
     on_both(warm)
     warm.close()
     torch.cuda.empty_cache()
-    free0 = _mem_free()
+    free0 = mem_free()
     s = pa.MdctSetup(M, dtype=dtype)
     on_both(s)
     scratch = rows * M * 8
-    assert _mem_free() <= free0 - 2 * scratch + (8 << 20), (free0, _mem_free(), scratch)
+    assert mem_free() <= free0 - 2 * scratch + (8 << 20), (free0, mem_free(), scratch)
     s.close()
     torch.cuda.empty_cache()
-    assert _mem_free() >= free0 - (8 << 20), (free0, _mem_free())
+    assert mem_free() >= free0 - (8 << 20), (free0, mem_free())
 
 
 # ------------------------------------------------------------------ 8. time
-def _best_of(fn, rounds=3, calls=20):
-    best = math.inf
-    for _ in range(rounds):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(calls):
-            fn()
-        e1.record()
-        e1.synchronize()
-        best = min(best, e0.elapsed_time(e1) * 1e-3 / calls)
-    return best
-
-
 def test_default_cells():
     """The default route of every (M, entry) is the recorded one; where it is fused, the fused kernel is no slower than the composed route:
     one alternating timing in one process, the best of three rounds of 20 calls at 2^16 frames."""
@@ -582,7 +496,7 @@ def test_default_cells():
                     torch.cuda.synchronize()
                 for sel in (SEL_FUSED, SEL_COMPOSED, SEL_FUSED, SEL_COMPOSED):
                     pa.set_variant(sel)
-                    t[sel] = min(t.get(sel, math.inf), _best_of(call))
+                    t[sel] = min(t.get(sel, math.inf), best_of(call))
             finally:
                 pa.set_variant(0)
             print(f"MDCT CELL M={M} what={what} frames={frames}: fused {t[SEL_FUSED] * 1e6:.1f} us, composed "

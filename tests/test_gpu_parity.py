@@ -15,13 +15,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 import pffft_amd as pa  # noqa: E402
 from oracle import pffft_oracle as po  # noqa: E402
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available() or pa.device_count() < 1:
-        pytest.fail("GPU tests need a HIP device: the product has no CPU fallback")  # fail loudly, never skip silently
-    torch.cuda.set_device(0)
+from gpu_kit import need_gpu, rand_t  # noqa: E402,F401
 
 
 def _dt(dt):
@@ -179,17 +173,12 @@ def test_single_tone(N, cplx):
 
 
 # ------------------------------------------------------------------ full-size properties (BASELINE configs)
-def _hash_uniform(shape, seed, device):
-    g = torch.Generator(device=device); g.manual_seed(seed)
-    return torch.rand(shape, device=device, generator=g) * 2 - 1
-
-
 def test_c2_full_batch_properties(ref):
     """BASELINE configs[1]: N=1024 complex float, batch 2^20 (8 GiB in / 8 GiB out)."""
     N, B = 1024, 1 << 20
     s = pa.Setup(N, pa.COMPLEX)
     assert pa.kernel_name(s) == "c1024_f32"
-    x = _hash_uniform((B, 2 * N), 2, "cuda")
+    x = rand_t((B, 2 * N), 2)
     y = s.transform_batch(x, None, pa.FORWARD, False)
     # (1) sampled transforms against the reference
     # SURVEY.md §8(d): >= 4096 sampled transforms against the reference (edges of the per-workgroup groups + a stride
@@ -221,7 +210,7 @@ def test_c3_full_batch_properties(ref):
     """BASELINE configs[2]: N=16384 real float forward, batch 2^16 (4 GiB)."""
     N, B = 16384, 1 << 16
     s = pa.Setup(N, pa.REAL)
-    x = _hash_uniform((B, N), 3, "cuda")
+    x = rand_t((B, N), 3)
     y = s.transform_batch(x, None, pa.FORWARD, False)
     idx = torch.tensor(sorted({0, 1, 2, 3, B // 3, B - 2, B - 1} | set(range(5, B, 15)))).cuda()   # >= 4096 sampled transforms
     assert idx.numel() >= 4096
@@ -257,13 +246,13 @@ def test_c5_double_properties(ref):
 def test_linearity_and_edge_batches():
     N = 1024
     s = pa.Setup(N, pa.COMPLEX)
-    a = _hash_uniform((37, 2 * N), 7, "cuda"); b = _hash_uniform((37, 2 * N), 8, "cuda")
+    a = rand_t((37, 2 * N), 7); b = rand_t((37, 2 * N), 8)
     fa, fb = s.transform_batch(a, None, 0, False), s.transform_batch(b, None, 0, False)
     fab = s.transform_batch(2 * a - 3 * b, None, 0, False)
     assert float((fab - (2 * fa - 3 * fb)).abs().max() / fab.abs().max()) <= 1e-5
     # batch sizes around the waves-per-workgroup / grid boundaries, and the empty batch
     for B in (0, 1, 7, 8, 9, 4095, 4097):
-        x = _hash_uniform((B, 2 * N), 9, "cuda")
+        x = rand_t((B, 2 * N), 9)
         y = s.transform_batch(x, None, 0, False)
         if B:
             assert torch.equal(y[-1:], s.transform_batch(x[-1:].contiguous(), None, 0, False))

@@ -15,64 +15,12 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pffft_amd as pa  # noqa: E402
+from gpu_kit import kernels_run, make_signal_host, need_gpu, padded_out, prototypes, same_bits, TDT  # noqa: E402,F401
 
 AB_PFB_COMPOSED, AB_PFB_FUSED = 126, 127
 SELECTORS = {"default": 0, "composed": AB_PFB_COMPOSED, "fused": AB_PFB_FUSED}
 MAX = pa.PFB_FUSED_MAX_TAPS
-DT = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64}
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available() or pa.device_count() < 1:
-        pytest.fail("GPU tests need a HIP device: the product has no CPU fallback")
-    torch.cuda.set_device(0)
-    yield
-    pa.set_variant(0)
-
-
-def kernels_run(fn):
-    """(fn(), names of the device kernels it ran): a kineto trace of the one call (the helper of tests/test_gpu_frames.py)."""
-    from torch.profiler import ProfilerActivity, profile
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        out = fn()
-        torch.cuda.synchronize()
-    names = []
-    for e in prof.events():
-        if e.device_type == torch.autograd.DeviceType.CUDA and not e.name.startswith(("Memcpy", "Memset")):
-            names.append(e.name.split("(")[0].split("<")[0].replace("void ", "").replace("pf::", "").strip())
-    assert names, "the trace recorded no kernel"
-    return out, names
-
-
-def bits(t):
-    return t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int64)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(bits(a), bits(b))
-
-
-def prototypes(N, taps, dtype, seed):
-    rng = np.random.default_rng(seed)
-    return {"prototype": pm.prototype(N, taps, dtype), "random": rng.uniform(-1, 1, taps * N).astype(dtype)}
-
-
-def make_signal(nsignals, scalars, pad, dtype, seed):
-    """[nsignals, scalars] view of a [nsignals, scalars + pad] tensor (pad > 0: a padded row stride), and its host copy."""
-    g = torch.Generator(device="cuda"); g.manual_seed(seed)
-    full = torch.empty((nsignals, scalars + pad), device="cuda", dtype=DT[np.dtype(dtype)])
-    full.uniform_(-1.0, 1.0, generator=g)
-    view = full[:, :scalars]
-    host = view.cpu().numpy()
-    return (view[0] if nsignals == 1 else view), host
-
-
-def padded_out(rows, row, pad, tdt):
-    """[rows, row] view with a row pitch of row + pad, pre-filled with a sentinel; the pad columns must keep it."""
-    full = torch.full((rows, row + pad), -77.0, device="cuda", dtype=tdt)
-    return full, full[:, :row]
+DT = TDT
 
 
 def run_pfb(s, sig, hop, nframes, h_t, output, pad):
@@ -98,7 +46,7 @@ def _identity_matrix(s, N, transform, dtype, taps_list, hops, nframes_list, sel_
             for nsig in nsignals_list:
                 for nframes in nframes_list:
                     scalars = pm.samples_needed(N, hop, taps, nframes) * spp
-                    sig, host = make_signal(nsig, scalars + offset, sig_pad if nsig > 1 else 0, dtype, seed + taps + hop + nsig + nframes)
+                    sig, host = make_signal_host(nsig, scalars + offset, sig_pad if nsig > 1 else 0, dtype, seed + taps + hop + nsig + nframes)
                     if offset:
                         sig, host = sig[..., offset:], host[:, offset:]
                     for pname, h in prototypes(N, taps, dtype, seed + hop + taps).items():
@@ -176,7 +124,7 @@ def test_one_tap_has_the_bits_of_the_frame_entry(case):
     try:
         for hop in (N // 4, N, 334):
             for nsig, nframes in ((1, 1001), (3, 7)):
-                sig, _ = make_signal(nsig, pm.samples_needed(N, hop, 1, nframes) * spp, 8 if nsig > 1 else 0, dtype, N + hop)
+                sig, _ = make_signal_host(nsig, pm.samples_needed(N, hop, 1, nframes) * spp, 8 if nsig > 1 else 0, dtype, N + hop)
                 w_t = torch.from_numpy(fm.hann(N, dtype)).cuda()
                 for output in ("internal", "ordered", "power"):
                     pa.set_variant(0)
@@ -198,49 +146,49 @@ def test_which_kernel_ran():
     N, hop, nframes, taps = 1024, 256, 300, 4
     s = pa.Setup(N, pa.COMPLEX)
     # (one signal for every call below: the longest is the odd hop of 333; + 1 sample for the view that starts off the 16-byte grid)
-    sig, _ = make_signal(1, (pm.samples_needed(N, 333, MAX + 1, nframes) + 1) * 2, 0, np.float32, 3)
+    sig, _ = make_signal_host(1, (pm.samples_needed(N, 333, MAX + 1, nframes) + 1) * 2, 0, np.float32, 3)
     h_t = torch.from_numpy(pm.prototype(N, taps, np.float32)).cuda()
     h_long = torch.from_numpy(pm.prototype(N, MAX + 1, np.float32)).cuda()
     fr = torch.empty((nframes, 2 * N), device="cuda", dtype=torch.float32).uniform_(-1, 1)
     try:
         for output in ("internal", "ordered", "power"):
             s.pfb_transform_batch(sig, hop, h_t, nframes, None, output)         # first use outside the traces
-            _, tname = kernels_run(lambda: s.transform_batch(fr, None, pa.FORWARD, output != "internal"))
+            _, tname = kernels_run(lambda: s.transform_batch(fr, None, pa.FORWARD, output != "internal"), short=True)
             assert len(tname) == 1 and tname[0].startswith("fft_c1024_f32"), tname
             composed = sorted(["pfb_fold_kernel", tname[0]] + (["frames_rows_kernel"] if output == "power" else []))
             pa.set_variant(AB_PFB_FUSED)
             if output == "power":
                 assert pa.pfb_route(s, hop, taps, 0, 0, output) == "composed"
-                _, names = kernels_run(lambda: s.pfb_transform_batch(sig, hop, h_t, nframes, None, output))
+                _, names = kernels_run(lambda: s.pfb_transform_batch(sig, hop, h_t, nframes, None, output), short=True)
                 assert sorted(names) == composed, (output, names)
             else:
                 assert pa.pfb_route(s, hop, taps, 0, 0, output) == "fused"
-                _, names = kernels_run(lambda: s.pfb_transform_batch(sig, hop, h_t, nframes, None, output))
+                _, names = kernels_run(lambda: s.pfb_transform_batch(sig, hop, h_t, nframes, None, output), short=True)
                 assert names == ["fft_pfb_c1024_kernel"], (output, names)
             pa.set_variant(AB_PFB_COMPOSED)
             assert pa.pfb_route(s, hop, taps, 0, 0, output) == "composed"
-            _, names = kernels_run(lambda: s.pfb_transform_batch(sig, hop, h_t, nframes, None, output))
+            _, names = kernels_run(lambda: s.pfb_transform_batch(sig, hop, h_t, nframes, None, output), short=True)
             assert sorted(names) == composed, (output, names)
             if output != "power":   # pitched rows: the row kernel behind the transform
                 full, view = padded_out(nframes, 2 * N, 8, torch.float32)
-                _, names = kernels_run(lambda: s.pfb_transform_batch(sig, hop, h_t, nframes, view, output))
+                _, names = kernels_run(lambda: s.pfb_transform_batch(sig, hop, h_t, nframes, view, output), short=True)
                 assert sorted(names) == sorted(composed + ["frames_rows_kernel"]), (output, names)
             pa.set_variant(0)
             route = pa.pfb_route(s, hop, taps, 0, 0, output)
-            _, names = kernels_run(lambda: s.pfb_transform_batch(sig, hop, h_t, nframes, None, output))
+            _, names = kernels_run(lambda: s.pfb_transform_batch(sig, hop, h_t, nframes, None, output), short=True)
             assert (names == ["fft_pfb_c1024_kernel"]) if route == "fused" else (sorted(names) == composed), (route, names)
-        _, tname = kernels_run(lambda: s.transform_batch(fr, None, pa.FORWARD, True))
+        _, tname = kernels_run(lambda: s.transform_batch(fr, None, pa.FORWARD, True), short=True)
         composed = sorted(["pfb_fold_kernel", tname[0]])
         pa.set_variant(AB_PFB_FUSED)
         # an odd hop is composed whatever the selector says
-        _, names = kernels_run(lambda: s.pfb_transform_batch(sig, 333, h_t, nframes, None, "ordered"))
+        _, names = kernels_run(lambda: s.pfb_transform_batch(sig, 333, h_t, nframes, None, "ordered"), short=True)
         assert sorted(names) == composed, names
         # so is a signal that does not start on a 16-byte boundary (the route query assumes aligned pointers: checked at the call)
-        _, names = kernels_run(lambda: s.pfb_transform_batch(sig[2:], hop, h_t, nframes, None, "ordered"))
+        _, names = kernels_run(lambda: s.pfb_transform_batch(sig[2:], hop, h_t, nframes, None, "ordered"), short=True)
         assert sorted(names) == composed, names
         # and a prototype of more taps than the LDS table holds
         assert pa.pfb_route(s, hop, MAX + 1, 0, 0, "ordered") == "composed"
-        _, names = kernels_run(lambda: s.pfb_transform_batch(sig, hop, h_long, nframes, None, "ordered"))
+        _, names = kernels_run(lambda: s.pfb_transform_batch(sig, hop, h_long, nframes, None, "ordered"), short=True)
         assert sorted(names) == composed, names
     finally:
         pa.set_variant(0)
@@ -260,7 +208,7 @@ def test_truth_and_power(sel):
     try:
         for taps, hop in ((4, 256), (8, 1024), (1, 512), (3, 334)):
             for nsig, nframes in ((1, 1001), (3, 7)):
-                sig, host = make_signal(nsig, pm.samples_needed(N, hop, taps, nframes) * 2, 8 if nsig > 1 else 0, np.float32, N + hop)
+                sig, host = make_signal_host(nsig, pm.samples_needed(N, hop, taps, nframes) * 2, 8 if nsig > 1 else 0, np.float32, N + hop)
                 for pname, h in prototypes(N, taps, np.float32, 7).items():
                     fr = pm.fold(host, N, hop, h, taps, np.float32, pa.COMPLEX, nframes)
                     h_t = torch.from_numpy(h).cuda()
@@ -290,7 +238,7 @@ def test_spectrum_is_the_long_dft_at_every_taps_th_bin():
     can add to any bin, at most its sum over the 2N scalars of the frame."""
     N, taps, hop, nframes = 1024, 8, 512, 64
     s = pa.Setup(N, pa.COMPLEX)
-    sig, host = make_signal(1, pm.samples_needed(N, hop, taps, nframes) * 2, 0, np.float32, 21)
+    sig, host = make_signal_host(1, pm.samples_needed(N, hop, taps, nframes) * 2, 0, np.float32, 21)
     h = pm.prototype(N, taps, np.float32)
     T = pm.long_dft_truth(host, N, hop, h, taps, pa.COMPLEX, nframes)
     S = pm.fold_abs_sum(host, N, hop, h, taps, pa.COMPLEX, nframes)

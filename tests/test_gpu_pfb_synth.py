@@ -20,36 +20,17 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pffft_amd as pa  # noqa: E402
+from gpu_kit import kernels_run, need_gpu, prototypes, short_name, TDT  # noqa: E402,F401
 
 AB_PFB_COMPOSED, AB_PFB_FUSED = 126, 127
 AB_PFB_SYN_SCALAR, AB_PFB_SYN_PLAIN, AB_PFB_SYN_XCD = 128, 129, 131
-DT = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64}
+DT = TDT
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available() or pa.device_count() < 1:
-        pytest.fail("GPU tests need a HIP device: the product has no CPU fallback")
-    torch.cuda.set_device(0)
-    yield
-    pa.set_variant(0)
-
-
-def kernels_run(fn):
-    """(fn(), names of the device kernels it ran, their full names with template arguments): a kineto trace of the one call (the helper
-    of tests/test_gpu_pfb.py)."""
-    from torch.profiler import ProfilerActivity, profile
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        out = fn()
-        torch.cuda.synchronize()
-    names, full = [], []
-    for e in prof.events():
-        if e.device_type == torch.autograd.DeviceType.CUDA and not e.name.startswith(("Memcpy", "Memset")):
-            names.append(e.name.split("(")[0].split("<")[0].replace("void ", "").replace("pf::", "").strip())
-            full.append(e.name)
-    assert names, "the trace recorded no kernel"
-    return out, names, full
+def names_run(fn):
+    """(fn(), names of the device kernels it ran, their full names with template arguments)."""
+    out, full = kernels_run(fn)
+    return out, [short_name(n) for n in full], full
 
 
 def np_bits(a):
@@ -58,11 +39,6 @@ def np_bits(a):
 
 def same_np(a, b):
     return a.shape == b.shape and np.array_equal(np_bits(np.ascontiguousarray(a)), np_bits(np.ascontiguousarray(b)))
-
-
-def prototypes(N, taps, dtype, seed):
-    rng = np.random.default_rng(seed)
-    return {"prototype": pm.prototype(N, taps, dtype), "random": rng.uniform(-1, 1, taps * N).astype(dtype)}
 
 
 def run_syn(s, spectra, hop, g_t, scaling, ordered, nsig, L, opad, offset, sel):
@@ -251,35 +227,35 @@ def test_which_kernels_ran():
     big = torch.empty(L + 4, device="cuda", dtype=torch.float32)
     try:
         s.pfb_synthesis_batch(spec, hop, g_t, 1.0, big[:L], True)                 # first use outside the traces
-        _, tname, _ = kernels_run(lambda: s.transform_batch(spec, None, pa.BACKWARD, True))
+        _, tname, _ = names_run(lambda: s.transform_batch(spec, None, pa.BACKWARD, True))
         assert len(tname) == 1, tname
         composed = sorted(["pfb_syn_kernel", tname[0]])
-        _, names, full = kernels_run(lambda: s.pfb_synthesis_batch(spec, hop, g_t, 1.0, big[:L], True))
+        _, names, full = names_run(lambda: s.pfb_synthesis_batch(spec, hop, g_t, 1.0, big[:L], True))
         assert sorted(names) == composed, names
         default_units = _syn_units(full)
         assert len(default_units) == 1 and default_units[0][0] == 4, (full, "aligned inputs run the wide form by default")
         pa.set_variant(AB_PFB_SYN_SCALAR)
-        _, names, full = kernels_run(lambda: s.pfb_synthesis_batch(spec, hop, g_t, 1.0, big[:L], True))
+        _, names, full = names_run(lambda: s.pfb_synthesis_batch(spec, hop, g_t, 1.0, big[:L], True))
         assert sorted(names) == composed and _syn_units(full) == [(1, default_units[0][1])], full
         pa.set_variant(AB_PFB_SYN_PLAIN)
-        _, names, full = kernels_run(lambda: s.pfb_synthesis_batch(spec, hop, g_t, 1.0, big[:L], True))
+        _, names, full = names_run(lambda: s.pfb_synthesis_batch(spec, hop, g_t, 1.0, big[:L], True))
         assert _syn_units(full) == [(4, 0)], full
         pa.set_variant(AB_PFB_SYN_XCD)
-        _, names, full = kernels_run(lambda: s.pfb_synthesis_batch(spec, hop, g_t, 1.0, big[:L], True))
+        _, names, full = names_run(lambda: s.pfb_synthesis_batch(spec, hop, g_t, 1.0, big[:L], True))
         assert _syn_units(full) == [(4, 1)], full
         pa.set_variant(0)
         # a signal that does not start on a 16-byte boundary, an odd hop and a prototype off its 8-byte grid: the scalar form
-        _, names, full = kernels_run(lambda: s.pfb_synthesis_batch(spec, hop, g_t, 1.0, big[1:L + 1], True))
+        _, names, full = names_run(lambda: s.pfb_synthesis_batch(spec, hop, g_t, 1.0, big[1:L + 1], True))
         assert [u for u, _ in _syn_units(full)] == [1], full
         L3 = sm.samples_out(N, 333, taps, nframes) * 2
-        _, names, full = kernels_run(lambda: s.pfb_synthesis_batch(spec, 333, g_t, 1.0, torch.empty(L3, device="cuda"), True))
+        _, names, full = names_run(lambda: s.pfb_synthesis_batch(spec, 333, g_t, 1.0, torch.empty(L3, device="cuda"), True))
         assert [u for u, _ in _syn_units(full)] == [1], full
         g_off = torch.empty(taps * N + 1, device="cuda", dtype=torch.float32).uniform_(-1, 1)[1:]
-        _, names, full = kernels_run(lambda: s.pfb_synthesis_batch(spec, hop, g_off, 1.0, big[:L], True))
+        _, names, full = names_run(lambda: s.pfb_synthesis_batch(spec, hop, g_off, 1.0, big[:L], True))
         assert [u for u, _ in _syn_units(full)] == [1], full
         # pitched spectra: the row kernel in front of the transform
         pitched = torch.empty((nframes, 2 * N + 8), device="cuda", dtype=torch.float32).uniform_(-1, 1)[:, :2 * N]
-        _, names, full = kernels_run(lambda: s.pfb_synthesis_batch(pitched, hop, g_t, 1.0, big[:L], True))
+        _, names, full = names_run(lambda: s.pfb_synthesis_batch(pitched, hop, g_t, 1.0, big[:L], True))
         assert sorted(names) == sorted(composed + ["frames_rows_kernel"]), names
     finally:
         pa.set_variant(0)

@@ -20,6 +20,7 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pffft_amd as pa  # noqa: E402
+from gpu_kit import assert_guards, assert_same_bits, guarded, kernels_run, make_signal, need_gpu, same_bits, SENTINEL, TDT, traced, windows  # noqa: E402,F401
 
 AB_PSD_COMPOSED, AB_PSD_FUSED = 134, 135
 SELECTORS = {"default": 0, "composed": AB_PSD_COMPOSED, "fused": AB_PSD_FUSED}
@@ -27,57 +28,8 @@ FUSED_N = (1024, 2048, 4096)
 NAVG = (1, 2, 31, 32, 33, 64, 65, 100, 0)
 NFRAMES_ALL = 70                    # frames per signal of the navg = 0 cases: runs of 32, 32 and 6
 SCALING = 1.0 / 37.0                # no power of two: the one product rounds
-SENTINEL = -77.0
-DT = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64}
+DT = TDT
 PEAK = 8e12
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available() or pa.device_count() < 1:
-        pytest.fail("GPU tests need a HIP device: the product has no CPU fallback")
-    torch.cuda.set_device(0)
-    yield
-    pa.set_variant(0)
-    torch.cuda.empty_cache()
-
-
-def kernels_run(fn):
-    """(fn(), names of the device kernels it ran): a kineto trace of the one call (the helper of tests/test_gpu_frames.py)."""
-    from torch.profiler import ProfilerActivity, profile
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        out = fn()
-        torch.cuda.synchronize()
-    names = []
-    for e in prof.events():
-        if e.device_type == torch.autograd.DeviceType.CUDA and not e.name.startswith(("Memcpy", "Memset")):
-            names.append(e.name.split("(")[0].split("<")[0].replace("void ", "").replace("pf::", "").strip())
-    assert names, "the trace recorded no kernel"
-    return out, names
-
-
-def bits(t):
-    return t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int64)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(bits(a), bits(b))
-
-
-def windows(N, dtype, seed):
-    rng = np.random.default_rng(seed)
-    return {"hann": fm.hann(N, dtype), "random": rng.uniform(-1, 1, N).astype(dtype), "none": None}
-
-
-def make_signal(nsignals, scalars, pad, dtype, seed, offset=0):
-    """[nsignals, scalars] view of a [nsignals, scalars + pad] tensor (pad > 0: a padded row stride); one signal: 1-D, `offset` scalars
-    into its allocation (offset = 1: no 16-byte alignment)."""
-    g = torch.Generator(device="cuda"); g.manual_seed(seed)
-    full = torch.empty((nsignals, offset + scalars + pad), device="cuda", dtype=DT[np.dtype(dtype)])
-    full.uniform_(-1.0, 1.0, generator=g)
-    view = full[:, offset:offset + scalars]
-    return view[0] if nsignals == 1 else view
 
 
 def power_rows(s, sig, hop, nframes, w_t):
@@ -177,7 +129,7 @@ def test_composed_only_cases_bit_for_bit(case):
         assert sig.data_ptr() % 16 == 4
         pa.set_variant(AB_PSD_FUSED)
         try:
-            _, names = kernels_run(lambda: s.frames_psd_batch(sig, 256, 64, None, 16, SCALING))
+            _, names = kernels_run(lambda: s.frames_psd_batch(sig, 256, 64, None, 16, SCALING), short=True)
         finally:
             pa.set_variant(0)
         assert sorted(names) == ["fft_tiled_kernel", "frames_gather_kernel", "psd_runs_kernel"], names
@@ -200,19 +152,19 @@ def test_which_kernel_ran(N):
                 call()                                                       # first use outside the traces
             pa.set_variant(AB_PSD_FUSED)
             assert pa.frames_psd_route(s, hop, 0, navg) == "fused"
-            _, names = kernels_run(call)
+            _, names = kernels_run(call, short=True)
             assert names == ["fft_psd_kernel"] + reduce, (navg, names)
             pa.set_variant(AB_PSD_COMPOSED)
             assert pa.frames_psd_route(s, hop, 0, navg) == "composed"
-            _, names = kernels_run(call)
+            _, names = kernels_run(call, short=True)
             assert sorted(names) == sorted(composed + reduce), (navg, names)
             pa.set_variant(0)
             route = pa.frames_psd_route(s, hop, 0, navg)
-            _, names = kernels_run(call)
+            _, names = kernels_run(call, short=True)
             assert (names == ["fft_psd_kernel"] + reduce) if route == "fused" else (sorted(names) == sorted(composed + reduce)), (route, names)
         # a hop that is no multiple of 16 bytes is composed whatever the selector says
         pa.set_variant(AB_PSD_FUSED)
-        _, names = kernels_run(lambda: s.frames_psd_batch(sig, 333, 96, w_t, 32, SCALING))
+        _, names = kernels_run(lambda: s.frames_psd_batch(sig, 333, 96, w_t, 32, SCALING), short=True)
         assert sorted(names) == sorted(composed), names
     finally:
         pa.set_variant(0)
@@ -265,7 +217,7 @@ def test_fused_loops_bit_for_bit(N, navg):
     two runs per group through the partial buffer, at half as many groups.  The long call must equal calls of 256 groups bit for bit, 64
     sampled groups plus the first and the last must equal the model over the existing entry's power rows, and the sentinel rows in
     front of and behind the output must be intact."""
-    from test_gpu_launch_shapes import assert_grid_loops, assert_guards, assert_same_bits, cus, guarded, traced
+    from test_gpu_launch_shapes import assert_grid_loops, cus
     s = pa.Setup(N, pa.REAL)
     head = pa.describe(s).strip().split("\n")[0]
     core = ls.core_vector_bytes(head)

@@ -14,20 +14,7 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pffft_amd as pa  # noqa: E402
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available() or pa.device_count() < 1:
-        pytest.fail("GPU tests need a HIP device: the product has no CPU fallback")
-    torch.cuda.set_device(0)
-
-
-def _uniform(shape, seed, dtype=torch.float32):
-    g = torch.Generator(device="cuda"); g.manual_seed(seed)
-    x = torch.empty(shape, device="cuda", dtype=dtype)
-    x.uniform_(-1.0, 1.0, generator=g)
-    return x
+from gpu_kit import need_gpu, uniform_t  # noqa: E402,F401
 
 
 # ------------------------------------------------------------------ BASELINE configs[4] at its stated sizes
@@ -35,7 +22,7 @@ def test_c5_full_batch_per_gpu(ref):
     """N=1024 complex double forward, batch 2^20 = the per-GPU shard of configs[4] (16 GiB in + 16 GiB out)."""
     N, B = 1024, 1 << 20
     s = pa.Setup(N, pa.COMPLEX, np.float64)
-    x = _uniform((B, 2 * N), 5, torch.float64)
+    x = uniform_t((B, 2 * N), 5, torch.float64)
     y = s.transform_batch(x, None, pa.FORWARD, False)
     idx = torch.tensor(sorted({0, 1, 7, 8, 9, 63, 64, 65, B // 2, B - 2, B - 1} | set(range(1000, B, 251)))).cuda()
     assert idx.numel() >= 4096                                # SURVEY.md §8(d): >= 4096 sampled transforms
@@ -62,7 +49,7 @@ def test_c5_strong_scaling_one_gpu_in_place(ref):
     if free < (B * 2 * N * 8) + (8 << 30):
         pytest.fail(f"needs 128 GiB + margin of HBM, {free >> 30} GiB free")
     s = pa.Setup(N, pa.COMPLEX, np.float64)
-    x = _uniform((B, 2 * N), 55, torch.float64)
+    x = uniform_t((B, 2 * N), 55, torch.float64)
     idx = torch.tensor(sorted({0, 1, 2, B // 3, B // 2, B - 2, B - 1} | set(range(12345, B, 2039)))).cuda()
     assert idx.numel() >= 4096                                # >= 4096 sampled transforms
     keep = x[idx].cpu().numpy()
@@ -127,8 +114,8 @@ def test_big_setup_zconvolve_long_batch(ref):
     N, B = 65536, 160
     s = pa.Setup(N, pa.COMPLEX)
     assert pa.kernel_name(s) == "fourstep"
-    a, b = _uniform((B, 2 * N), 21), _uniform((B, 2 * N), 22)
-    ab0 = _uniform((B, 2 * N), 23)
+    a, b = uniform_t((B, 2 * N), 21), uniform_t((B, 2 * N), 22)
+    ab0 = uniform_t((B, 2 * N), 23)
     rs = ref.setup(N, 1)
     for acc in (True, False):
         for bc in (False, True):
@@ -144,7 +131,7 @@ def test_big_setup_on_two_streams(ref):
     """two streams running the same beyond-LDS setup concurrently must not share scratch."""
     N, B = 65536, 24
     s = pa.Setup(N, pa.COMPLEX)
-    xa, xb = _uniform((B, 2 * N), 31), _uniform((B, 2 * N), 32)
+    xa, xb = uniform_t((B, 2 * N), 31), uniform_t((B, 2 * N), 32)
     ya_ref = s.transform_batch(xa, None, pa.FORWARD, True).clone()
     yb_ref = s.transform_batch(xb, None, pa.FORWARD, False).clone()
     torch.cuda.synchronize()
@@ -222,7 +209,7 @@ def test_fastconv_batch_strided_rows_and_empty():
     taps, L = 4096, 1 << 18
     h = np.random.default_rng(3).uniform(-1, 1, taps).astype(np.float32)
     fc = pa.FastConv(h, 0, 0)
-    big = _uniform((4, L + 4096), 77)
+    big = uniform_t((4, L + 4096), 77)
     x = big[:, :L]                                # row stride L + 4096
     out = torch.zeros((4, L + 64), device="cuda")
     y, n = fc.apply_batch(x, True, out=out[:, :L])
@@ -348,7 +335,7 @@ def test_stockham_direct_first_stage(ref, dt, tr, N):
     rs = ref.setup(N, tr, dt)
     try:
         for B in (1, 3, 7, 1031):
-            x = _uniform((B, s.vec_scalars), 400 + B, tdt)
+            x = uniform_t((B, s.vec_scalars), 400 + B, tdt)
             idx = sorted({0, B // 2, B - 1})
             xh = x[idx].cpu().numpy()
             modes = [(pa.FORWARD, False), (pa.FORWARD, True), (pa.BACKWARD, True)]
@@ -384,7 +371,7 @@ def test_stockham_direct_first_stage_steady_state(ref, dt, tr, N):
     rs = ref.setup(N, tr, dt)
     vec_bytes = s.vec_scalars * (4 if dt == np.float32 else 8)
     B = ((4 << 30) if vec_bytes <= 4096 else (1 << 30)) // vec_bytes + 3      # ragged tail
-    x = _uniform((B, s.vec_scalars), 500 + N, tdt)
+    x = uniform_t((B, s.vec_scalars), 500 + N, tdt)
     # product build (pffft_hip_has_variants() == 0): selectors 54 / 55 reach the SAME kernel (one variant per plan is instantiated),
     # so the bit-for-bit comparison below compares a kernel with itself - the reference then checks >= 512 sampled vectors
     nsamp = 6 if pa.has_variants() else 512
@@ -431,8 +418,8 @@ def test_every_compile_time_stockham_plan_against_reference(ref, dt, tr):
             s = pa.Setup(N, tr, dtype)
             rs = ref.setup(N, tr, dtype)
             tol = tol_for(dt, N)
-            x = _uniform((7, s.vec_scalars), 600 + n, tdt)
-            xl = _uniform((2051, s.vec_scalars), 601 + n, tdt)
+            x = uniform_t((7, s.vec_scalars), 600 + n, tdt)
+            xl = uniform_t((2051, s.vec_scalars), 601 + n, tdt)
             xh = x.cpu().numpy()
             for d in (pa.FORWARD, pa.BACKWARD):
                 for o in (False, True):
@@ -461,7 +448,7 @@ def test_streaming_passes_for_sizes_beyond_the_stockham_plans(ref, dt, tr, N):
     s = pa.Setup(N, tr, dtype)
     rs = ref.setup(N, tr, dtype)
     tol = tol_for(dt, N)                                  # north_star's bar, flat: 1e-5 float whatever N
-    x = _uniform((3, s.vec_scalars), 700 + N % 997, tdt)
+    x = uniform_t((3, s.vec_scalars), 700 + N % 997, tdt)
     xh = x.cpu().numpy()
     for d in (pa.FORWARD, pa.BACKWARD):
         for o in (False, True):

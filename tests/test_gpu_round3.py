@@ -16,13 +16,7 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pffft_amd as pa  # noqa: E402
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available() or pa.device_count() < 1:
-        pytest.fail("GPU tests need a HIP device: the product has no CPU fallback")
-    torch.cuda.set_device(0)
+from gpu_kit import need_gpu, uniform_t  # noqa: E402,F401
 
 
 def expected_family(N, transform, dt):
@@ -42,13 +36,6 @@ def expected_family(N, transform, dt):
     return "fourstep"
 
 
-def _uniform(shape, seed, tdt):
-    g = torch.Generator(device="cuda"); g.manual_seed(seed)
-    x = torch.empty(shape, device="cuda", dtype=tdt)
-    x.uniform_(-1.0, 1.0, generator=g)
-    return x
-
-
 def _check_size(ref, N, tr, dt, batch):
     dtype = np.float32 if dt == "f32" else np.float64
     tdt = torch.float32 if dt == "f32" else torch.float64
@@ -56,7 +43,7 @@ def _check_size(ref, N, tr, dt, batch):
     assert pa.kernel_name(s) == expected_family(N, tr, dt), (dt, tr, N, pa.kernel_name(s))
     rs = ref.setup(N, tr, dtype)
     tol = tol_for(dt, N)
-    x = _uniform((batch, s.vec_scalars), 3000 + N % 9973, tdt)
+    x = uniform_t((batch, s.vec_scalars), 3000 + N % 9973, tdt)
     xh = x.cpu().numpy()
     worst = 0.0
     for d in (pa.FORWARD, pa.BACKWARD):
@@ -166,7 +153,7 @@ def test_odd_stage_tile_plans(ref, dt, N):
     for tr, NN in ((pa.COMPLEX, N), (pa.REAL, 2 * N)):
         _check_size(ref, NN, tr, dt, batch=2)
         s = pa.Setup(NN, tr, dtype)
-        x = _uniform((2, s.vec_scalars), 77 + N % 1000, tdt)
+        x = uniform_t((2, s.vec_scalars), 77 + N % 1000, tdt)
         a = s.transform_batch(x, None, pa.FORWARD, True)
         pa.set_variant(83)
         try:

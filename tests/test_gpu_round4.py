@@ -6,6 +6,7 @@ import pytest
 import pffft_amd as pa
 
 torch = pytest.importorskip("torch")
+from gpu_kit import rand_t  # noqa: E402,F401
 pytestmark = pytest.mark.gpu
 
 
@@ -167,11 +168,6 @@ def test_convolve_batch_c2_c5_shapes(ref, dt, tol, N, B):
 
 
 # ------------------------------------------------------------------ long batches of the in-order families against the reference
-def _uniform(shape, seed, tdt):
-    g = torch.Generator(device="cuda"); g.manual_seed(seed)
-    return torch.rand(shape, device="cuda", dtype=tdt, generator=g) * 2 - 1
-
-
 @pytest.mark.parametrize("dt,tr,N", [(np.float32, pa.COMPLEX, 4320), (np.float32, pa.COMPLEX, 8192), (np.float32, pa.COMPLEX, 8640),
                                      (np.float64, pa.COMPLEX, 2160), (np.float64, pa.COMPLEX, 3072), (np.float64, pa.COMPLEX, 4096),
                                      (np.float32, pa.COMPLEX, 480 * 256), (np.float64, pa.COMPLEX, 480 * 128),
@@ -187,7 +183,7 @@ def test_in_order_families_on_long_ragged_batches(ref, dt, tr, N):
     rs = ref.setup(N, tr, dt)
     vec_bytes = s.vec_scalars * np.dtype(dt).itemsize
     B = max(4 * 256 * 4 + 7, (1 << 29) // vec_bytes + 7)          # >= 4 groups per resident workgroup slot, ragged
-    x = _uniform((B, s.vec_scalars), 40 + N % 1000, tdt)
+    x = rand_t((B, s.vec_scalars), 40 + N % 1000, tdt)
     rng = np.random.default_rng(N)
     idx = sorted({0, 1, 2, B // 2, B - 3, B - 2, B - 1} | set(rng.integers(0, B, 512).tolist()))
     it = torch.tensor(idx, device="cuda")
@@ -217,7 +213,7 @@ def test_real_forward_two_sweeps(ref, dt, tol, lg):
     s = pa.Setup(N, pa.REAL, dt)
     rs = ref.setup(N, pa.REAL, dt)
     B = 5
-    x = _uniform((B, N), 90 + lg, tdt)
+    x = rand_t((B, N), 90 + lg, tdt)
     xh = x.cpu().numpy()
     from oracle.ref import FORWARD
     want = rs.batch(xh, FORWARD, True)
@@ -270,7 +266,7 @@ def test_runtime_tile_plans(ref, dt, N):
         s = pa.Setup(NN, tr, dtype)
         rs = ref.setup(NN, tr, dtype)
         B = 24 if dt == "f32" else 12
-        x = _uniform((B, s.vec_scalars), 4242 + N % 1000, tdt)
+        x = rand_t((B, s.vec_scalars), 4242 + N % 1000, tdt)
         xh = x[[0, B // 2, B - 1]].cpu().numpy()
         for d in (pa.FORWARD, pa.BACKWARD):
             got_o = s.transform_batch(x, None, d, True)
@@ -341,9 +337,9 @@ def test_device_entries_replay_from_a_hip_graph(ref):
         s1 = pa.Setup(1024, pa.COMPLEX)
         s2 = pa.Setup(1 << 16, pa.COMPLEX)
         fc = pa.FastConv(h, 0, 0)
-        x1 = _uniform((300, 2048), 1, torch.float32); y1 = torch.empty_like(x1); c1 = torch.empty_like(x1)
-        x2 = _uniform((5, 2 << 16), 2, torch.float32); y2 = torch.empty_like(x2)
-        xs = _uniform((300001,), 3, torch.float32); ys = torch.zeros_like(xs)
+        x1 = rand_t((300, 2048), 1, torch.float32); y1 = torch.empty_like(x1); c1 = torch.empty_like(x1)
+        x2 = rand_t((5, 2 << 16), 2, torch.float32); y2 = torch.empty_like(x2)
+        xs = rand_t((300001,), 3, torch.float32); ys = torch.zeros_like(xs)
         H = s1.transform_batch(x1[:1].contiguous(), None, pa.FORWARD, False).reshape(-1).contiguous()
 
         def work():
@@ -387,7 +383,7 @@ def test_values_do_not_depend_on_the_launch_shape(dt, tr, N):
     s = pa.Setup(N, tr, dtype)
     vb = s.vec_scalars * np.dtype(dtype).itemsize
     big = max(64, min((160 << 20) // vb, 40000))          # many groups per workgroup for the LDS-resident sizes
-    x = _uniform((big, s.vec_scalars), 31 + N % 97, tdt)
+    x = rand_t((big, s.vec_scalars), 31 + N % 97, tdt)
     for d in (pa.FORWARD, pa.BACKWARD):
         for o in (True, False):
             full = s.transform_batch(x, None, d, o)

@@ -10,6 +10,7 @@ import pytest
 import pffft_amd as pa
 
 torch = pytest.importorskip("torch")
+from gpu_kit import rand_t  # noqa: E402,F401
 pytestmark = pytest.mark.gpu
 
 
@@ -20,11 +21,6 @@ def ref():
         from conftest import missing_checker
         missing_checker("oracle/_ref/libpffft_ref.so")
     return oref.get()
-
-
-def _uniform(shape, seed, tdt=None):
-    g = torch.Generator(device="cuda"); g.manual_seed(seed)
-    return torch.rand(shape, device="cuda", dtype=tdt or torch.float32, generator=g) * 2 - 1
 
 
 # ------------------------------------------------------------------ pffastconv hint flags (include/pffft/pffastconv.h:100-126)
@@ -83,7 +79,7 @@ def test_ten_streams_round_robin_on_one_big_setup(ref, dt, tr, N):
     s = pa.Setup(N, tr, dtype)
     rs = ref.setup(N, tr, dtype)
     streams = [torch.cuda.Stream() for _ in range(10)]
-    xs = [_uniform((7, s.vec_scalars), 100 + i, tdt) for i in range(10)]
+    xs = [rand_t((7, s.vec_scalars), 100 + i, tdt) for i in range(10)]
     want = [s.transform_batch(x, None, pa.FORWARD, i % 2 == 0).clone() for i, x in enumerate(xs)]
     torch.cuda.synchronize()
     for i in (0, 9):
@@ -115,7 +111,7 @@ def test_beyond_lds_on_long_ragged_batches(ref, dt, tr, N):
     rs = ref.setup(N, tr, dtype)
     vb = s.vec_scalars * np.dtype(dtype).itemsize
     B = max(600, (640 << 20) // vb) + 3                           # >= 640 MiB of vectors: > 4 tiles per resident workgroup for every tile size
-    x = _uniform((B, s.vec_scalars), 77 + N % 1000, tdt)
+    x = rand_t((B, s.vec_scalars), 77 + N % 1000, tdt)
     rng = np.random.default_rng(N)
     idx = sorted({0, 1, B // 2, B - 2, B - 1} | set(rng.integers(0, B, 512).tolist()))
     it = torch.tensor(idx, device="cuda")
@@ -155,7 +151,7 @@ def test_two_threads_two_setups_select_the_device_themselves(ref):
                 for N, tr in ((1024, pa.COMPLEX), (1 << 16, pa.REAL)):
                     s = pa.Setup(N, tr)
                     rs = ref.setup(N, tr, np.float32)
-                    x = _uniform((33, s.vec_scalars), 900 + tid)
+                    x = rand_t((33, s.vec_scalars), 900 + tid)
                     for rep in range(4):
                         y = s.transform_batch(x, None, pa.FORWARD, bool(rep & 1))
                         st.synchronize()
@@ -184,7 +180,7 @@ def test_graph_replay_survives_larger_direct_calls_and_more_streams(ref):
     N = 1 << 16
     s = pa.Setup(N, pa.COMPLEX)
     with torch.cuda.stream(st):
-        x = _uniform((40, 2 * N), 5)
+        x = rand_t((40, 2 * N), 5)
         y = torch.empty_like(x)
         s.transform_batch(x, y, pa.FORWARD, True)                # warm-up: tables, this stream's scratch
         st.synchronize()
@@ -193,7 +189,7 @@ def test_graph_replay_survives_larger_direct_calls_and_more_streams(ref):
         with torch.cuda.graph(g, stream=st):
             s.transform_batch(x, y, pa.FORWARD, True)
         # (a) a larger direct batch on the same stream: the scratch grows
-        xb = _uniform((96, 2 * N), 6)
+        xb = rand_t((96, 2 * N), 6)
         yb = s.transform_batch(xb, None, pa.FORWARD, True)
         st.synchronize()
         y.zero_(); g.replay(); st.synchronize()
@@ -210,7 +206,7 @@ def test_graph_replay_survives_larger_direct_calls_and_more_streams(ref):
     # (c) replays on `st` while direct in-order launches of the same setup run on another stream: > one ring of counter slots apart is
     #     not needed - the captured launch's counters are outside the ring
     o = others[0]
-    big = _uniform((300, 2 * N), 8)
+    big = rand_t((300, 2 * N), 8)
     with torch.cuda.stream(o):
         wbig = s.transform_batch(big, None, pa.FORWARD, True).clone()
     torch.cuda.synchronize()
@@ -238,7 +234,7 @@ def test_c1024_short_launch_kernel_is_bit_identical(ref):
     s = pa.Setup(1024, pa.COMPLEX)
     rs = ref.setup(1024, pa.COMPLEX, np.float32)
     big = 1 << 17
-    x = _uniform((big, 2048), 12)
+    x = rand_t((big, 2048), 12)
     for d in (pa.FORWARD, pa.BACKWARD):
         for o in (True, False):
             full = s.transform_batch(x, None, d, o)
@@ -289,7 +285,7 @@ def test_transform_batch_multi_from_one_thread(ref, dt):
     multi = L.pffftd_hip_transform_batch_multi if dt == "f64" else L.pffft_hip_transform_batch_multi
     multi.restype = C.c_int
     N, B = 1024, 3000
-    x = _uniform((B, 2 * N), 21, torch.float64 if dt == "f64" else torch.float32)
+    x = rand_t((B, 2 * N), 21, torch.float64 if dt == "f64" else torch.float32)
     whole = pa.Setup(N, pa.COMPLEX, dtype)
     want = whole.transform_batch(x, None, pa.FORWARD, False)
     torch.cuda.synchronize()

@@ -12,6 +12,7 @@ import pffft_amd as pa
 from conftest import legal_sizes, relerr
 
 torch = pytest.importorskip("torch")
+from gpu_kit import mem_free, rand_t  # noqa: E402,F401
 pytestmark = pytest.mark.gpu
 
 AB_FIR_SPLIT, AB_FAKE_DEVICE = 119, 130
@@ -26,11 +27,6 @@ def ref():
     return oref.get()
 
 
-def _uniform(shape, seed, tdt=None):
-    g = torch.Generator(device="cuda"); g.manual_seed(seed)
-    return torch.rand(shape, device="cuda", dtype=tdt or torch.float32, generator=g) * 2 - 1
-
-
 # ------------------------------------------------------------------ FIR: 16384-sample blocks on 256 threads (fft_fir32.h)
 @pytest.mark.parametrize("taps,nsig,L", [(4096, 1, (1 << 22) + 12345), (4096, 40, 1 << 17), (2048, 1, 1 << 22), (1500, 3, 1500000),
                                          (851, 1, 4000001), (6000, 2, 3000000), (8192, 1, 1 << 22), (4096, 300, 20000)])
@@ -42,7 +38,7 @@ def test_fir32_block_kernel_against_reference_and_split_kernel(ref, taps, nsig, 
     samples; signals whose last block is partial or shorter than one row of the gather."""
     rng = np.random.default_rng(taps + nsig)
     h = rng.uniform(-1, 1, taps).astype(np.float32)
-    x = _uniform((nsig, L), taps * 3 + nsig)
+    x = rand_t((nsig, L), taps * 3 + nsig)
     fc = pa.FastConv(h, 0, 0)
     y = torch.full((nsig, L), 7.0, device="cuda")
     if nsig == 1:
@@ -91,7 +87,7 @@ def test_fir32_is_the_route_of_the_c4_throughput_shapes(ref):
     rng = np.random.default_rng(44)
     taps, nsig, L = 4096, 64, 1 << 20
     h = rng.uniform(-1, 1, taps).astype(np.float32)
-    x = _uniform((nsig, L), 9)
+    x = rand_t((nsig, L), 9)
     fc = pa.FastConv(h, 0, 0)
     y, n = fc.apply_batch(x, True)
     torch.cuda.synchronize()
@@ -113,11 +109,6 @@ def test_fir32_is_the_route_of_the_c4_throughput_shapes(ref):
 
 
 # ------------------------------------------------------------------ one setup, any device
-def _mem_free():
-    torch.cuda.synchronize()
-    return torch.cuda.mem_get_info()[0]
-
-
 @pytest.mark.parametrize("dt,tr,N", [("f32", pa.COMPLEX, 1024), ("f64", pa.COMPLEX, 1024), ("f32", pa.REAL, 16384), ("f32", pa.COMPLEX, 4000),
                                      ("f32", pa.COMPLEX, 1 << 16), ("f64", pa.REAL, 36864 * 2)])
 def test_one_setup_shared_by_threads_on_two_device_keys(ref, dt, tr, N):
@@ -129,10 +120,10 @@ def test_one_setup_shared_by_threads_on_two_device_keys(ref, dt, tr, N):
     from conftest import relerr, tol_for
     dtype = np.float32 if dt == "f32" else np.float64
     tdt = torch.float32 if dt == "f32" else torch.float64
-    free0 = _mem_free()
+    free0 = mem_free()
     s = pa.Setup(N, tr, dtype)
     assert pa.setup_devices(s) == []
-    x = _uniform((37, s.vec_scalars), N % 1000 + 1, tdt)
+    x = rand_t((37, s.vec_scalars), N % 1000 + 1, tdt)
     want_u = s.transform_batch(x, None, pa.FORWARD, False).clone()
     want_o = s.transform_batch(x, None, pa.FORWARD, True).clone()
     want_b = s.transform_batch(want_u, None, pa.BACKWARD, False).clone()
@@ -180,7 +171,7 @@ def test_one_setup_shared_by_threads_on_two_device_keys(ref, dt, tr, N):
     torch.cuda.empty_cache()
     assert pa.error_count() == e0
     # everything the setup held on both device keys is back (the allocator's granularity is 2 MiB)
-    assert _mem_free() >= free0 - (8 << 20), (free0, _mem_free())
+    assert mem_free() >= free0 - (8 << 20), (free0, mem_free())
 
 
 def test_fastconv_setup_follows_its_user_to_another_device_key(ref):
@@ -189,7 +180,7 @@ def test_fastconv_setup_follows_its_user_to_another_device_key(ref):
     rng = np.random.default_rng(5)
     for taps, L in ((4096, 1 << 20), (2048, 1 << 22), (300, 1 << 20), (17, 200000)):
         h = rng.uniform(-1, 1, taps).astype(np.float32)
-        x = _uniform((L,), taps)
+        x = rand_t((L,), taps)
         fc = pa.FastConv(h, 0, 0)
         y0, n0 = fc.apply(x, True)
         y0 = y0.clone()
@@ -231,7 +222,7 @@ def test_transform_batch_multi_same_setup_and_argument_matrix(ref, dt):
     dtype = np.float64 if dt == "f64" else np.float32
     multi = _multi(dt)
     N, B = 1024, 2500
-    x = _uniform((B, 2 * N), 31, torch.float64 if dt == "f64" else torch.float32)
+    x = rand_t((B, 2 * N), 31, torch.float64 if dt == "f64" else torch.float32)
     s = pa.Setup(N, pa.COMPLEX, dtype)
     want = s.transform_batch(x, None, pa.FORWARD, True).clone()
     torch.cuda.synchronize()
@@ -268,7 +259,7 @@ def test_one_setup_on_every_visible_device(ref, dt, tr, N):
     tdt = torch.float32 if dt == "f32" else torch.float64
     nd = pa.device_count()
     s = pa.Setup(N, tr, dtype)
-    x0 = _uniform((64, s.vec_scalars), 3, tdt)
+    x0 = rand_t((64, s.vec_scalars), 3, tdt)
     want = s.transform_batch(x0, None, pa.FORWARD, False).clone()
     torch.cuda.synchronize()
     rs = ref.setup(N, tr, dtype)
@@ -353,7 +344,7 @@ def test_fir_nonfinite_samples_stay_in_their_blocks(ref):
     rng = np.random.default_rng(8)
     taps, L = 2048, 1 << 22
     h = rng.uniform(-1, 1, taps).astype(np.float32)
-    x = _uniform((L,), 77)
+    x = rand_t((L,), 77)
     fc = pa.FastConv(h, 0, 0)
     clean, n = fc.apply(x, True)
     clean = clean.clone()
@@ -381,11 +372,11 @@ def test_graph_replay_equals_direct_call_on_lds_resident_routes(ref):
     h = rng.uniform(-1, 1, 4096).astype(np.float32)
     fc = pa.FastConv(h, 0, 0)
     with torch.cuda.stream(st):
-        x = _uniform((1 << 18, 2048), 5)
+        x = rand_t((1 << 18, 2048), 5)
         y = torch.empty_like(x)
         H = s.transform_batch(x[:1].contiguous(), None, pa.FORWARD, False)[0].contiguous()
         yc = torch.empty_like(x)
-        xs = _uniform((64, 1 << 20), 6)
+        xs = rand_t((64, 1 << 20), 6)
         ys = torch.zeros_like(xs)
         s.transform_batch(x, y, pa.FORWARD, False)                # warm-ups: tables on this stream
         s.convolve_batch(x, H, yc, 1.0 / 1024)
@@ -563,7 +554,7 @@ def test_real_forward_pair_pass_inside_the_row_pass(ref, dt, N):
         pa.set_variant(var)
         fused = "real-rows" in pa.describe(s) if var == 0 else True
         for batch in (1, 3):
-            x = _uniform((batch, N), 700 + batch, tdt)
+            x = rand_t((batch, N), 700 + batch, tdt)
             xh = x.cpu().numpy()
             outs = {}
             for v in (var, 121):

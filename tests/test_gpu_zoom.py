@@ -24,13 +24,13 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pffft_amd as pa  # noqa: E402
+from gpu_kit import guarded, kinds_by, mem_free, need_gpu, same_bits, SENTINEL, TDT, traced, under, uniform_t  # noqa: E402,F401
 
 SEL_COMPOSED, SEL_FUSED = zm.AB_ZOOM_COMPOSED, zm.AB_ZOOM_FUSED
 DTYPES = [np.float32, np.float64]
-DT = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64}
+DT = TDT
 BATCHES = (1, 7, 1000)
 PEAK = 8e12
-SENTINEL = -77.0
 SHORT = 256
 G = zm.on_grid
 # (N, K, f0, df), each for the failure it can expose: composed below N + K - 1 = 257 (3, 5) (200, 57); the smallest fused shape, odd ends
@@ -46,65 +46,10 @@ SHAPES = [(3, 5, 0.1, 0.07), (200, 57, -0.2, 1.0 / 3), (129, 129, G(0.3), G(1.0 
 FUSED_DEFAULT = {512: True, 1024: True, 2048: True, 4096: True}
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available() or pa.device_count() < 1:
-        pytest.fail("GPU tests need a HIP device: the product has no CPU fallback")
-    torch.cuda.set_device(0)
-    yield
-    pa.set_variant(0)
-    torch.cuda.empty_cache()
-
-
-def traced(fn):
-    """(fn(), [(kernel name, grid in workgroups or None)]) from a kineto trace of the one call; the grid from its chrome-trace export."""
-    import json
-    import os
-    import tempfile
-    from torch.profiler import ProfilerActivity, profile
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        out = fn()
-        torch.cuda.synchronize()
-    names = [e.name for e in prof.events()
-             if e.device_type == torch.autograd.DeviceType.CUDA and not e.name.startswith(("Memcpy", "Memset"))]
-    assert names, "the trace recorded no kernel"
-    grids = {}
-    with tempfile.TemporaryDirectory() as d:
-        path = os.path.join(d, "trace.json")
-        prof.export_chrome_trace(path)
-        with open(path) as f:
-            events = json.load(f).get("traceEvents", [])
-    for e in events:
-        g = (e.get("args") or {}).get("grid")
-        if e.get("cat") == "kernel" and isinstance(g, list) and len(g) == 3:
-            grids[e["name"]] = int(g[0]) * int(g[1]) * int(g[2])
-    return out, [(n, grids.get(n)) for n in names]
-
-
 def kinds(kernels):
     """The kernels of this feature by kind: 'zoom' = the convolution kernel with the zoom policy, 'conv' = the dense one, 'pad', 'crop'."""
-    out = []
-    for n, _ in kernels:
-        if "ZoomIO" in n:
-            out.append("zoom")
-        elif "zoom_pad_kernel" in n:
-            out.append("pad")
-        elif "zoom_crop_kernel" in n:
-            out.append("crop")
-        elif "fft_conv_kernel" in n:
-            out.append("conv")
-        else:
-            out.append("other")
-    return out
-
-
-def bits(t):
-    return t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int64)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(bits(a), bits(b))
+    return kinds_by((("ZoomIO", "zoom"), ("zoom_pad_kernel", "pad"), ("zoom_crop_kernel", "crop"), ("fft_conv_kernel", "conv")),
+                    [n for n, _ in kernels])
 
 
 def rows_under_1gib(N, K, M, dtype, want):
@@ -117,21 +62,8 @@ def uniform(batch, N, dtype, seed):
     return np.random.default_rng(seed).uniform(-1, 1, (batch, 2 * N)).astype(dtype)
 
 
-def uniform_t(shape, seed, tdt):
-    g = torch.Generator(device="cuda"); g.manual_seed(seed)
-    x = torch.empty(shape, device="cuda", dtype=tdt)
-    x.uniform_(-1.0, 1.0, generator=g)
-    return x
-
-
 def run(s, x_t, direction, sel=0, out=None):
-    pa.set_variant(sel)
-    try:
-        y = s.transform_batch(x_t, out, direction)
-        torch.cuda.synchronize()
-    finally:
-        pa.set_variant(0)
-    return y
+    return under(sel, lambda: s.transform_batch(x_t, out, direction))
 
 
 def sels_of(s):
@@ -307,12 +239,6 @@ def test_rows_do_not_depend_on_the_call(case):
 
 
 # ------------------------------------------------------------------ 5. every workgroup loops
-def guarded(rows, row, tdt):
-    """(allocation, its rows 2 ... rows + 2): two sentinel rows in front of the output and two behind."""
-    full = torch.full(((rows + 4) * row,), SENTINEL, device="cuda", dtype=tdt)
-    return full, full[2 * row:(rows + 2) * row].view(rows, row)
-
-
 @pytest.mark.parametrize("shape", [(129, 129), (700, 300), (300, 1700), (2047, 2050)], ids=lambda c: f"N{c[0]}-K{c[1]}")
 def test_fused_loops_at_the_bar(shape):
     """The convolution kernel with the zoom policy (the table registers are set once, before the loop) at the long batch of its convolution
@@ -467,11 +393,6 @@ def test_graph_replay_capture_rule_and_two_streams():
     s.close()
 
 
-def _mem_free():
-    torch.cuda.synchronize()
-    return torch.cuda.mem_get_info()[0]
-
-
 @pytest.mark.parametrize("dtype", DTYPES, ids=lambda d: np.dtype(d).name)
 def test_memory_is_back_after_close(dtype):
     """Two streams, two scratch images; after close() the device has what it had, within the allowance tests/test_gpu_any.py uses.  The
@@ -495,15 +416,15 @@ def test_memory_is_back_after_close(dtype):
     on_both(warm)
     warm.close()
     torch.cuda.empty_cache()
-    free0 = _mem_free()
+    free0 = mem_free()
     s = pa.ZoomSetup(N, K, f0, df, dtype)
     M = s.conv_size
     on_both(s)
     scratch = batch * M * 2 * np.dtype(dtype).itemsize
-    assert _mem_free() <= free0 - 2 * scratch + (8 << 20), (free0, _mem_free(), scratch)
+    assert mem_free() <= free0 - 2 * scratch + (8 << 20), (free0, mem_free(), scratch)
     s.close()
     torch.cuda.empty_cache()
-    assert _mem_free() >= free0 - (8 << 20), (free0, _mem_free())
+    assert mem_free() >= free0 - (8 << 20), (free0, mem_free())
 
 
 # ------------------------------------------------------------------ 7. time
