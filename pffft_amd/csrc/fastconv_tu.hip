@@ -6,8 +6,17 @@
 // The reference walks the blocks one by one on one core; here every block of the call is gathered
 // into a [nblk][Nfft] device image and pushed through the batched kernels in place:
 //   gather -> rFFT fwd (internal layout) -> x Hf * 1/Nfft -> rFFT bwd -> scatter.
-// (included at the end of pffft_hip.hip)
-#pragma once
+// A translation unit of libpffft_hip.so: it runs the transforms and helpers through the typed entries of pf_host.h.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+#include "../../include/pffft_hip.h"
+#include "pf_host.h"
+#include "pf_launch.h"
 #include "fft_fir.h"
 
 namespace pf {
@@ -612,7 +621,7 @@ PF_EXPORT int pffastconv_hip_apply_batch(PFFASTCONV_Setup* s, const float* d_inp
 // Host pointers (the reference's calling convention): up to FC_ZC_LIMIT bytes per signal there is no DMA copy — the signal
 // is copied by the CPU into a pinned host image that the kernel reads over PCIe directly, the kernel writes its outputs
 // into another pinned image, one stream synchronisation, CPU copy out (the same scheme as the transform entries,
-// pffft_hip.hip legacy_run).  Larger signals are staged through device buffers.  Failure: fail-soft like the transform
+// abi_tu.hip legacy_run).  Larger signals are staged through device buffers.  Failure: fail-soft like the transform
 // entries (stderr, pffft_hip_last_error(), error counter) and the return value -1, abort() only under PFFFT_HIP_ABORT=1.
 PF_EXPORT int pffastconv_apply(PFFASTCONV_Setup* s, const float* input, int cplxInputLen, float* output, int applyFlush) {
     using namespace pf;

@@ -1,38 +1,16 @@
-// Shared pieces of the LDS / streaming kernels that survive from the first coverage kernel (an in-place radix 2-5 transform in
-// one LDS image; every size it served now runs a Stockham plan or the streaming passes, and the kernel itself was removed in
-// round 3): the radix plan struct the setup keeps, bin_of() - the internal-layout map of SURVEY.md appendix A -, the in-place
-// DIF stage used by the strided fallback of fft_big.h, and the direct (no LDS image) zreorder / zconvolve kernels that serve
-// vectors beyond LDS and double precision (pffft_zreorder src/pffft_priv_impl.h:1158-1193, pffft_zconvolve_* :1534-1684).
+// Pieces the LDS / streaming kernels share (the in-place radix 2-5 kernel this file was written for is gone; every size it served runs a
+// Stockham plan or the streaming passes).  What it provides today:
+//   MAX_STAGES   bound of a radix schedule (StridedPlan, fft_big.h);
+//   bin_of()     the internal-layout map of SURVEY.md appendix A;
+//   gpad(), fdiv(), stage()   padded LDS index, fast division and the in-place DIF stage of the strided fallback of fft_big.h;
+//   zreorder_kernel, zconvolve_kernel   the direct (no LDS image) kernels that serve vectors beyond LDS and double precision
+//                (pffft_zreorder src/pffft_priv_impl.h:1158-1193, pffft_zconvolve_* :1534-1684).
 #pragma once
 #include "cxmath.h"
 
 namespace pf {
 
 constexpr int MAX_STAGES = 28;
-
-struct GenericPlan {
-    int n;        // complex length held in LDS: N (complex) or N/2 (real)
-    int nstages;
-    int is_real;
-    int G;        // transforms per workgroup pass
-    unsigned char radix[MAX_STAGES];
-};
-
-// canonical bin k (natural order) -> LDS position after the DIF passes (mixed-radix digit reversal)
-__device__ __forceinline__ int pos_of(int k, const GenericPlan& p) {
-    int pos = 0, m = p.n;
-    for (int s = 0; s < p.nstages; ++s) {
-        int R = p.radix[s], d;
-        switch (R) {
-            case 2: d = k & 1; k >>= 1; m >>= 1; break;
-            case 4: d = k & 3; k >>= 2; m >>= 2; break;
-            case 3: d = k % 3; k /= 3; m /= 3; break;
-            default: d = k % 5; k /= 5; m /= 5; break;
-        }
-        pos += d * m;
-    }
-    return pos;
-}
 
 // Spectrum bin stored at slot l (0..3) of 4-scalar group v of one vector in the pffft-internal
 // layout (SIMD_SZ == 4).  Closed forms checked against the reference's own pffft_zreorder

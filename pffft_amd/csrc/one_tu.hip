@@ -118,9 +118,9 @@ template <typename T> static OneFn<T> one_kernel(int flags) {
 
 template <typename T>
 static int launch_one_t(Setup* s, const T* in, T* out, size_t batch, int dir, int ordered, hipStream_t st) {
-    const bool bwd = dir == PFFFT_BACKWARD, real = s->transform == PFFFT_REAL;
-    const int flags = (real ? 8 : 0) | (bwd ? 4 : 0) | (!ordered ? (bwd ? 1 : 2) : 0);
-    const int pi = (flags == 5 && sizeof(T) == 4) ? 2 : bwd ? 1 : 0;      // (the float complex backward transform from the layout: a plan of its own)
+    const bool real = s->transform == PFFFT_REAL;
+    const int flags = layout_flags(dir, ordered, real);
+    const int pi = one_plan_index(sizeof(T) == 8, flags);      // (the float complex backward transform from the layout: a plan of its own)
     const StockPlan& p = s->one[pi];
     const size_t lds = one_lds<T>(p, real).total;
     auto k = one_kernel<T>(flags);

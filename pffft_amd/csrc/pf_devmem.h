@@ -16,7 +16,7 @@
 
 namespace pf {
 
-int fail(hipError_t e, const char* what);   // pffft_hip.hip (pf_host.h: PF_CHECK)
+int fail(hipError_t e, const char* what);   // plan_tu.hip (pf_host.h: PF_CHECK)
 bool stream_capturing(hipStream_t st);
 
 struct DeviceMem {

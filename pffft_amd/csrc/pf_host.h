@@ -1,6 +1,7 @@
 // Host-side declarations shared by the translation units of libpffft_hip.so: the plan ("PFFFT_Setup":
-// src/pffft_priv_impl.h:1051-1060), error plumbing and launch helpers.  pffft_hip.hip owns the definitions; dma_tu.hip
-// (the LDS-DMA staged kernels, compiled on their own so that they can be iterated on in seconds) uses them.
+// src/pffft_priv_impl.h:1051-1060), error plumbing and launch helpers, and what each unit offers the others.  The planner is
+// plan_tu.hip, the device state and the LDS-resident launchers pffft_hip.hip, the C ABI abi_tu.hip; every kernel family beyond those
+// has a *_tu.hip of its own.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -22,7 +23,14 @@
 
 namespace pf {
 
+#ifdef PFFFT_HIP_VARIANTS
+constexpr bool PF_HAS_VARIANTS = true;
+#else
+constexpr bool PF_HAS_VARIANTS = false;
+#endif
+
 extern thread_local std::string g_last_error;
+extern thread_local int g_ab_raw;   // pffft_hip_set_variant(): ab() decodes it (pf_route.h)
 int fail(hipError_t e, const char* what);
 #define PF_CHECK(expr)                                   \
     do {                                                 \
@@ -57,7 +65,8 @@ static int allow_big_lds(K kernel, size_t bytes) {
 // (it sat on the launch path of every tile pass and FIR call: pure host latency for the one-vector legacy entries)
 int cached_occupancy(const void* kernel, int threads, size_t lds, int* per_cu);
 
-enum Kernel { K_GENERIC = 0, K_C1024_F32 = 1, K_TILED = 2, K_BIG = 3 };
+// the class a SIZE is built for: K_STOCK its mixed-radix Stockham plan (fft_stock.h), K_BIG beyond LDS (streaming / tile passes, fft_one.h)
+enum Kernel { K_STOCK = 0, K_C1024_F32 = 1, K_TILED = 2, K_BIG = 3 };
 constexpr size_t LDS_MAX = 160 * 1024;
 constexpr unsigned CTR_RING = 4096;
 constexpr unsigned CTR_CAPTURED = 512;   // counter pairs set aside for launches recorded into a HIP graph (take_counters)
@@ -70,9 +79,6 @@ struct Setup {
     Kernel kernel;
     // what runs for [direction][ordered], decided at pffft_new_setup (plan_routes); pffft_hip_describe() prints it
     Route route[2][2];
-    GenericPlan gp;
-    int gthreads;
-    size_t glds;
     // mixed-radix Stockham plans (fft_stock.h): [0] forward order, [1] backward order of the same radices
     StockPlan sk[2], skw[2];          // workgroup-phase plans; wave-local plans (small n)
     int sk_threads = 0, skw_threads = 0;
@@ -155,9 +161,85 @@ inline int scratch_buffer(StreamScratch& pool, hipStream_t st, size_t bytes, con
     return 0;
 }
 
-// pffft_hip.hip, for frames_tu.hip: pffft(d)_hip_transform_batch on a checked setup, and the lazy device initialisation of a resolved one
+// ---- formulas more than one unit uses
+constexpr int SIMD = 4;  // the internal layout is the reference's SIMD_SZ == 4 layout (SURVEY.md finding 2)
+
+// radix schedule of the in-place DIF stages (fft_generic.h stage, the strided plans of fft_big.h): 5s, 3s, then 4s, then at most one 2
+constexpr int radix_schedule(int n, unsigned char* radix) {
+    int ns = 0;
+    while (n % 5 == 0) { radix[ns++] = 5; n /= 5; }
+    while (n % 3 == 0) { radix[ns++] = 3; n /= 3; }
+    while (n % 4 == 0) { radix[ns++] = 4; n /= 4; }
+    if (n % 2 == 0) { radix[ns++] = 2; n /= 2; }
+    return ns;
+}
+constexpr bool radix_schedule_is(int n, int ns, int r0, int r1, int r2, int r3) {
+    unsigned char r[MAX_STAGES] = {};
+    return radix_schedule(n, r) == ns && r[0] == r0 && r[1] == r1 && r[2] == r2 && r[3] == r3;
+}
+static_assert(radix_schedule_is(240, 4, 5, 3, 4, 4), "240 = 5 x 3 x 4 x 4");
+static_assert(radix_schedule_is(32, 3, 4, 4, 2, 0) && radix_schedule_is(1, 0, 0, 0, 0, 0), "one 2 at the end; nothing for 1");
+
+// bytes of an LDS image of `points` elements with one pad element per 32 (fft_generic.h gpad) and two spare
+constexpr size_t padded_image_bytes(size_t points, size_t elem_bytes) { return (points + (points >> 5) + 2) * elem_bytes; }
+static_assert(padded_image_bytes(2048, 8) == 16912 && padded_image_bytes(20480, 8) == 168976, "n + n / 32 + 2 elements");
+
+// workgroup threads of the strided kernels (fft_big.h): points / 8, rounded up to wavefronts, within 64 .. 1024
+constexpr int strided_threads(size_t points) {
+    const int th = (int)((points / 8 + 63) / 64 * 64);
+    return th < 64 ? 64 : (th > 1024 ? 1024 : th);
+}
+static_assert(strided_threads(256) == 64 && strided_threads(640) == 128 && strided_threads(4096) == 512 && strided_threads(100000) == 1024, "");
+
+// power-of-two n with a register-tiled kernel (fft_tiled.h): 16 .. 16384 points and at most 128 KiB per vector
+constexpr bool is_pow2_tiled(int n, size_t elem_bytes) {
+    return (n & (n - 1)) == 0 && n >= 16 && n <= 16384 && (size_t)n * elem_bytes <= 128 * 1024;
+}
+static_assert(is_pow2_tiled(16384, 8) && !is_pow2_tiled(16384, 16) && is_pow2_tiled(8192, 16), "float to 16384, double to 8192");
+static_assert(!is_pow2_tiled(8, 8) && !is_pow2_tiled(48, 8) && is_pow2_tiled(16, 16), "powers of two from 16");
+
+// resident wavefronts per CU of the N = 1024 short-launch kernel: 4 workgroups x C1024_ONCE_W wavefronts (35 KiB of LDS and 84 VGPRs each)
+constexpr int C1024_ONCE_W = 4, C1024_ONCE_RESIDENT = 16;
+
+// ---- plan_tu.hip: sizes, setups, routes and their text.  Nothing here launches.
+int min_fft_size(int transform);
+int is_valid_size(int N, int transform);
+int nearest_size(int N, int transform, int higher);
+int next_pow2(int N);
+int is_pow2(int N);
+void* aligned_malloc64(size_t nb);
+void aligned_free64(void* p);
+Setup* new_setup(int N, int transform, int is_double);
+void destroy_setup(Setup* s);
+int current_device_key(int* key);   // the key the calling thread's current device goes by (AB_FAKE_DEVICE: a key of its own)
+// the route of a (direction, layout) under a selector, planned as new_setup plans the stored ones (transform_batch and describe() under set_variant)
+Route plan_route(const Setup* s, int dir, int ordered, const AbSel& sel);
+const char* setup_family(const Setup* s);
+int describe_setup(const Setup* s, char* buf, size_t len);
+int validate_layout(FILE* dbg);
+
+// ---- pffft_hip.hip: the lazy device state, the LDS-resident launchers, the batched transform.  transform_batch / ensure_device are
+// instantiated there for float and double; the *_any twins serve the composed units behind type-erased pointers.
+template <typename T> int ensure_device(Setup* s);
+template <typename T> int transform_batch(Setup* s, const T* in, T* out, size_t batch, int dir, int ordered, hipStream_t st);
 int transform_batch_any(Setup* s, const void* in, void* out, size_t batch, int dir, int ordered, hipStream_t st);
 int ensure_device_any(Setup* s);
+int shift_transform_batch(Setup* s, const float* in, float* out, size_t batch, int ordered, double rate, double phase_rad, hipStream_t st);
+// the measured table of the register-tiled kernels (fft_tiled.h): the one planner input that needs kernel addresses; false: no kernel for n
+bool tiled_pick_any(bool is_double, int n, int dir, int real, int ordered, TiledSel* e);
+
+// ---- big_tu.hip: the sweeps of a FAM_BIG route (fft_big.h), as plan_big planned them
+int launch_big(Setup* s, const Route& r, const void* in, void* out, size_t batch, int dir, int ordered, hipStream_t st);
+
+// ---- aux_tu.hip: pffft_zreorder / pffft_zconvolve_* / the composed convolution, batched; instantiated there for float and double
+template <typename T> int zreorder_batch(Setup* s, const T* in, T* out, size_t batch, int dir, hipStream_t st);
+template <typename T> int zconvolve_batch(Setup* s, const T* a, const T* b, T* ab, T scaling, size_t batch, int accumulate, int b_broadcast, hipStream_t st);
+template <typename T> int convolve_batch(Setup* s, const T* in, const T* H, T* out, T scaling, size_t batch, int accumulate, int h_broadcast, hipStream_t st);
+
+// ---- abi_tu.hip: what pffastconv_apply shares with the legacy transform entries
+void legacy_fatal(int code, const char* entry, void* out, size_t out_bytes, bool out_is_host);
+bool is_device_ptr(const void* p);
+bool zero_copy_enabled();
 
 struct FcBatch { int nsig; size_t xstride, ystride; };   // signals of one pffastconv call (1 for the reference entries)
 

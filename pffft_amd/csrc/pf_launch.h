@@ -1,8 +1,11 @@
 // The one host launch path of the persistent ("loop") kernels: resident workgroups pull groups of vectors in order from a {next, done}
 // counter pair, and short launches run one group per workgroup in hardware dispatch order instead.  Every launcher of such a kernel
 // takes its grid and its counters from here and keeps only its own typed hipLaunchKernelGGL line.  The tile passes, launch_one, the
-// N = 1024 macros, the compile-time path of launch_stock and the zreorder / zconvolve launches follow other rules and stay on their own.
+// N = 1024 launchers, the compile-time path of launch_stock and the zreorder / zconvolve launches follow other rules and stay on their own.
+// Also here: the dispatchers from run-time (direction, layout) flags to the template arguments of a kernel.
 #pragma once
+#include <type_traits>
+
 #include "pf_host.h"
 
 namespace pf {
@@ -54,6 +57,22 @@ static int loop_launch(Setup* s, hipStream_t st, K kernel, int threads, size_t l
     if (int rc = loop_resident(kernel, threads, lds, &resident)) return rc;
     *ll = loop_take(s, st, resident, groups, oneshot);
     return 0;
+}
+
+// (direction, layout) -> the <DIR, IN_INTERNAL, OUT_INTERNAL> template triple of the kernels that read or write the internal layout
+// themselves (fft_c1024.h, fft_tiny.h).  `f` is a generic lambda called with three std::integral_constant<int, .>; exactly these four
+// triples exist as kernels: the forward transform never reads the layout, the backward one never writes it.
+template <class F>
+static int with_dir_layout(int dir, int ordered, F&& f) {
+    typedef std::integral_constant<int, 0> No;
+    typedef std::integral_constant<int, 1> Yes;
+    if (dir == FWD) return ordered ? f(std::integral_constant<int, FWD>{}, No{}, No{}) : f(std::integral_constant<int, FWD>{}, No{}, Yes{});
+    return ordered ? f(std::integral_constant<int, BWD>{}, No{}, No{}) : f(std::integral_constant<int, BWD>{}, Yes{}, No{});
+}
+// the two-way sibling: a run-time flag as a template argument
+template <class F>
+static int with_flag(bool on, F&& f) {
+    return on ? f(std::integral_constant<int, 1>{}) : f(std::integral_constant<int, 0>{});
 }
 
 }  // namespace pf

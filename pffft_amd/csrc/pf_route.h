@@ -148,6 +148,21 @@ struct BigPlan {             // n beyond LDS: the sweeps over HBM, in order
     int sweeps = 0;              // passes over the whole vector set
 };
 
+// The (direction, layout, real) flag bits every LDS-resident family shares (fft_stock.h, fft_one.h, fft_tiled.h: the low two): 1 = backward
+// FROM the internal layout, 2 = forward INTO it, 4 = backward, 8 = real.  dir: 0 forward, 1 backward (pffft_direction_t).
+constexpr int layout_flags(int dir, int ordered, bool real) {
+    return (!ordered ? (dir ? 1 : 2) : 0) | (dir ? 4 : 0) | (real ? 8 : 0);
+}
+static_assert(layout_flags(0, 1, false) == 0 && layout_flags(0, 0, false) == 2, "complex forward: canonical / into the layout");
+static_assert(layout_flags(1, 1, false) == 4 && layout_flags(1, 0, false) == 5, "complex backward: canonical / from the layout");
+static_assert(layout_flags(0, 1, true) == 8 && layout_flags(0, 0, true) == 10, "real forward");
+static_assert(layout_flags(1, 1, true) == 12 && layout_flags(1, 0, true) == 13, "real backward");
+
+// which of Setup::one[0..2] a flag set runs (fft_one.h): the float complex backward transform from the layout has a plan of its own
+constexpr int one_plan_index(bool is_double, int flags) { return (flags == 5 && !is_double) ? 2 : (flags & 4) ? 1 : 0; }
+static_assert(one_plan_index(false, 5) == 2 && one_plan_index(true, 5) == 1 && one_plan_index(false, 13) == 1, "the narrow plan: float complex only");
+static_assert(one_plan_index(false, 2) == 0 && one_plan_index(false, 4) == 1 && one_plan_index(true, 10) == 0, "else the plan of the direction");
+
 struct Route {
     Family fam = FAM_NONE;
     LaunchRule rule = LR_DISPATCH;

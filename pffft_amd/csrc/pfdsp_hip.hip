@@ -70,7 +70,7 @@ static void* g_stage = nullptr;
 static size_t g_stage_bytes = 0;
 
 // blocks up to ZC_LIMIT on host pointers: CPU memcpy into one pinned host image, the kernel rotates it in place over
-// PCIe, one synchronisation, CPU memcpy out — no DMA copies (same scheme as the legacy FFT entries, pffft_hip.hip)
+// PCIe, one synchronisation, CPU memcpy out — no DMA copies (same scheme as the legacy FFT entries, abi_tu.hip)
 constexpr size_t ZC_LIMIT = 256 * 1024;
 static void* g_pinned = nullptr;
 static size_t g_pinned_bytes = 0;

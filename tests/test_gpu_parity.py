@@ -662,7 +662,7 @@ def test_fastconv_short_filters_complex_io(ref, taps, flags):
 @pytest.mark.parametrize("taps", [129, 600, 1024, 2048, 4096, 5000])
 def test_fastconv_long_signals(ref, taps):
     """Throughput regime (signals long enough for >= one internal block per CU): the same outputs are computed through
-    longer INTERNAL blocks (Nfft 8192 / 16384, pffastconv_impl.h fc_big_nfft) while the number of samples a call produces
+    longer INTERNAL blocks (Nfft 8192 / 16384, fastconv_tu.hip fc_big_nfft) while the number of samples a call produces
     follows the reference's block schedule exactly — flush and no flush — and the values meet the reference's FIR bar
     against a float64 direct convolution (sampled windows) and against the reference on the whole signal."""
     L = (1 << 22) + 12345
