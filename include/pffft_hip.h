@@ -269,6 +269,54 @@ int pffftd_hip_frames_psd_batch(PFFFTD_Setup *, const double *signal, size_t sig
  * Host arithmetic only; PFFFT_Setup and PFFFTD_Setup handles. */
 const char *pffft_hip_frames_psd_route(const void *setup, size_t hop, size_t signal_stride, size_t navg);
 
+/* Averaged cross-spectra and coherence of TWO signals over overlapping frames (Welch's method; scipy's csd / coherence without detrending,
+ * one-sided doubling or normalisation) without the two nframes x N spectrograms.  x and y are framed alike: framing, `window` (NULL = no
+ * product), `hop`, the sample / scalar rules, the grouping by `navg` (0 = nframes, else nframes % navg == 0; output row v = i*G + g with
+ * G = nframes / navg), P (N/2 + 1 for a real setup, N for a complex one), real and complex setups, float and double, every legal size and
+ * the rules of the two per-stream buffers during HIP graph capture are exactly those of pffft_hip_frames_psd_batch.  x_stride and y_stride
+ * may differ (neither is read when nsignals == 1); y == x is legal; out must not overlap x or y.
+ * `what` selects the row written at out + v*out_stride (0 = dense):
+ *     PFFFT_HIP_CSD_CROSS      P complex bins, (re, im) interleaved: 2P scalars - the cross-spectrum Pxy
+ *     PFFFT_HIP_CSD_ALL        Pxx[P] | Pyy[P] | Pxy[2P]: 4P scalars
+ *     PFFFT_HIP_CSD_COHERENCE  P scalars |Sxy|^2 / (Sxx*Syy); `scaling` is not read
+ * ARITHMETIC - THE ORDER IS PART OF THE CONTRACT.  X_f and Y_f are the ordered spectra that pffft_hip_frames_transform_batch(...,
+ * PFFFT_HIP_FRAMES_ORDERED) produces for frame f of x and of y, bit for bit.  Per frame and bin, every product and every sum rounded once,
+ * no FMA:
+ *     c_re = Xr*Yr + Xi*Yi,   c_im = Xr*Yi - Xi*Yr          (conj(X) * Y, scipy's convention)
+ * and pxx, pyy are exactly the PFFFT_HIP_FRAMES_POWER expressions of x and of y.  The two real-only bins of a real setup (the packed bin 0)
+ * give (X_0*Y_0, +0) and (X_{N/2}*Y_{N/2}, +0).  Each of the four sums is accumulated exactly as pffft_hip_frames_psd_batch accumulates:
+ * runs of PFFFT_HIP_PSD_RUN consecutive frames, f ascending, started from the first term; then the run partials ascending, started from
+ * the first.  CROSS and ALL multiply each sum ONCE by `scaling`.  COHERENCE forms (Sre*Sre + Sim*Sim) / (Sxx*Syy) from the UNSCALED group
+ * sums: two squares, one sum, one product, one IEEE division, each rounded once; 0/0 = NaN.  No atomics: the result is deterministic and
+ * equal on every route.  Hence: Pxx and Pyy of ALL are the bits of pffft_hip_frames_psd_batch for x and for y; csd(x, x) has those bits in
+ * its real parts and a zero in every imaginary part; csd(y, x) is csd(x, y) with every non-zero imaginary part negated; coherence(x, x) is
+ * exactly 1 wherever Sxx*Sxx neither overflows nor underflows.
+ * ROUTES.  Everything runs COMPOSED: the framing kernel for the x frames and for the y frames of whole runs into the two halves of the
+ * per-stream frame matrix (the 256 MiB cap holds for both together), ONE pffft_hip_transform_batch(ordered = 1) over both halves, a kernel
+ * that walks each run's rows of both sets in order, and for averages longer than one run the partial buffer of the PSD entry (rows of 2P
+ * scalars for CROSS, 4P for ALL and COHERENCE) with its reduction, which forms the coherence ratio.  The cross-spectrum of real float
+ * setups of N = 1024 / 2048 / 4096 runs FUSED when hop, x_stride and y_stride are multiples of 4 and x, y and window are 16-byte aligned
+ * (out needs scalar alignment only): one kernel runs the framed transform twice per frame, keeps X_f in registers while Y_f is computed,
+ * accumulates the products in registers and stores once per run - 2*hop + 2P / min(navg, 32) scalars of HBM traffic per frame.  ALL and
+ * COHERENCE have no fused kernel (their four sums do not fit the register file next to two spectra).
+ * Validation happens before any device is touched: what the PSD entry refuses, an unknown `what`, a NULL y, a y_stride smaller than one
+ * signal's scalars when nsignals > 1, an out_stride smaller than the row of `what` -> non-zero, nothing launched.  nsignals == 0 or
+ * nframes == 0 -> 0, nothing launched. */
+#define PFFFT_HIP_CSD_CROSS 0
+#define PFFFT_HIP_CSD_ALL 1
+#define PFFFT_HIP_CSD_COHERENCE 2
+int pffft_hip_frames_csd_batch(PFFFT_Setup *, const float *x, size_t x_stride, const float *y, size_t y_stride, size_t nsignals,
+                               size_t nframes, size_t hop, const float *window, size_t navg, float scaling, int what, float *out,
+                               size_t out_stride, void *stream);
+int pffftd_hip_frames_csd_batch(PFFFTD_Setup *, const double *x, size_t x_stride, const double *y, size_t y_stride, size_t nsignals,
+                                size_t nframes, size_t hop, const double *window, size_t navg, double scaling, int what, double *out,
+                                size_t out_stride, void *stream);
+/* The route pffft_hip_frames_csd_batch takes for these arguments under the calling thread's selector (pffft_hip_set_variant: 142 = always
+ * composed, 143 = fused wherever it is legal): "fused" or "composed"; "" for an invalid handle, hop == 0 or an unknown `what`.  Pointer
+ * alignment is checked at the call: the query assumes 16-byte aligned pointers.  x_stride = y_stride = 0: one signal; navg = 0: every frame
+ * of a signal.  Host arithmetic only; PFFFT_Setup and PFFFTD_Setup handles. */
+const char *pffft_hip_frames_csd_route(const void *setup, size_t hop, size_t x_stride, size_t y_stride, size_t navg, int what);
+
 /* Polyphase filter-bank analysis (weighted overlap-add channelizer): the framing of pffft_hip_frames_transform_batch with a prototype
  * filter of taps*N real coefficients that is folded onto N points before the transform.  For frame f of signal i
  *     u_f[j] = sum over p = 0 ... taps-1 of  prototype[p*N + j] * x_i[f*hop + p*N + j],   j < N

@@ -83,6 +83,9 @@ def lib():
         g("hip_frames_psd_batch").restype = C.c_int
         g("hip_frames_psd_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p,
                                               C.c_size_t, ct, C.c_void_p, C.c_size_t, C.c_void_p]
+        g("hip_frames_csd_batch").restype = C.c_int
+        g("hip_frames_csd_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
+                                              C.c_void_p, C.c_size_t, ct, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
         g("hip_pfb_transform_batch").restype = C.c_int
         g("hip_pfb_transform_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
                                                  C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
@@ -137,6 +140,8 @@ def lib():
     L.pffft_hip_frames_route.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int]
     L.pffft_hip_frames_psd_route.restype = C.c_char_p
     L.pffft_hip_frames_psd_route.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t]
+    L.pffft_hip_frames_csd_route.restype = C.c_char_p
+    L.pffft_hip_frames_csd_route.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int]
     L.pffft_hip_pfb_route.restype = C.c_char_p
     L.pffft_hip_pfb_route.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int]
     L.pffft_hip_any_conv_size.restype = C.c_int; L.pffft_hip_any_conv_size.argtypes = [C.c_void_p]
@@ -269,6 +274,15 @@ def frames_psd_route(setup: "Setup", hop, signal_stride=0, navg=0) -> str:
     """pffft_hip_frames_psd_route: "fused" / "composed" for an averaged-power call with 16-byte aligned pointers, under the calling
     thread's selector.  Host arithmetic only."""
     return lib().pffft_hip_frames_psd_route(setup.handle, int(hop), int(signal_stride), int(navg)).decode()
+
+
+CSD_WHAT = {"cross": 0, "all": 1, "coherence": 2}   # PFFFT_HIP_CSD_* of include/pffft_hip.h
+
+
+def frames_csd_route(setup: "Setup", hop, x_stride=0, y_stride=0, navg=0, what="cross") -> str:
+    """pffft_hip_frames_csd_route: "fused" / "composed" for an averaged cross-spectrum call with 16-byte aligned pointers, under the
+    calling thread's selector.  Host arithmetic only."""
+    return lib().pffft_hip_frames_csd_route(setup.handle, int(hop), int(x_stride), int(y_stride), int(navg), CSD_WHAT[what]).decode()
 
 
 PFB_FUSED_MAX_TAPS = 16   # PFFFT_HIP_PFB_FUSED_MAX_TAPS of include/pffft_hip.h
@@ -543,6 +557,27 @@ class Setup(_Handle):
         _check(self._fn("hip_frames_psd_batch")(self.handle, signal.data_ptr(), sstride, nsig, nframes, hop,
                                                 self._window_ptr(window, signal), int(navg), float(scaling), out.data_ptr(), pitch,
                                                 self._stream()), "hip_frames_psd_batch")
+        return out
+
+    def frames_csd_row(self, what="cross") -> int:
+        """Scalars per output row of frames_csd_batch: 2P (re, im interleaved), 4P (Pxx | Pyy | Pxy) or P."""
+        return {"cross": 2, "all": 4, "coherence": 1}[what] * self.frames_out_row("power")
+
+    def frames_csd_batch(self, x, y, hop, nframes=None, window=None, navg=0, scaling=1.0, what="cross", out=None):
+        """pffft_hip_frames_csd_batch: conj(X) Y of the frames of x and y (tensors of one shape; their row strides may differ), averaged
+        over groups of `navg` consecutive frames (0 = every frame of a signal: Welch) in the documented order.  what = "cross": the
+        cross-spectrum times `scaling`, (re, im) interleaved; "all": Pxx | Pyy | Pxy, each times `scaling`; "coherence": |Sxy|^2 / (Sxx Syy).
+        Returns [nsignals,] nframes / navg, frames_csd_row(what)]; `out` may have padded rows (its stride(-2) is the row pitch)."""
+        nsig, xstride, nframes = self._analysis_in(x, hop, nframes, self.N)
+        ysig, ystride, _ = self._analysis_in(y, hop, nframes, self.N)
+        assert ysig == nsig and y.dim() == x.dim() and y.dtype == x.dtype, "x and y hold the same number of signals"
+        per = navg if navg else nframes
+        assert nframes == 0 or nframes % per == 0, "nframes must be a multiple of navg"
+        groups = nframes // per if nframes else 0
+        out, pitch = self._rows_out(out, x, nsig, groups, self.frames_csd_row(what), "row v = i groups + g")
+        _check(self._fn("hip_frames_csd_batch")(self.handle, x.data_ptr(), xstride, y.data_ptr(), ystride, nsig, nframes, hop,
+                                                self._window_ptr(window, x), int(navg), float(scaling), CSD_WHAT[what], out.data_ptr(),
+                                                pitch, self._stream()), "hip_frames_csd_batch")
         return out
 
     def pfb_transform_batch(self, signal, hop, prototype, nframes=None, out=None, output="internal"):

@@ -109,6 +109,13 @@ template <typename V> __device__ __forceinline__ V mdct_mul(V a, V w) {
     const T yy = a.y * w.y;
     return mk<T>(fma_(a.x, w.x, -yy), fma_(a.x, w.y, a.y * w.x));
 }
+// Magnitude-squared coherence from the UNSCALED group sums of pffft_hip_frames_csd_batch (fft_csd.h), the ONE place it is written:
+// |Sxy|^2 / (Sxx Syy) with both squares, the sum, the product of the denominators and the IEEE division rounded once each; 0 / 0 = NaN.
+// The run's own store (averages of one run) and the reduction (longer ones) of every route call it; the two real-only bins of a real
+// setup pass sim = +0.
+template <typename T> __device__ __forceinline__ T coherence_ratio(T sre, T sim, T sxx, T syy) {
+    return (sre * sre + sim * sim) / (sxx * syy);
+}
 // the same for a COMPILE-TIME constant w (the fixed twiddles inside radix 16 / 32 / 9 / 25 / 27): the scalar form lets the
 // compiler keep the constants in scalar registers / literals; an asm operand would pin each one in a VGPR pair.  Same
 // operations as cmul / cmulc.
