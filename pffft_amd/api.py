@@ -545,14 +545,19 @@ class Setup(_Handle):
                                                       self._stream()), "hip_frames_transform_batch")
         return out
 
+    @staticmethod
+    def _groups(nframes, navg):
+        """Groups of `navg` consecutive frames (0 = every frame of a signal) in `nframes` frames of a signal."""
+        per = navg if navg else nframes
+        assert nframes == 0 or nframes % per == 0, "nframes must be a multiple of navg"
+        return nframes // per if nframes else 0
+
     def frames_psd_batch(self, signal, hop, nframes=None, window=None, navg=0, scaling=1.0, out=None):
         """pffft_hip_frames_psd_batch: |X|^2 of the frames of frames_transform_batch, averaged over groups of `navg` consecutive frames
         (0 = every frame of a signal: Welch) in the documented order and multiplied once by `scaling`.  Returns [nsignals,] nframes / navg,
         P]; `out` may have padded rows (its stride(-2) is the row pitch)."""
         nsig, sstride, nframes = self._analysis_in(signal, hop, nframes, self.N)
-        per = navg if navg else nframes
-        assert nframes == 0 or nframes % per == 0, "nframes must be a multiple of navg"
-        groups = nframes // per if nframes else 0
+        groups = self._groups(nframes, navg)
         out, pitch = self._rows_out(out, signal, nsig, groups, self.frames_out_row("power"), "row v = i groups + g")
         _check(self._fn("hip_frames_psd_batch")(self.handle, signal.data_ptr(), sstride, nsig, nframes, hop,
                                                 self._window_ptr(window, signal), int(navg), float(scaling), out.data_ptr(), pitch,
@@ -571,9 +576,7 @@ class Setup(_Handle):
         nsig, xstride, nframes = self._analysis_in(x, hop, nframes, self.N)
         ysig, ystride, _ = self._analysis_in(y, hop, nframes, self.N)
         assert ysig == nsig and y.dim() == x.dim() and y.dtype == x.dtype, "x and y hold the same number of signals"
-        per = navg if navg else nframes
-        assert nframes == 0 or nframes % per == 0, "nframes must be a multiple of navg"
-        groups = nframes // per if nframes else 0
+        groups = self._groups(nframes, navg)
         out, pitch = self._rows_out(out, x, nsig, groups, self.frames_csd_row(what), "row v = i groups + g")
         _check(self._fn("hip_frames_csd_batch")(self.handle, x.data_ptr(), xstride, y.data_ptr(), ystride, nsig, nframes, hop,
                                                 self._window_ptr(window, x), int(navg), float(scaling), CSD_WHAT[what], out.data_ptr(),

@@ -150,8 +150,8 @@ PF_EXPORT int pffftd_hip_frames_overlap_add_batch(PFFFTD_Setup* s, const double*
 }
 
 PF_EXPORT const char* pffft_hip_frames_route(const void* setup, size_t hop, size_t signal_stride, size_t out_stride, int output) {
-    const pf::Setup* s = static_cast<const pf::Setup*>(setup);
-    if (!s || s->magic != pf::MAGIC || hop == 0 || output < 0 || output > 2) return "";
+    const pf::Setup* s = pf::route_setup(setup, hop);
+    if (!s || output < 0 || output > 2) return "";
     if (out_stride == 0) out_stride = pf::frame_dims(s, output).out_row;
     return pf::frames_route_fused(s, hop, signal_stride, out_stride, output, pf::ab()) ? "fused" : "composed";
 }

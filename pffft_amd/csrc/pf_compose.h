@@ -1,8 +1,8 @@
-// The one host path of the entries that are COMPOSED on top of pf::Setup (frames_tu.hip, psd_tu.hip, pfb_tu.hip, any_tu.hip,
-// zoom_tu.hip, dct_tu.hip): how much scratch one launch sequence may hold, how a batch walks through it, how a fused launch is cut into
-// slices, the frame-matrix routes of analysis and synthesis, the lookup of the register-tiled configuration a fused kernel must share
-// with transform_batch, and the handle that owns an inner setup.  Every decision is written here once; each unit keeps its validation
-// texts, its route decision and its own typed kernel launches.  Every function is internal to the unit that includes it.
+// The one host path of the entries that are COMPOSED on top of pf::Setup (frames_tu.hip, psd_tu.hip, csd_tu.hip, pfb_tu.hip, any_tu.hip,
+// zoom_tu.hip, dct_tu.hip, mdct_tu.hip): how much scratch one launch sequence may hold, how a batch walks through it, how a fused launch is
+// cut into slices, the frame-matrix routes of analysis and synthesis, the run walk of the averages, the lookup of the register-tiled
+// configuration a fused kernel must share with transform_batch, and the handle that owns an inner setup.  Every decision is written here once;
+// each unit keeps its validation texts, its route decision and its own typed kernel launches.  Every function is internal to its includer.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -67,6 +67,43 @@ static_assert(synth_plan(20000, 16384, 3, 0).run == 16381 && synth_plan(20000, 1
 static_assert(synth_plan(20000, 16384, 15, 15).run == 16369 && synth_plan(20000, 16384, 15, 15).buffer_rows == 16384, "... and taps 4");
 static_assert(synth_plan(100, 2, 5, 0).run == 1 && synth_plan(100, 2, 5, 0).buffer_rows == 6, "cap <= reach, frames: one new frame per run");
 static_assert(synth_plan(100, 2, 5, 5).run == 5 && synth_plan(100, 2, 5, 5).buffer_rows == 10, "cap <= reach, filter bank: 2 reach rows");
+
+// The Welch averages (psd, csd) sum runs of AVG_RUN frames; a group of `navg` frames is rpg runs.  An average of one run is scaled and stored
+// by the run itself.  Longer ones go through the partial buffer in whole groups: `vstep` of the V output rows per pass (a fused kernel counts
+// the runs of a launch in 32 bits), then the reduction of those rows.  Composed, the frames of `crun` whole runs (of up to `lfull` frames) go
+// through the frame matrix per chunk; frame_bytes: one frame row times the frame sets (csd: x and y, the cap holds for both together).
+constexpr size_t AVG_RUN = PFFFT_HIP_PSD_RUN;   // (pf::PSD_RUN of fft_psd.h: psd_tu.hip and csd_tu.hip assert it)
+struct AvgPlan { size_t V, navg; bool fused; size_t rpg, vstep, lfull, crun, part_rows, set_rows; };
+constexpr AvgPlan avg_plan(size_t V, size_t navg, size_t part_row_bytes, size_t frame_bytes, bool fused) {
+    AvgPlan p{V, navg, fused, (navg + AVG_RUN - 1) / AVG_RUN, V, std::min(navg, AVG_RUN), 0, 0, 0};
+    if (p.rpg > 1) p.vstep = cap_rows(p.rpg * part_row_bytes);
+    if (fused) p.vstep = std::min(p.vstep, std::max<size_t>(1, ROW_SLICE / p.rpg));
+    p.vstep = std::min(p.vstep, V);
+    p.crun = std::max<size_t>(1, cap_rows(frame_bytes) / p.lfull);
+    p.part_rows = p.vstep * p.rpg;                                                   // rows of the partial buffer (taken where rpg > 1)
+    p.set_rows = std::min(V * navg, std::min(p.crun, p.vstep * p.rpg) * p.lfull);    // rows of one set of the frame matrix (composed)
+    return p;
+}
+// first frame of run r, in the numbering v = i nframes + f
+constexpr size_t first_frame(size_t r, size_t navg, size_t rpg) { return (r / rpg) * navg + (r % rpg) * AVG_RUN; }
+constexpr bool avg_is(const AvgPlan& p, size_t rpg, size_t vstep, size_t lfull, size_t crun, size_t part_rows, size_t set_rows) {
+    return p.rpg == rpg && p.vstep == vstep && p.lfull == lfull && p.crun == crun && p.part_rows == part_rows && p.set_rows == set_rows;
+}
+// real float N = 4096: partial rows of P = 2049 (psd) or 2P (csd cross) scalars, frame rows of 4096 scalars in one set (psd) or two (csd)
+static_assert(avg_is(avg_plan(7, 16, 8196, 16384, false), 1, 7, 16, 1024, 7, 112), "an average of one run; V smaller than vstep");
+static_assert(avg_is(avg_plan(10, 32, 8196, 16384, false), 1, 10, 32, 512, 10, 320), "navg = 32: still one run");
+static_assert(avg_is(avg_plan(10, 33, 8196, 16384, false), 2, 10, 32, 512, 20, 330), "navg = 33: two runs, the partial buffer");
+static_assert(avg_is(avg_plan(10000, 100, 8196, 16384, false), 4, 8188, 32, 512, 32752, 16384), "psd, navg = 100: 8188 groups per pass");
+static_assert(avg_is(avg_plan(10000, 100, 16392, 32768, false), 4, 4094, 32, 256, 16376, 8192), "csd cross, navg = 100: two sets");
+static_assert(avg_is(avg_plan(100, 100, 16392, 32768, false), 4, 100, 32, 256, 400, 8192), "... 10 000 frames: 8192 rows per half");
+static_assert(avg_plan(16377, 33, 8196, 16384, false).vstep == 16376 && avg_plan(8189, 33, 16392, 32768, false).vstep == 8188, "one group more: a second pass");
+static_assert(avg_plan(5, 64, (size_t)1 << 26, 16384, false).vstep == 2 && avg_plan(5, 64, ((size_t)1 << 26) + 1, 16384, false).vstep == 1 &&
+              avg_plan(5, 1, 8196, (size_t)1 << 27, false).crun == 2 && avg_plan(5, 1, 8196, ((size_t)1 << 27) + 1, false).crun == 1,
+              "both sides of an exact division of the cap: by the partial rows of a group, by the frame rows");
+static_assert(avg_is(avg_plan(5, 100, 8196, SCRATCH_CAP_BYTES + 1, false), 4, 5, 32, 1, 20, 32), "a row longer than the cap: one run per chunk");
+static_assert(avg_plan(ROW_SLICE + 1, 16, 8196, 16384, true).vstep == ROW_SLICE && avg_plan(ROW_SLICE + 1, 16, 8196, 16384, false).vstep == ROW_SLICE + 1 &&
+              avg_plan(10, (size_t)1 << 37, 4, 16384, true).vstep == 1, "a fused launch holds at most ROW_SLICE runs, and at least one group");
+static_assert(first_frame(3, 100, 4) == 96 && first_frame(4, 100, 4) == 100 && first_frame(7, 100, 4) == 196 && first_frame(5, 16, 1) == 80, "a group of 100: runs of 32, 32, 32, 4");
 
 // ------------------------------------------------------------------------------------------------ shared launches
 inline int bad_in(const char* prefix, const char* what, hipError_t e = hipErrorInvalidValue) {
@@ -215,6 +252,63 @@ static int synthesis_runs(Setup* s, const T* spectra, size_t spectra_stride, siz
             if ((rc = gather((const T*)buf, f0, 0, fb, signal + i * signal_stride, 0, 1, fa * hop, fb == nframes ? samples : fb * hop))) return rc;
         }
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ averages (psd, csd)
+// The run walk of avg_plan.  Takes the partial buffer of `st` (Setup::psd, where rpg > 1) and then the frame matrix (Setup::frames, where
+// composed), always in this order, and hands the runs of each pass to fused(dst, dstride, first output row, runs, scale) or, in chunks, to
+// composed(X, first run, runs, first frame, frames, dst, dstride, scale): a run stores into `out` with the scaling (rpg == 1) or into its
+// partial row, which reduce(part, rows, out rows) sums after the pass.  The callables enqueue on `st`; the first two return 0 or an error.
+// part_row, frame_row: the scalars behind the plan's two byte counts (a partial row; a frame row times the frame sets).
+template <typename T, class Fused, class Composed, class Reduce>
+static int averaged_runs(Setup* s, hipStream_t st, const AvgPlan& p, size_t part_row, size_t frame_row, T* out, size_t out_stride, T scaling,
+                         Fused&& fused, Composed&& composed, Reduce&& reduce) {
+    const size_t rpg = p.rpg;
+    std::unique_lock<std::mutex> lkp(s->psd.mu, std::defer_lock), lkf(s->frames.mu, std::defer_lock);
+    void *part = nullptr, *X = nullptr;
+    if (rpg > 1) {
+        lkp.lock();
+        if (int rc = scratch_buffer(s->psd, st, p.part_rows * part_row * sizeof(T), "the partial buffer", &part)) return rc;
+    }
+    if (!p.fused) {
+        lkf.lock();
+        if (int rc = scratch_buffer(s->frames, st, p.set_rows * frame_row * sizeof(T), "the frame matrix", &X)) return rc;
+    }
+    for (size_t v0 = 0; v0 < p.V; v0 += p.vstep) {
+        const size_t rows = std::min(p.V - v0, p.vstep), ra = v0 * rpg, rb = (v0 + rows) * rpg;
+        T* dst = rpg == 1 ? out + v0 * out_stride : (T*)part;
+        const size_t dstride = rpg == 1 ? out_stride : part_row;
+        const T scale = rpg == 1 ? scaling : (T)1;
+        if (p.fused) {
+            if (int rc = fused(dst, dstride, v0, rb - ra, scale)) return rc;
+        } else {
+            for (size_t r = ra; r < rb; r += p.crun) {
+                const size_t cnt = std::min(rb - r, p.crun), fa = first_frame(r, p.navg, rpg), nfr = first_frame(r + cnt, p.navg, rpg) - fa;
+                if (int rc = composed((T*)X, r, cnt, fa, nfr, dst + (r - ra) * dstride, dstride, scale)) return rc;
+                PF_CHECK(hipGetLastError());
+            }
+        }
+        if (rpg > 1) {
+            reduce((T*)part, rows, out + v0 * out_stride);
+            PF_CHECK(hipGetLastError());
+        }
+    }
+    return 0;
+}
+
+// What the fused routes of both entries ask of a call whose pointers are 16-byte aligned: the entry's selector pair and test of the setup,
+// 16-byte loads of every frame (hop, strides: multiples of 4 scalars), an average's frames counted in 32 bits, fused under no selector.
+template <class Fusable>
+static bool averaged_route_fused(const AbSel& sel, AbValue composed, AbValue fused, Fusable&& fusable, size_t hop, size_t stride_a, size_t stride_b,
+                                 size_t navg, bool by_default) {
+    if (sel.is(composed) || !fusable() || hop % 4 || stride_a % 4 || stride_b % 4 || navg > 0xffffffffull) return false;
+    return sel.is(fused) || by_default;
+}
+
+// the setup a `*_route` export answers for; NULL: it answers ""
+inline const Setup* route_setup(const void* setup, size_t hop) {
+    const Setup* s = static_cast<const Setup*>(setup);
+    return s && s->magic == MAGIC && hop != 0 ? s : nullptr;
 }
 
 // ------------------------------------------------------------------------------------------------ the framed register-tiled configuration

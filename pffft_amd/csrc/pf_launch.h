@@ -74,5 +74,10 @@ template <class F>
 static int with_flag(bool on, F&& f) {
     return on ? f(std::integral_constant<int, 1>{}) : f(std::integral_constant<int, 0>{});
 }
+// the three-way sibling: a run-time value out of {A, B, C} as a template argument (the caller has refused every other value)
+template <int A, int B, int C, class F>
+static auto with_one_of(int v, F&& f) {
+    return v == A ? f(std::integral_constant<int, A>{}) : v == B ? f(std::integral_constant<int, B>{}) : f(std::integral_constant<int, C>{});
+}
 
 }  // namespace pf

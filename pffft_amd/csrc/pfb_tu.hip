@@ -177,8 +177,8 @@ PF_EXPORT int pffftd_hip_pfb_transform_batch(PFFFTD_Setup* s, const double* sign
 }
 
 PF_EXPORT const char* pffft_hip_pfb_route(const void* setup, size_t hop, size_t taps, size_t signal_stride, size_t out_stride, int output) {
-    const pf::Setup* s = static_cast<const pf::Setup*>(setup);
-    if (!s || s->magic != pf::MAGIC || hop == 0 || taps == 0 || output < 0 || output > 2) return "";
+    const pf::Setup* s = pf::route_setup(setup, hop);
+    if (!s || taps == 0 || output < 0 || output > 2) return "";
     if (out_stride == 0) out_stride = pf::frame_dims(s, output).out_row;
     return pf::pfb_route_fused(s, hop, taps, signal_stride, out_stride, output, pf::ab()) ? "fused" : "composed";
 }

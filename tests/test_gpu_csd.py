@@ -361,6 +361,46 @@ def test_fused_loops_bit_for_bit(N, navg):
     s.close()
 
 
+def test_composed_second_pass_of_the_partial_buffer_bit_for_bit():
+    """The smallest shape at which the composed route walks the partial buffer twice (the fused route: test_fused_loops_bit_for_bit): real
+    float N = 4096, cross, navg = 33 (two runs per group, 2 x 2P scalars of partials), hop = 4.  floor(256 MiB / (2 csd_part_row 4 B)) = 8188
+    groups fill the buffer, so 8189 groups are two passes: 64 chunks of 256 runs through the two halves of the frame matrix and a reduction,
+    then one chunk of the last two runs and a second reduction (read from the trace).  The call must equal calls of 256 groups bit for bit,
+    64 sampled groups plus the first and the last must equal the model over the existing entry's ordered rows, and the sentinel rows around
+    the output must be intact."""
+    N, navg, hop, rpg = 4096, 33, 4, 2
+    R = N + 2                                                                    # csd_part_row(cross) = the output row: 2P scalars
+    vstep = (256 << 20) // (rpg * R * 4)
+    crun = (256 << 20) // (2 * N * 4) // pm.RUN
+    groups = vstep + 1
+    assert (vstep, crun, groups) == (8188, 256, 8189)
+    nframes = groups * navg
+    s = pa.Setup(N, pa.REAL)
+    x, y = make_pair(1, (nframes - 1) * hop + N, (0, 0), np.float32, N + navg + 1)
+    w_t = torch.from_numpy(fm.hann(N, np.float32)).cuda()
+    pa.set_variant(AB_CSD_COMPOSED)
+    try:
+        ref = torch.empty((groups, R), device="cuda", dtype=torch.float32)
+        for g0 in range(0, groups, 256):
+            n = min(256, groups - g0)
+            s.frames_csd_batch(x[g0 * navg * hop:], y[g0 * navg * hop:], hop, n * navg, w_t, navg, SCALING, "cross", ref[g0:g0 + n])
+        full, out = guarded(groups, R, torch.float32)
+        _, names = kernels_run(lambda: s.frames_csd_batch(x, y, hop, nframes, w_t, navg, SCALING, "cross", out), short=True)
+        assert names.count("psd_reduce_kernel") == 2 and names.count("csd_runs_kernel") == math.ceil(vstep * rpg / crun) + 1, \
+            (names.count("psd_reduce_kernel"), names.count("csd_runs_kernel"))
+        assert_guards(full, groups, R, (N, navg))
+        assert_same_bits(out, ref, (N, navg, "two passes against calls of 256 groups"))
+        rng = np.random.default_rng(N + navg)
+        pick = sorted(set([0, groups - 1]) | set(int(v) for v in rng.integers(0, groups, 64)))
+        X = np.concatenate([ordered_rows(s, x[g * navg * hop:], hop, navg, w_t) for g in pick])
+        Y = np.concatenate([ordered_rows(s, y[g * navg * hop:], hop, navg, w_t) for g in pick])
+        want = torch.from_numpy(cm.rows(X, Y, True, "cross", navg, SCALING, np.float32)).cuda()
+        assert_same_bits(out[torch.tensor(pick, device="cuda")], want, (N, navg, "sampled groups against the model"))
+    finally:
+        pa.set_variant(0)
+    s.close()
+
+
 # ------------------------------------------------------------------ graph capture and chunking
 def test_graph_replay_and_the_scratch_rule():
     """A captured replay after one warm call reproduces the bits (the inputs changed between the replays); a call that would have to grow

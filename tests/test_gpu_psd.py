@@ -252,6 +252,46 @@ def test_fused_loops_bit_for_bit(N, navg):
     s.close()
 
 
+def test_second_pass_of_the_partial_buffer_bit_for_bit():
+    """The smallest shape at which the partial buffer is walked twice: real float N = 4096, navg = 33 (two runs per group, 2 P scalars of
+    partials), hop = 4.  floor(256 MiB / (2 P 4 B)) = 16376 groups fill the buffer, so 16377 groups are two passes - on the composed route
+    also 64 chunks of 512 runs through the frame matrix in the first pass and one chunk of the last two runs in the second (read from the
+    trace), on the fused route two launches.  Either call must equal composed calls of 256 groups bit for bit, 64 sampled groups plus the
+    first and the last must equal the model over the existing entry's power rows, and the sentinel rows around the output must be intact."""
+    N, navg, hop, rpg = 4096, 33, 4, 2
+    P = N // 2 + 1
+    vstep = (256 << 20) // (rpg * P * 4)
+    crun = (256 << 20) // (N * 4) // pm.RUN
+    groups = vstep + 1
+    assert (vstep, crun, groups) == (16376, 512, 16377)
+    nframes = groups * navg
+    s = pa.Setup(N, pa.REAL)
+    sig = make_signal(1, (nframes - 1) * hop + N, 0, np.float32, N + navg + 1)
+    w_t = torch.from_numpy(fm.hann(N, np.float32)).cuda()
+    try:
+        ref = torch.empty((groups, P), device="cuda", dtype=torch.float32)
+        pa.set_variant(AB_PSD_COMPOSED)
+        for g0 in range(0, groups, 256):
+            n = min(256, groups - g0)
+            s.frames_psd_batch(sig[g0 * navg * hop:], hop, n * navg, w_t, navg, SCALING, ref[g0:g0 + n])
+        for sel, runs in ((AB_PSD_COMPOSED, "psd_runs_kernel"), (AB_PSD_FUSED, "fft_psd_kernel")):
+            pa.set_variant(sel)
+            full, out = guarded(groups, P, torch.float32)
+            _, names = kernels_run(lambda: s.frames_psd_batch(sig, hop, nframes, w_t, navg, SCALING, out), short=True)
+            assert names.count("psd_reduce_kernel") == 2, (sel, names.count("psd_reduce_kernel"))
+            assert names.count(runs) == (math.ceil(vstep * rpg / crun) + 1 if sel == AB_PSD_COMPOSED else 2), (sel, names.count(runs))
+            assert_guards(full, groups, P, (N, navg, sel))
+            assert_same_bits(out, ref, (N, navg, sel, "two passes against calls of 256 groups"))
+        rng = np.random.default_rng(N + navg)
+        pick = sorted(set([0, groups - 1]) | set(int(v) for v in rng.integers(0, groups, 64)))
+        p = torch.cat([power_rows(s, sig[g * navg * hop:], hop, navg, w_t) for g in pick]).cpu().numpy()
+        want = torch.from_numpy(pm.average(p, navg, pm.RUN, SCALING, np.float32)).cuda()
+        assert_same_bits(out[torch.tensor(pick, device="cuda")], want, (N, navg, "sampled groups of the fused call against the model"))
+    finally:
+        pa.set_variant(0)
+    s.close()
+
+
 # ------------------------------------------------------------------ graph capture and chunking
 def test_graph_replay_and_the_scratch_rule():
     """A captured replay after one warm call reproduces the bits (the input changed between the replays); a call that would have to grow
