@@ -634,6 +634,63 @@ int pffftd_hip_mdct_overlap_add_batch(PFFFTD_HIP_MdctSetup *, const double *coef
 const char *pffft_hip_mdct_route(const void *setup, int what);
 int pffft_hip_mdct_table(const void *setup, int which, size_t first, size_t count, void *host_out);
 
+/* ANALYTIC SIGNALS of real rows (scipy.signal.hilbert): the step between real samples from a converter and the complex rows the mixers
+ * and the channelizer work on.  With X = DFT(x) (forward, exp(-2 pi j n k / N)):
+ *     Z[k] = c_k gain[k] X[k], 0 <= k <= N/2, c_0 = c_{N/2} = 1, c_k = 2 otherwise;   Z[k] = 0 above N/2;   z = IDFT(Z) / N
+ * gain == NULL is all ones - exactly scipy.signal.hilbert.  A gain (N/2 + 1 host values, copied at setup) makes the call a one-sided
+ * band-pass and an analytic signal in the same pass: the real -> IQ channel extraction in front of the mixers.
+ *   in   batch dense rows of N reals
+ *   out  PFFFT_HIP_ANALYTIC: batch dense rows of N interleaved complex values z;  PFFFT_HIP_HILBERT: rows of N reals Im z (the Hilbert
+ *        transform of x);  PFFFT_HIP_ENVELOPE: rows of N reals |z|
+ * Legal N: every N pffft[d]_new_setup(N, PFFFT_COMPLEX) takes; NULL for any other N.  Creating a setup touches no device; the handle
+ * owns a complex setup of N.  The filter spectrum H[k] = c_k gain[k] is formed in double (exact for float gains), rounded once to the
+ * setup's type and permuted into the inner setup's internal layout (exact); no transform is involved, because the spectrum is given.
+ * The 1 / N rides on the convolution's scaling.  The envelope is ONE device function on every route: sqrt(fma(re, re, im im)) with the
+ * correctly rounded square root and no scaling tricks - it overflows to +inf where re^2 + im^2 does and loses bits where that sum is
+ * subnormal.
+ * in / out are device pointers, 8-byte aligned on a real side and 16-byte aligned on the complex side.  out == in IS LEGAL for HILBERT
+ * and ENVELOPE (any other overlap is refused); for ANALYTIC any overlap of in and out is refused.  The call is asynchronous on `stream`;
+ * 0, else a hipError_t with its text in pffft_hip_last_error().  Validation happens before any device is touched: a NULL or foreign
+ * handle or the other precision's (hipErrorInvalidHandle), another `what`, NULL, misaligned or overlapping in / out
+ * (hipErrorInvalidValue) -> nothing launched.
+ * Routes (pffft_hip_analytic_route names the one a call takes under the calling thread's selector):
+ *   "fused"     float, N = 512 / 1024 / 2048 / 4096: ONE kernel - the fused convolution kernel of pffft_hip_convolve_batch with a loader
+ *               that takes N reals (an exact zero as imaginary part) and a store that writes z, Im z or |z|: 12 N bytes per row for
+ *               ANALYTIC and 8 N for the real outputs, where widening, convolve_batch and .imag / .abs() move 28 N and about 40 N.
+ *               Which (N, what) cells run it by default is a measured table; pffft_hip_set_variant(145) runs it
+ *               wherever it is legal, 144 never.
+ *   "composed"  every setup.  ANALYTIC: a widening kernel writes (x, 0) straight into out, pffft[d]_hip_convolve_batch with the one
+ *               broadcast H runs in place there - no scratch of this handle, so the call is legal on a capturing stream once the
+ *               tables exist (the inner convolve_batch keeps its own rules).  HILBERT / ENVELOPE: the widening kernel into a per-stream
+ *               scratch image of batch x N complex values, convolve_batch in place there, a narrowing kernel into out.  The image holds
+ *               at most 256 MiB (longer batches go through it in chunks on the stream); a call that would have to grow it on a capturing
+ *               stream returns hipErrorStreamCaptureUnsupported before any launch.
+ * In the four fused cells convolve_batch itself runs the fused convolution kernel on the same configuration, H and scaling, and the
+ * loader's zero is exact: THE ROUTES AGREE BIT FOR BIT in all three outputs.
+ * THE FIRST CALL ON A SETUP BUILDS ITS TABLES: it allocates and synchronises the device, so it must happen BEFORE a stream capture (during
+ * one it fails with hipErrorStreamCaptureUnsupported and launches nothing).  batch == 0 builds the tables, launches nothing else and
+ * returns 0.  A setup serves ONE device, the one that is current at the first call (hipErrorInvalidDevice from another); any number of
+ * streams and threads of that device may share it.
+ * Two real rows per complex transform, a fused double kernel, strided rows, a down-mix fused into the store and the instantaneous phase
+ * are not offered. */
+typedef enum { PFFFT_HIP_ANALYTIC, PFFFT_HIP_HILBERT, PFFFT_HIP_ENVELOPE } pffft_hip_analytic_what_t;
+typedef struct PFFFT_HIP_AnalyticSetup PFFFT_HIP_AnalyticSetup;
+typedef struct PFFFTD_HIP_AnalyticSetup PFFFTD_HIP_AnalyticSetup;
+PFFFT_HIP_AnalyticSetup *pffft_hip_analytic_new_setup(int N, const float *gain);     /* gain: NULL or N/2 + 1 host values */
+PFFFTD_HIP_AnalyticSetup *pffftd_hip_analytic_new_setup(int N, const double *gain);
+void pffft_hip_analytic_destroy_setup(PFFFT_HIP_AnalyticSetup *);     /* NULL-safe */
+void pffftd_hip_analytic_destroy_setup(PFFFTD_HIP_AnalyticSetup *);
+int pffft_hip_analytic_transform_batch(PFFFT_HIP_AnalyticSetup *, const float *in, float *out, size_t batch,
+                                       pffft_hip_analytic_what_t what, void *stream);
+int pffftd_hip_analytic_transform_batch(PFFFTD_HIP_AnalyticSetup *, const double *in, double *out, size_t batch,
+                                        pffft_hip_analytic_what_t what, void *stream);
+/* Host arithmetic only, handles of both precisions.  pffft_hip_analytic_route: "fused" / "composed" for `what` under the calling
+ * thread's selector; "" for an invalid handle or another `what`.  pffft_hip_analytic_table: `count` values H[k] from k = `first` in
+ * canonical order (N real scalars of the setup's type in all: c_k gain[k] up to N/2, zeros above) into host_out - the values the
+ * device's spectrum holds.  0; non-zero for an invalid handle, a range beyond N values or a NULL host_out. */
+const char *pffft_hip_analytic_route(const void *setup, int what);
+int pffft_hip_analytic_table(const void *setup, size_t first, size_t count, void *host_out);
+
 /* Overlap-save FIR on device-resident signal/output (same block schedule as pffastconv_apply,
  * src/pffastconv.c:204-261): returns the number of output samples written, or -1 on error. */
 int pffastconv_hip_apply_device(PFFASTCONV_Setup *, const float *d_input, int inputLen, float *d_output,

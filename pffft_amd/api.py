@@ -118,6 +118,10 @@ def lib():
         g("hip_mdct_overlap_add_batch").restype = C.c_int
         g("hip_mdct_overlap_add_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, ct, C.c_void_p,
                                                     C.c_size_t, C.c_void_p]
+        g("hip_analytic_new_setup").restype = C.c_void_p; g("hip_analytic_new_setup").argtypes = [C.c_int, C.c_void_p]
+        g("hip_analytic_destroy_setup").restype = None; g("hip_analytic_destroy_setup").argtypes = [C.c_void_p]
+        g("hip_analytic_transform_batch").restype = C.c_int
+        g("hip_analytic_transform_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
         getattr(L, f"validate_{pfx}_simd").restype = C.c_int
         getattr(L, f"validate_{pfx}_simd_ex").restype = C.c_int
         getattr(L, f"validate_{pfx}_simd_ex").argtypes = [C.c_void_p]
@@ -159,6 +163,9 @@ def lib():
     L.pffft_hip_mdct_route.restype = C.c_char_p; L.pffft_hip_mdct_route.argtypes = [C.c_void_p, C.c_int]
     L.pffft_hip_mdct_table.restype = C.c_int
     L.pffft_hip_mdct_table.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p]
+    L.pffft_hip_analytic_route.restype = C.c_char_p; L.pffft_hip_analytic_route.argtypes = [C.c_void_p, C.c_int]
+    L.pffft_hip_analytic_table.restype = C.c_int
+    L.pffft_hip_analytic_table.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
     L.pffft_hip_kernel_name.restype = C.c_char_p; L.pffft_hip_kernel_name.argtypes = [C.c_void_p]
     L.pffft_hip_describe.restype = C.c_int; L.pffft_hip_describe.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.pffft_hip_route_occupancy.restype = C.c_int; L.pffft_hip_route_occupancy.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -304,6 +311,15 @@ def any_route(setup) -> str:
 def zoom_route(setup) -> str:
     """pffft_hip_zoom_route: "fused" / "composed" for a ZoomSetup under the calling thread's selector.  Host arithmetic only."""
     return lib().pffft_hip_zoom_route(setup.handle).decode()
+
+
+ANALYTIC_WHAT = {"analytic": 0, "hilbert": 1, "envelope": 2}   # pffft_hip_analytic_what_t
+
+
+def analytic_route(setup, what="analytic") -> str:
+    """pffft_hip_analytic_route: "fused" / "composed" for an AnalyticSetup and one of its outputs under the calling thread's selector; ""
+    for another `what`.  Host arithmetic only."""
+    return lib().pffft_hip_analytic_route(setup.handle, ANALYTIC_WHAT[what] if what in ANALYTIC_WHAT else int(what)).decode()
 
 
 def _is_torch(x) -> bool:
@@ -809,6 +825,49 @@ class DctSetup(_Handle):
         out = self._dense_out(out, x, batch, self.N)
         _check(self._fn("hip_dct_transform_batch")(self.handle, x.data_ptr(), out.data_ptr(), batch, self._stream()),
                "hip_dct_transform_batch")
+        return out
+
+
+class AnalyticSetup(_Handle):
+    """PFFFT_HIP_AnalyticSetup / PFFFTD_HIP_AnalyticSetup: the analytic signal z = x + j H{x} of rows of N reals (scipy.signal.hilbert),
+    its imaginary part and its envelope |z| (include/pffft_hip.h).  gain: None, or N/2 + 1 values that weight the bins 0 ... N/2 (a
+    one-sided band-pass in the same pass).  Raises ValueError where pffft_hip_analytic_new_setup returns NULL."""
+
+    _new, _destroy = "hip_analytic_new_setup", "hip_analytic_destroy_setup"
+
+    def __init__(self, N: int, gain=None, dtype=np.float32):
+        self.N, self.dtype = int(N), np.dtype(dtype)
+        g = None
+        if gain is not None:
+            g = np.ascontiguousarray(gain, dtype=self.dtype).ravel()
+            if g.size != self.N // 2 + 1:
+                raise ValueError(f"gain holds {g.size} values, N/2 + 1 = {self.N // 2 + 1} wanted")
+        self._open(_pfx(dtype), self.N, g.ctypes.data if g is not None else None,
+                   shown=f"pffft_hip_analytic_new_setup({N}, {'NULL' if g is None else 'gain'})")
+
+    def route(self, what="analytic") -> str:
+        """pffft_hip_analytic_route: "fused" / "composed" for this output under the calling thread's selector.  Host arithmetic only."""
+        return analytic_route(self, what)
+
+    def table(self, first: int = 0, count=None) -> np.ndarray:
+        """pffft_hip_analytic_table: the filter spectrum H[k] = c_k gain[k], k = first ... (N values in all, zeros above N/2), as a real
+        array of the setup's precision (host arithmetic only)."""
+        if count is None:
+            count = self.N - first
+        out = np.empty(max(int(count), 0), dtype=self.dtype)
+        rc = self._L.pffft_hip_analytic_table(self.handle, int(first), int(count), out.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"pffft_hip_analytic_table failed ({rc}): {self._L.pffft_hip_last_error().decode()}")
+        return out
+
+    def transform_batch(self, x, out=None, what="analytic"):
+        """x: contiguous CUDA tensor of the setup's dtype holding `batch` rows of N scalars.  what = "analytic": the result has `batch` rows
+        of 2N scalars (interleaved complex) and must not overlap x; "hilbert" / "envelope": rows of N scalars, out may be x."""
+        w = ANALYTIC_WHAT[what] if what in ANALYTIC_WHAT else int(what)
+        batch = self._whole_rows(x, self.N)
+        out = self._dense_out(out, x, batch, 2 * self.N if w == 0 else self.N)
+        _check(self._fn("hip_analytic_transform_batch")(self.handle, x.data_ptr(), out.data_ptr(), batch, w, self._stream()),
+               "hip_analytic_transform_batch")
         return out
 
 

@@ -85,7 +85,9 @@ enum AbValue : int {
     AB_MDCT_FUSED = 141,        // ... the fused register-tiled kernel wherever it is legal, whatever the measured default of the (size, entry) is
     AB_CSD_COMPOSED = 142,      // pffft_hip_frames_csd_batch: framing kernel (x and y) + transform_batch + run kernel through the frame matrix
     AB_CSD_FUSED = 143,         // ... the two-pass accumulating framed kernel wherever it is legal, whatever the measured default of the cell is
-    AB_FAKE_DEVICE = 130,      // the calling thread counts as being on ANOTHER device than its current one (key + 64): exercises the per-device
+    AB_ANALYTIC_COMPOSED = 144, // pffft_hip_analytic_transform_batch: never the fused kernel (widening kernel + convolve_batch + narrowing kernel)
+    AB_ANALYTIC_FUSED = 145,    // ... the fused real-loading convolution kernel wherever it is legal, whatever the measured default of the (size, output) is
+    AB_FAKE_DEVICE = 130,     // the calling thread counts as being on ANOTHER device than its current one (key + 64): exercises the per-device
                                 // replicas of a shared setup on a box with one GPU (tests/test_gpu_round6.py)
 };
 struct AbSel {
