@@ -691,6 +691,73 @@ int pffftd_hip_analytic_transform_batch(PFFFTD_HIP_AnalyticSetup *, const double
 const char *pffft_hip_analytic_route(const void *setup, int what);
 int pffft_hip_analytic_table(const void *setup, size_t first, size_t count, void *host_out);
 
+/* CROSS- AND AUTOCORRELATION OF ROWS (plain and PHAT-weighted): two rows that BOTH change per call, r[m] = sum_n conj(x[n]) y[n + m] -
+ * delay estimation (TDOA, GCC-PHAT), burst / preamble search against a received reference, range profiles of pulse pairs, and the
+ * autocorrelation (pitch, periodicity, Wiener-Khinchin).  (A FIXED template is pffft_hip_convolve_batch / pffastconv.)  A setup fixes
+ *   N                     any length pffft[d]_new_setup(N, PFFFT_COMPLEX) takes
+ *   real_rows             non-zero: rows of scalars in and out; zero: rows of interleaved (re, im) pairs in and out
+ *   len_x, len_y          1 <= len <= N: samples per x row / y row
+ *   lag0, nlags           the lag window: -N < lag0 < N, 1 <= nlags <= N
+ * NULL for anything else.  Creating a setup touches no device; the handle owns a complex setup of N and has no tables.  With x and y
+ * zero-extended to N samples and all indices taken mod N:
+ *     X = DFT_N(x),  Y = DFT_N(y)                      (forward, unscaled)
+ *     G[k] = W( conj(X[k]) Y[k] )
+ *     r = IDFT_N(G)                                    (backward, unscaled)
+ *     out[v][i] = s r[(lag0 + i) mod N],  i < nlags,   s = (T)(scaling / N) formed in double, rounded once
+ * Real rows: len_x / len_y scalars in and nlags scalars out (Re r).  Complex rows: interleaved in and out.  With len_x + len_y - 1 <= N,
+ * lag0 = -(len_x - 1), nlags = len_x + len_y - 1 this is scipy.signal.correlate(y, x, "full") (= np.correlate(y, x, "full")); with
+ * len_x = len_y = nlags = N, lag0 = 0 it is the circular correlation.
+ * The arithmetic between the transforms is ONE device function on every route, without fused multiply-adds in the product:
+ *     c_re = Xr Yr + Xi Yi,  c_im = Xr Yi - Xi Yr      (every product and every sum rounded once)
+ *     PFFFT_HIP_XCORR_PLAIN   G = (c_re, c_im)
+ *     PFFFT_HIP_XCORR_PHAT    m = sqrt(fma(c_re, c_re, c_im c_im)) with the correctly rounded square root (the envelope's form),
+ *                             G = (c_re / m, c_im / m) with correctly rounded divisions; m == 0 GIVES (+0, +0), never a NaN.
+ * Consequences of the PHAT rule, stated rather than hidden: a bin with |c| above about 1.8e19 (float; 1.3e154 double) has m = inf and
+ * comes out as ZERO; a bin whose c_re^2 + c_im^2 underflows to zero counts as EMPTY (zero); a non-finite input propagates (NaN).  The
+ * multiplication by s is one product per stored component, followed by + 0: that addition is exact and only turns a -0 into +0, so that
+ * A ROW WHOSE BINS ARE ALL EMPTY COMES OUT AS ALL +0 ON EVERY ROUTE (the inverse transform of an all +0 spectrum holds -0 in places on
+ * some routes).
+ * y == x (the same pointer; the setup must have len_x == len_y) is the AUTOCORRELATION: one load and one forward transform per row, G
+ * from (X, X) through the same function.  c_im is then a - a = +0 exactly, so the result is BIT-IDENTICAL to the cross path on a copy
+ * of x on the same route.  The routes themselves run different butterfly networks: they agree at the accuracy bar, not bit for bit.
+ * x, y, out are device pointers, non-NULL for batch > 0, aligned to ONE ELEMENT (4 / 8 bytes real, 8 / 16 bytes complex, float /
+ * double), rows dense.  out must not overlap x or y; x and y may overlap each other freely (both are only read).  batch == 0 binds the
+ * device and returns 0.  The call is asynchronous on `stream`; 0, else a hipError_t with its text in pffft_hip_last_error().
+ * Validation happens before any device is touched: a NULL or foreign handle or the other precision's (hipErrorInvalidHandle), an
+ * unknown weight, NULL pointers, y == x with len_x != len_y, misalignment, overlap of out with an input (hipErrorInvalidValue) ->
+ * nothing launched.
+ * Routes (pffft_hip_xcorr_route names the one a call takes under the calling thread's selector):
+ *   "fused"     float, N = 512 / 1024 / 2048 / 4096, both kinds, both weights, cross and auto: ONE kernel.  A workgroup slot runs the
+ *               forward register-tiled transform on the x row, keeps its bins in registers, runs it again on the y row through the same
+ *               LDS image, forms G, runs the backward transform and scatters the lag window: len_x + len_y elements read and nlags
+ *               written per row pair, predicated element-sized non-temporal accesses.  Which cells run it by default is a measured
+ *               table; pffft_hip_set_variant(147) runs it wherever it is legal, 146 never.
+ *   "composed"  every setup: a pad kernel writes the zero-extended x rows and y rows into the two halves of a per-stream scratch image,
+ *               ONE forward pffft[d]_hip_transform_batch (ordered) runs over both halves, a product kernel forms G in place on the y
+ *               half, ONE backward transform_batch (ordered) runs on that half, a crop kernel stores the lag window.  The
+ *               autocorrelation takes one row of the image per input row.  The image holds at most 256 MiB (longer batches go through
+ *               it in chunks on the stream); a call that would have to grow it on a capturing stream returns
+ *               hipErrorStreamCaptureUnsupported before any launch: run the call once before capturing.
+ * A setup serves ONE device, the one that is current at the first call (hipErrorInvalidDevice from another); any number of streams and
+ * threads of that device may share it.  THE FIRST CALL ON A SETUP BINDS IT (and the inner setup builds its device tables at its first
+ * use): make it BEFORE a stream capture - during one it fails with hipErrorStreamCaptureUnsupported and launches nothing.
+ * Two real rows packed into one complex transform, strided rows or a broadcast x, 16-byte fast paths for aligned lengths, SCOT / ML
+ * weightings, normalised coefficients and a fused double or other-size kernel are not offered. */
+typedef enum { PFFFT_HIP_XCORR_PLAIN = 0, PFFFT_HIP_XCORR_PHAT = 1 } pffft_hip_xcorr_weight_t;
+typedef struct PFFFT_HIP_XcorrSetup PFFFT_HIP_XcorrSetup;
+typedef struct PFFFTD_HIP_XcorrSetup PFFFTD_HIP_XcorrSetup;
+PFFFT_HIP_XcorrSetup *pffft_hip_xcorr_new_setup(int N, int real_rows, int len_x, int len_y, int lag0, int nlags);
+PFFFTD_HIP_XcorrSetup *pffftd_hip_xcorr_new_setup(int N, int real_rows, int len_x, int len_y, int lag0, int nlags);
+void pffft_hip_xcorr_destroy_setup(PFFFT_HIP_XcorrSetup *);     /* NULL-safe */
+void pffftd_hip_xcorr_destroy_setup(PFFFTD_HIP_XcorrSetup *);
+int pffft_hip_xcorr_batch(PFFFT_HIP_XcorrSetup *, const float *x, const float *y, float *out, size_t batch, pffft_hip_xcorr_weight_t w,
+                          float scaling, void *stream);
+int pffftd_hip_xcorr_batch(PFFFTD_HIP_XcorrSetup *, const double *x, const double *y, double *out, size_t batch,
+                           pffft_hip_xcorr_weight_t w, double scaling, void *stream);
+/* Host arithmetic only, handles of both precisions: "fused" / "composed" for (weight, cross or auto) under the calling thread's
+ * selector; "" for an invalid handle or another weight. */
+const char *pffft_hip_xcorr_route(const void *setup, int weight, int is_auto);
+
 /* Overlap-save FIR on device-resident signal/output (same block schedule as pffastconv_apply,
  * src/pffastconv.c:204-261): returns the number of output samples written, or -1 on error. */
 int pffastconv_hip_apply_device(PFFASTCONV_Setup *, const float *d_input, int inputLen, float *d_output,

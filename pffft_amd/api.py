@@ -122,6 +122,10 @@ def lib():
         g("hip_analytic_destroy_setup").restype = None; g("hip_analytic_destroy_setup").argtypes = [C.c_void_p]
         g("hip_analytic_transform_batch").restype = C.c_int
         g("hip_analytic_transform_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+        g("hip_xcorr_new_setup").restype = C.c_void_p; g("hip_xcorr_new_setup").argtypes = [C.c_int] * 6
+        g("hip_xcorr_destroy_setup").restype = None; g("hip_xcorr_destroy_setup").argtypes = [C.c_void_p]
+        g("hip_xcorr_batch").restype = C.c_int
+        g("hip_xcorr_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, ct, C.c_void_p]
         getattr(L, f"validate_{pfx}_simd").restype = C.c_int
         getattr(L, f"validate_{pfx}_simd_ex").restype = C.c_int
         getattr(L, f"validate_{pfx}_simd_ex").argtypes = [C.c_void_p]
@@ -166,6 +170,7 @@ def lib():
     L.pffft_hip_analytic_route.restype = C.c_char_p; L.pffft_hip_analytic_route.argtypes = [C.c_void_p, C.c_int]
     L.pffft_hip_analytic_table.restype = C.c_int
     L.pffft_hip_analytic_table.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+    L.pffft_hip_xcorr_route.restype = C.c_char_p; L.pffft_hip_xcorr_route.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.pffft_hip_kernel_name.restype = C.c_char_p; L.pffft_hip_kernel_name.argtypes = [C.c_void_p]
     L.pffft_hip_describe.restype = C.c_int; L.pffft_hip_describe.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.pffft_hip_route_occupancy.restype = C.c_int; L.pffft_hip_route_occupancy.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -868,6 +873,48 @@ class AnalyticSetup(_Handle):
         out = self._dense_out(out, x, batch, 2 * self.N if w == 0 else self.N)
         _check(self._fn("hip_analytic_transform_batch")(self.handle, x.data_ptr(), out.data_ptr(), batch, w, self._stream()),
                "hip_analytic_transform_batch")
+        return out
+
+
+XCORR_WEIGHT = {"plain": 0, "phat": 1}              # pffft_hip_xcorr_weight_t
+
+
+class XcorrSetup(_Handle):
+    """PFFFT_HIP_XcorrSetup / PFFFTD_HIP_XcorrSetup: cross- and autocorrelation r[m] = sum_n conj(x[n]) y[n + m] of rows through transforms
+    of length N, plain or PHAT-weighted, the lags lag0 ... lag0 + nlags - 1 (mod N) stored (include/pffft_hip.h).  real = True: rows of
+    scalars in and out; else interleaved complex rows.  len_x / len_y default to N, nlags to N.  Raises ValueError where
+    pffft_hip_xcorr_new_setup returns NULL."""
+
+    _new, _destroy = "hip_xcorr_new_setup", "hip_xcorr_destroy_setup"
+
+    def __init__(self, N: int, len_x=None, len_y=None, lag0: int = 0, nlags=None, real: bool = False, dtype=np.float32):
+        self.N, self.dtype, self.real = int(N), np.dtype(dtype), bool(real)
+        self.len_x = self.N if len_x is None else int(len_x)
+        self.len_y = self.N if len_y is None else int(len_y)
+        self.lag0 = int(lag0)
+        self.nlags = self.N if nlags is None else int(nlags)
+        self.spp = 1 if self.real else 2
+        self._open(_pfx(dtype), self.N, int(self.real), self.len_x, self.len_y, self.lag0, self.nlags,
+                   shown=f"pffft_hip_xcorr_new_setup({N}, {int(self.real)}, {self.len_x}, {self.len_y}, {self.lag0}, {self.nlags})")
+
+    def route(self, weighting="plain", auto: bool = False) -> str:
+        """pffft_hip_xcorr_route: "fused" / "composed" for (weighting, cross or auto) under the calling thread's selector; "" for another
+        weighting.  Host arithmetic only."""
+        w = XCORR_WEIGHT[weighting] if weighting in XCORR_WEIGHT else int(weighting)
+        return self._L.pffft_hip_xcorr_route(self.handle, w, int(bool(auto))).decode()
+
+    def correlate_batch(self, x, y=None, out=None, weighting="plain", scaling=1.0):
+        """x, y: contiguous CUDA tensors of the setup's dtype holding `batch` rows of len_x / len_y elements (scalars, or interleaved
+        complex pairs).  y = None (or y is x) is the autocorrelation.  The result has `batch` rows of nlags elements and must not overlap
+        x or y."""
+        w = XCORR_WEIGHT[weighting] if weighting in XCORR_WEIGHT else int(weighting)
+        batch = self._whole_rows(x, self.len_x * self.spp)
+        if y is None:
+            y = x
+        assert self._whole_rows(y, self.len_y * self.spp) == batch, "x and y hold different numbers of rows"
+        out = self._dense_out(out, x, batch, self.nlags * self.spp)
+        _check(self._fn("hip_xcorr_batch")(self.handle, x.data_ptr(), y.data_ptr(), out.data_ptr(), batch, w, float(scaling), self._stream()),
+               "hip_xcorr_batch")
         return out
 
 
