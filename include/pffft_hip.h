@@ -758,6 +758,50 @@ int pffftd_hip_xcorr_batch(PFFFTD_HIP_XcorrSetup *, const double *x, const doubl
  * selector; "" for an invalid handle or another weight. */
 const char *pffft_hip_xcorr_route(const void *setup, int weight, int is_auto);
 
+/* ---- batched 2-D complex transforms (numpy.fft.fft2 of a batch of images)
+ * pffft[d]_hip_fft2_new_setup(rows, cols): both lengths must be ones a complex setup of that precision takes, NULL otherwise.  Creating a
+ * setup touches no device; the handle owns one inner complex setup per distinct length (rows == cols shares one) and has no tables.
+ * An image is rows x cols interleaved complex values, row-major and dense; `batch` images follow one another:
+ *     out[u][v] = scaling * sum_r sum_c in[r][c] exp(-/+ 2 pi j (u r / rows + v c / cols))       (forward: the minus sign)
+ * Forward with scaling = 1 is numpy.fft.fft2, backward is ifft2 * rows * cols.  Input and output are in natural order; there is no internal
+ * layout.  `scaling` is ONE product per stored component in the last kernel of either route: scaling == 1 changes no bit.
+ * in, out are device pointers, non-NULL for batch > 0, ALIGNED TO 16 BYTES (as the ordered transform_batch asks).  in == out (in place) is
+ * legal on every route; any other overlap of the two ranges is refused.  `in` is never written unless it is `out`.  batch == 0 returns 0.
+ * The call is asynchronous on `stream`; 0, else a hipError_t with its text in pffft_hip_last_error().  Validation happens before any device
+ * is touched: a NULL or foreign handle or the other precision's (hipErrorInvalidHandle), an unknown direction, NULL pointers, misalignment,
+ * partial overlap (hipErrorInvalidValue) -> nothing launched.
+ * Routes (pffft_hip_fft2_route names the one a call takes under the calling thread's selector):
+ *   "fused"     float, rows and cols out of 16 / 32 / 64 (nine shapes): ONE kernel.  A workgroup holds whole images in LDS: 16-byte loads
+ *               of the image's dense run, a row pass and a column pass in place in a padded LDS image (one in-register 16- or 32-point
+ *               transform per line, 64 points as 8 x 8 with W_64 from the inner setup's table), 16-byte stores.  One HBM read and one HBM
+ *               write per image.  Which shapes run it by default is a measured table; pffft_hip_set_variant(149) runs
+ *               it wherever it is legal, 148 never.
+ *   "composed"  every setup: an ordered pffft[d]_hip_transform_batch of length cols over batch * rows rows from in to out, a transposing
+ *               kernel [rows][cols] -> [cols][rows] per image into a per-stream scratch image, an ordered transform_batch of length rows
+ *               over batch * cols rows in place there, the transposing kernel back into out, times scaling.  With scaling == 1 the result
+ *               equals, bit for bit, the four steps a caller can do by hand (transform_batch, transpose, transform_batch, transpose).  The
+ *               scratch holds at most 256 MiB (longer batches go through it in chunks of whole images on the stream); a call that would
+ *               have to grow it on a capturing stream returns hipErrorStreamCaptureUnsupported before any launch: run the call once before
+ *               capturing.
+ * The two routes agree at the accuracy bar of a transform of rows * cols points, not bit for bit.
+ * A setup serves ONE device, the one that is current at the first call (hipErrorInvalidDevice from another); any number of streams and
+ * threads of that device may share it.  THE FIRST CALL ON A SETUP BINDS IT: make it BEFORE a stream capture - during one it fails with
+ * hipErrorStreamCaptureUnsupported and launches nothing.
+ * Real input (rfft2, half-spectrum columns), strided or padded images, transforms along one axis only, a fused double kernel, fused shapes
+ * beyond 64 and mixed-radix tiles, multi-device shards of one setup and 3-D transforms are not offered. */
+typedef struct PFFFT_HIP_Fft2Setup PFFFT_HIP_Fft2Setup;
+typedef struct PFFFTD_HIP_Fft2Setup PFFFTD_HIP_Fft2Setup;
+PFFFT_HIP_Fft2Setup *pffft_hip_fft2_new_setup(int rows, int cols);
+PFFFTD_HIP_Fft2Setup *pffftd_hip_fft2_new_setup(int rows, int cols);
+void pffft_hip_fft2_destroy_setup(PFFFT_HIP_Fft2Setup *);     /* NULL-safe */
+void pffftd_hip_fft2_destroy_setup(PFFFTD_HIP_Fft2Setup *);
+int pffft_hip_fft2_transform_batch(PFFFT_HIP_Fft2Setup *, const float *in, float *out, size_t batch, pffft_direction_t direction,
+                                   float scaling, void *stream);
+int pffftd_hip_fft2_transform_batch(PFFFTD_HIP_Fft2Setup *, const double *in, double *out, size_t batch, pffft_direction_t direction,
+                                    double scaling, void *stream);
+/* Host arithmetic only, handles of both precisions: "fused" / "composed" under the calling thread's selector; "" for an invalid handle. */
+const char *pffft_hip_fft2_route(const void *setup);
+
 /* Overlap-save FIR on device-resident signal/output (same block schedule as pffastconv_apply,
  * src/pffastconv.c:204-261): returns the number of output samples written, or -1 on error. */
 int pffastconv_hip_apply_device(PFFASTCONV_Setup *, const float *d_input, int inputLen, float *d_output,

@@ -126,6 +126,10 @@ def lib():
         g("hip_xcorr_destroy_setup").restype = None; g("hip_xcorr_destroy_setup").argtypes = [C.c_void_p]
         g("hip_xcorr_batch").restype = C.c_int
         g("hip_xcorr_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, ct, C.c_void_p]
+        g("hip_fft2_new_setup").restype = C.c_void_p; g("hip_fft2_new_setup").argtypes = [C.c_int, C.c_int]
+        g("hip_fft2_destroy_setup").restype = None; g("hip_fft2_destroy_setup").argtypes = [C.c_void_p]
+        g("hip_fft2_transform_batch").restype = C.c_int
+        g("hip_fft2_transform_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, ct, C.c_void_p]
         getattr(L, f"validate_{pfx}_simd").restype = C.c_int
         getattr(L, f"validate_{pfx}_simd_ex").restype = C.c_int
         getattr(L, f"validate_{pfx}_simd_ex").argtypes = [C.c_void_p]
@@ -171,6 +175,7 @@ def lib():
     L.pffft_hip_analytic_table.restype = C.c_int
     L.pffft_hip_analytic_table.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
     L.pffft_hip_xcorr_route.restype = C.c_char_p; L.pffft_hip_xcorr_route.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.pffft_hip_fft2_route.restype = C.c_char_p; L.pffft_hip_fft2_route.argtypes = [C.c_void_p]
     L.pffft_hip_kernel_name.restype = C.c_char_p; L.pffft_hip_kernel_name.argtypes = [C.c_void_p]
     L.pffft_hip_describe.restype = C.c_int; L.pffft_hip_describe.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.pffft_hip_route_occupancy.restype = C.c_int; L.pffft_hip_route_occupancy.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -915,6 +920,37 @@ class XcorrSetup(_Handle):
         out = self._dense_out(out, x, batch, self.nlags * self.spp)
         _check(self._fn("hip_xcorr_batch")(self.handle, x.data_ptr(), y.data_ptr(), out.data_ptr(), batch, w, float(scaling), self._stream()),
                "hip_xcorr_batch")
+        return out
+
+
+class Fft2Setup(_Handle):
+    """PFFFT_HIP_Fft2Setup / PFFFTD_HIP_Fft2Setup: batched 2-D complex transforms of dense row-major images of rows x cols interleaved
+    complex values, natural order in and out (include/pffft_hip.h): forward with scaling 1 is numpy.fft.fft2, backward ifft2 * rows * cols.
+    Raises ValueError where pffft_hip_fft2_new_setup returns NULL (a length no complex setup of the precision takes)."""
+
+    _new, _destroy = "hip_fft2_new_setup", "hip_fft2_destroy_setup"
+
+    def __init__(self, rows: int, cols: int, dtype=np.float32):
+        self.rows, self.cols, self.dtype = int(rows), int(cols), np.dtype(dtype)
+        self.image_scalars = 2 * self.rows * self.cols
+        self._open(_pfx(dtype), self.rows, self.cols, shown=f"pffft_hip_fft2_new_setup({rows}, {cols})")
+
+    def route(self) -> str:
+        """pffft_hip_fft2_route: "fused" / "composed" under the calling thread's selector.  Host arithmetic only."""
+        return self._L.pffft_hip_fft2_route(self.handle).decode()
+
+    def transform_batch(self, x, out=None, direction=FORWARD, scaling=1.0):
+        """x: contiguous CUDA tensor of the setup's dtype holding whole images (of any shape, such as [batch, rows, 2 cols]).  out: None
+        (a new tensor shaped like x), another such tensor, or x itself (in place).  direction: FORWARD / BACKWARD or "forward" /
+        "backward"."""
+        import torch
+        d = {"forward": FORWARD, "backward": BACKWARD}.get(direction, direction)
+        batch = self._whole_rows(x, self.image_scalars)
+        if out is None:
+            out = torch.empty_like(x)
+        assert self._whole_rows(out, self.image_scalars) == batch, "x and out hold different numbers of images"
+        _check(self._fn("hip_fft2_transform_batch")(self.handle, x.data_ptr(), out.data_ptr(), batch, int(d), float(scaling), self._stream()),
+               "hip_fft2_transform_batch")
         return out
 
 

@@ -89,7 +89,9 @@ enum AbValue : int {
     AB_ANALYTIC_FUSED = 145,    // ... the fused real-loading convolution kernel wherever it is legal, whatever the measured default of the (size, output) is
     AB_XCORR_COMPOSED = 146,    // pffft_hip_xcorr_batch: never the fused kernel (pad kernel + transform_batch + product kernel + transform_batch + crop kernel)
     AB_XCORR_FUSED = 147,       // ... the fused two-pass correlation kernel wherever it is legal, whatever the measured default of the cell is
-    AB_FAKE_DEVICE = 130,     // the calling thread counts as being on ANOTHER device than its current one (key + 64): exercises the per-device
+    AB_FFT2_COMPOSED = 148,     // pffft_hip_fft2_transform_batch: never the fused kernel (transform_batch + transposing kernel + transform_batch + its twin)
+    AB_FFT2_FUSED = 149,        // ... the fused LDS-resident 2-D kernel wherever it is legal, whatever the measured default of the shape is
+    AB_FAKE_DEVICE = 130,    // the calling thread counts as being on ANOTHER device than its current one (key + 64): exercises the per-device
                                 // replicas of a shared setup on a box with one GPU (tests/test_gpu_round6.py)
 };
 struct AbSel {
