@@ -787,8 +787,9 @@ const char *pffft_hip_xcorr_route(const void *setup, int weight, int is_auto);
  * A setup serves ONE device, the one that is current at the first call (hipErrorInvalidDevice from another); any number of streams and
  * threads of that device may share it.  THE FIRST CALL ON A SETUP BINDS IT: make it BEFORE a stream capture - during one it fails with
  * hipErrorStreamCaptureUnsupported and launches nothing.
- * Real input (rfft2, half-spectrum columns), strided or padded images, transforms along one axis only, a fused double kernel, fused shapes
- * beyond 64 and mixed-radix tiles, multi-device shards of one setup and 3-D transforms are not offered. */
+ * Real images with half-spectrum columns are the next entry (pffft[d]_hip_rfft2_*).  Strided or padded images, transforms along one axis
+ * only, a fused double kernel, fused shapes beyond 64 and mixed-radix tiles, multi-device shards of one setup and 3-D transforms are not
+ * offered. */
 typedef struct PFFFT_HIP_Fft2Setup PFFFT_HIP_Fft2Setup;
 typedef struct PFFFTD_HIP_Fft2Setup PFFFTD_HIP_Fft2Setup;
 PFFFT_HIP_Fft2Setup *pffft_hip_fft2_new_setup(int rows, int cols);
@@ -801,6 +802,61 @@ int pffftd_hip_fft2_transform_batch(PFFFTD_HIP_Fft2Setup *, const double *in, do
                                     double scaling, void *stream);
 /* Host arithmetic only, handles of both precisions: "fused" / "composed" under the calling thread's selector; "" for an invalid handle. */
 const char *pffft_hip_fft2_route(const void *setup);
+
+/* ---- batched 2-D real transforms (numpy.fft.rfft2 / irfft2 of a batch of images)
+ * pffft[d]_hip_rfft2_new_setup(rows, cols): rows must be a length a COMPLEX setup of that precision takes, cols one a REAL setup takes
+ * (so cols >= 32), NULL otherwise.  Creating a setup touches no device; the handle owns a real inner setup of length cols, a complex one of
+ * length rows (and, for the fused row pass of cols = 64, a complex one of length 64 where rows is another length) and has no tables.
+ * bins = cols / 2 + 1.  Images are dense and row-major, `batch` of them one after another:
+ *   forward    rows x cols reals in, rows x bins interleaved complex values out:
+ *                  out[u][v] = scaling * sum_r sum_c in[r][c] exp(-2 pi j (u r / rows + v c / cols)),  v = 0 ... cols / 2
+ *              with scaling = 1 this is numpy.fft.rfft2.
+ *   backward   rows x bins complex values in, rows x cols reals out: numpy.fft.irfft2(X, s = (rows, cols)) * rows * cols * scaling.
+ *              A half-spectrum that is not Hermitian is read by numpy's rule: after the transform along the columns the imaginary parts
+ *              of the columns 0 and cols / 2 contribute nothing - only the Hermitian part (X[u] + conj X[rows - u]) / 2 of those two
+ *              columns counts.  Every route obeys it.
+ * `scaling` is ONE product per stored component and scaling == 1 changes no bit: forward in the last kernel of either route; backward in
+ * the store of the fused kernel, and on the composed route in the packing kernel AHEAD of the last transform_batch (which has no scaling
+ * argument) - so there a power of two reproduces the product of the unscaled result bit for bit, any other factor to rounding.
+ * in, out are device pointers, non-NULL for batch > 0, ALIGNED TO 16 BYTES (every image then starts on 16 bytes too: rows is a multiple of
+ * 16).  The two sides differ in size (4 rows cols against 8 rows bins bytes in float), so there is NO in-place form: in == out and every
+ * partial overlap of the two ranges, each with its own byte count for the direction, are refused.  `in` is never written.  batch == 0
+ * returns 0.  The call is asynchronous on `stream`; 0, else a hipError_t with its text in pffft_hip_last_error().  Validation happens before
+ * any device is touched, in this order: a NULL or foreign handle or the other precision's (hipErrorInvalidHandle), an unknown direction,
+ * the empty call, NULL pointers, misalignment, overlap (hipErrorInvalidValue) -> nothing launched.
+ * Routes (pffft_hip_rfft2_route names the one a call takes under the calling thread's selector):
+ *   "fused"     float, rows out of 16 / 32 / 64 and cols out of 32 / 64 (six shapes): ONE kernel, no scratch.  A workgroup holds whole
+ *               images in LDS: 16-byte loads of the image's dense run, the rows 2 l and 2 l + 1 as the real and imaginary parts of one
+ *               complex line, a row pass of rows / 2 lines, an untangling step, a column pass of cols / 2 columns (columns 0 and cols / 2
+ *               travel as one), 16-byte stores.  One HBM read and one HBM write per image.  Which shapes run it by default is a measured
+ *               table; pffft_hip_set_variant(151) runs it wherever it is legal, 150 never.
+ *   "composed"  every setup.  Forward: an ordered real pffft[d]_hip_transform_batch of length cols over batch * rows rows, an unpacking and
+ *               transposing kernel [rows][cols packed] -> [bins][rows] into a per-stream scratch image, an ordered complex
+ *               transform_batch of length rows over batch * bins rows in place there, a transposing kernel into out, times scaling.
+ *               Backward: the transposing kernel [rows][bins] -> [bins][rows] into the scratch, the complex transform_batch there, a
+ *               transposing and packing kernel into canonical packed real spectra in out, times scaling (it drops the imaginary parts of
+ *               the columns 0 and cols / 2: numpy's rule), the ordered real transform_batch in place in out.  With scaling == 1 either
+ *               direction equals, bit for bit, the same steps done by hand.  The scratch holds at most 256 MiB (longer batches go through
+ *               it in chunks of whole images on the stream); a call that would have to grow it on a capturing stream returns
+ *               hipErrorStreamCaptureUnsupported before any launch: run the call once before capturing.
+ * The two routes agree at the accuracy bar of a transform of rows * cols points, not bit for bit.
+ * A setup serves ONE device, the one that is current at the first call (hipErrorInvalidDevice from another); any number of streams and
+ * threads of that device may share it.  THE FIRST CALL ON A SETUP BINDS IT: make it BEFORE a stream capture - during one it fails with
+ * hipErrorStreamCaptureUnsupported and launches nothing.
+ * Padded or strided rows (and therefore in place), cols = 16, a fused double kernel, fused lengths beyond 64 and mixed-radix tiles,
+ * transforms along one axis only, multi-device shards of one setup and 3-D transforms are not offered. */
+typedef struct PFFFT_HIP_Rfft2Setup PFFFT_HIP_Rfft2Setup;
+typedef struct PFFFTD_HIP_Rfft2Setup PFFFTD_HIP_Rfft2Setup;
+PFFFT_HIP_Rfft2Setup *pffft_hip_rfft2_new_setup(int rows, int cols);
+PFFFTD_HIP_Rfft2Setup *pffftd_hip_rfft2_new_setup(int rows, int cols);
+void pffft_hip_rfft2_destroy_setup(PFFFT_HIP_Rfft2Setup *);     /* NULL-safe */
+void pffftd_hip_rfft2_destroy_setup(PFFFTD_HIP_Rfft2Setup *);
+int pffft_hip_rfft2_transform_batch(PFFFT_HIP_Rfft2Setup *, const float *in, float *out, size_t batch, pffft_direction_t direction,
+                                    float scaling, void *stream);
+int pffftd_hip_rfft2_transform_batch(PFFFTD_HIP_Rfft2Setup *, const double *in, double *out, size_t batch, pffft_direction_t direction,
+                                     double scaling, void *stream);
+/* Host arithmetic only, handles of both precisions: "fused" / "composed" under the calling thread's selector; "" for an invalid handle. */
+const char *pffft_hip_rfft2_route(const void *setup);
 
 /* Overlap-save FIR on device-resident signal/output (same block schedule as pffastconv_apply,
  * src/pffastconv.c:204-261): returns the number of output samples written, or -1 on error. */

@@ -130,6 +130,10 @@ def lib():
         g("hip_fft2_destroy_setup").restype = None; g("hip_fft2_destroy_setup").argtypes = [C.c_void_p]
         g("hip_fft2_transform_batch").restype = C.c_int
         g("hip_fft2_transform_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, ct, C.c_void_p]
+        g("hip_rfft2_new_setup").restype = C.c_void_p; g("hip_rfft2_new_setup").argtypes = [C.c_int, C.c_int]
+        g("hip_rfft2_destroy_setup").restype = None; g("hip_rfft2_destroy_setup").argtypes = [C.c_void_p]
+        g("hip_rfft2_transform_batch").restype = C.c_int
+        g("hip_rfft2_transform_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, ct, C.c_void_p]
         getattr(L, f"validate_{pfx}_simd").restype = C.c_int
         getattr(L, f"validate_{pfx}_simd_ex").restype = C.c_int
         getattr(L, f"validate_{pfx}_simd_ex").argtypes = [C.c_void_p]
@@ -176,6 +180,7 @@ def lib():
     L.pffft_hip_analytic_table.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
     L.pffft_hip_xcorr_route.restype = C.c_char_p; L.pffft_hip_xcorr_route.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.pffft_hip_fft2_route.restype = C.c_char_p; L.pffft_hip_fft2_route.argtypes = [C.c_void_p]
+    L.pffft_hip_rfft2_route.restype = C.c_char_p; L.pffft_hip_rfft2_route.argtypes = [C.c_void_p]
     L.pffft_hip_kernel_name.restype = C.c_char_p; L.pffft_hip_kernel_name.argtypes = [C.c_void_p]
     L.pffft_hip_describe.restype = C.c_int; L.pffft_hip_describe.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.pffft_hip_route_occupancy.restype = C.c_int; L.pffft_hip_route_occupancy.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -951,6 +956,40 @@ class Fft2Setup(_Handle):
         assert self._whole_rows(out, self.image_scalars) == batch, "x and out hold different numbers of images"
         _check(self._fn("hip_fft2_transform_batch")(self.handle, x.data_ptr(), out.data_ptr(), batch, int(d), float(scaling), self._stream()),
                "hip_fft2_transform_batch")
+        return out
+
+
+class Rfft2Setup(_Handle):
+    """PFFFT_HIP_Rfft2Setup / PFFFTD_HIP_Rfft2Setup: batched 2-D real transforms of dense row-major images (include/pffft_hip.h): forward
+    rows x cols reals -> rows x bins interleaved complex values, bins = cols / 2 + 1 (numpy.fft.rfft2 with scaling 1); backward the
+    half-spectrum -> rows x cols reals (numpy.fft.irfft2 * rows * cols).  There is no in-place form.  Raises ValueError where
+    pffft_hip_rfft2_new_setup returns NULL (rows: a length no complex setup of the precision takes; cols: one no real setup takes)."""
+
+    _new, _destroy = "hip_rfft2_new_setup", "hip_rfft2_destroy_setup"
+
+    def __init__(self, rows: int, cols: int, dtype=np.float32):
+        self.rows, self.cols, self.dtype = int(rows), int(cols), np.dtype(dtype)
+        self.bins = self.cols // 2 + 1
+        self.image_scalars = self.rows * self.cols
+        self.spectrum_scalars = 2 * self.rows * self.bins
+        self._open(_pfx(dtype), self.rows, self.cols, shown=f"pffft_hip_rfft2_new_setup({rows}, {cols})")
+
+    def route(self) -> str:
+        """pffft_hip_rfft2_route: "fused" / "composed" under the calling thread's selector.  Host arithmetic only."""
+        return self._L.pffft_hip_rfft2_route(self.handle).decode()
+
+    def transform_batch(self, x, out=None, direction=FORWARD, scaling=1.0):
+        """x: contiguous CUDA tensor of the setup's dtype holding whole images of the direction's input side (forward: image_scalars reals
+        each; backward: spectrum_scalars each).  out: None (a new [batch, scalars of the other side] tensor) or such a tensor that does not
+        overlap x.  direction: FORWARD / BACKWARD or "forward" / "backward"."""
+        d = {"forward": FORWARD, "backward": BACKWARD}.get(direction, direction)
+        row_in, row_out = (self.spectrum_scalars, self.image_scalars) if d == BACKWARD else (self.image_scalars, self.spectrum_scalars)
+        batch = self._whole_rows(x, row_in)
+        if out is None:
+            out = self._dense_out(None, x, batch, row_out)
+        assert self._whole_rows(out, row_out) == batch, "x and out hold different numbers of images"
+        _check(self._fn("hip_rfft2_transform_batch")(self.handle, x.data_ptr(), out.data_ptr(), batch, int(d), float(scaling), self._stream()),
+               "hip_rfft2_transform_batch")
         return out
 
 

@@ -91,6 +91,8 @@ enum AbValue : int {
     AB_XCORR_FUSED = 147,       // ... the fused two-pass correlation kernel wherever it is legal, whatever the measured default of the cell is
     AB_FFT2_COMPOSED = 148,     // pffft_hip_fft2_transform_batch: never the fused kernel (transform_batch + transposing kernel + transform_batch + its twin)
     AB_FFT2_FUSED = 149,        // ... the fused LDS-resident 2-D kernel wherever it is legal, whatever the measured default of the shape is
+    AB_RFFT2_COMPOSED = 150,    // pffft_hip_rfft2_transform_batch: never the fused kernel (real transform_batch + unpacking kernel + transform_batch + transposing kernel)
+    AB_RFFT2_FUSED = 151,       // ... the fused LDS-resident 2-D real kernel wherever it is legal, whatever the measured default of the shape is
     AB_FAKE_DEVICE = 130,    // the calling thread counts as being on ANOTHER device than its current one (key + 64): exercises the per-device
                                 // replicas of a shared setup on a box with one GPU (tests/test_gpu_round6.py)
 };
