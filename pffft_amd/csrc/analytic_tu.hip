@@ -34,8 +34,7 @@ static bool analytic_fused_default(int N, int what) {
 }
 
 static bool analytic_fused_now(const AnalyticSetup* z, int what, const AbSel& sel) {
-    if (!z->fusable || sel.is(AB_ANALYTIC_COMPOSED)) return false;
-    return sel.is(AB_ANALYTIC_FUSED) || analytic_fused_default(z->N, what);
+    return fused_selected(sel, AB_ANALYTIC_COMPOSED, AB_ANALYTIC_FUSED, z->fusable, analytic_fused_default(z->N, what));
 }
 
 template <typename G>
@@ -69,10 +68,7 @@ static int analytic_build_tables(AnalyticSetup* z) {
     int rc = upload_table(tmp, h);
     if (!rc) rc = z->d_H.grow(N * sizeof(cx<T>));
     if (rc) return rc;
-    if constexpr (sizeof(T) == 8)
-        rc = pffftd_hip_zreorder_batch(static_cast<PFFFTD_Setup*>(z->inner), tmp.as<double>(), z->d_H.as<double>(), 1, PFFFT_BACKWARD, nullptr);
-    else
-        rc = pffft_hip_zreorder_batch(static_cast<PFFFT_Setup*>(z->inner), tmp.as<float>(), z->d_H.as<float>(), 1, PFFFT_BACKWARD, nullptr);
+    rc = inner_zreorder_batch<T>(z->inner, tmp.as<T>(), z->d_H.as<T>(), 1, PFFFT_BACKWARD, nullptr);
     const hipError_t e = hipStreamSynchronize(nullptr);   // (the permutation reads tmp: it has finished before the temporary goes)
     if (rc) return rc;
     return e == hipSuccess ? 0 : fail(e, "the filter spectrum of an analytic setup");
@@ -96,9 +92,7 @@ static int analytic_fused(AnalyticSetup* z, const float* in, float* out, size_t 
 
 template <typename T>
 static int analytic_widen(const T* in, cx<T>* X, size_t total, hipStream_t st) {
-    hipLaunchKernelGGL((analytic_widen_kernel<T>), dim3(stream_grid(total)), dim3(256), 0, st, in, X, total);
-    PF_CHECK(hipGetLastError());
-    return 0;
+    return stream_launch(analytic_widen_kernel<T>, total, st, in, X, total);
 }
 
 // ANALYTIC: (x, 0) straight into out, the convolution in place there - no scratch of this handle's
@@ -107,10 +101,7 @@ static int analytic_composed_complex(AnalyticSetup* z, const T* in, T* out, size
     const size_t N = (size_t)z->N;
     const T scaling = (T)1 / (T)N;
     if (int rc = analytic_widen<T>(in, reinterpret_cast<cx<T>*>(out), batch * N, st)) return rc;
-    if constexpr (sizeof(T) == 8)
-        return pffftd_hip_convolve_batch(static_cast<PFFFTD_Setup*>(z->inner), out, z->d_H.as<double>(), out, scaling, batch, 0, 1, st);
-    else
-        return pffft_hip_convolve_batch(static_cast<PFFFT_Setup*>(z->inner), out, z->d_H.as<float>(), out, scaling, batch, 0, 1, st);
+    return inner_convolve_batch<T>(z->inner, out, z->d_H.as<T>(), out, scaling, batch, st);
 }
 
 // HILBERT / ENVELOPE: through the chunked scratch image
@@ -120,12 +111,7 @@ static int analytic_composed_real(AnalyticSetup* z, const T* in, T* out, size_t 
     return bluestein_composed<T>(
         z->inner, z->pad, (const T*)z->d_H.as<T>(), N, batch, st,
         [&](cx<T>* X, size_t v0, size_t cnt) { return analytic_widen<T>(in + v0 * N, X, cnt * N, st); },
-        [&](cx<T>* X, size_t v0, size_t cnt) {
-            hipLaunchKernelGGL((analytic_narrow_kernel<T, WHAT>), dim3(stream_grid(cnt * N)), dim3(256), 0, st, (const cx<T>*)X, out + v0 * N,
-                               cnt * N);
-            PF_CHECK(hipGetLastError());
-            return 0;
-        });
+        [&](cx<T>* X, size_t v0, size_t cnt) { return stream_launch(analytic_narrow_kernel<T, WHAT>, cnt * N, st, (const cx<T>*)X, out + v0 * N, cnt * N); });
 }
 
 // ------------------------------------------------------------------------------------------------ the entry
@@ -139,9 +125,8 @@ static int analytic_transform_batch(void* setup, const T* in, T* out, size_t bat
     if (((uintptr_t)in & 7) || ((uintptr_t)out & (cplx ? 15 : 7)))
         return bad("analytic: in / out not aligned to 8 bytes (real rows) / 16 bytes (complex rows)");
     if (batch && (cplx || in != out)) {   // the real outputs: the same rows in place, or rows that do not overlap
-        const uintptr_t i0 = (uintptr_t)in, i1 = i0 + batch * (size_t)z->N * sizeof(T);
-        const uintptr_t o0 = (uintptr_t)out, o1 = o0 + batch * (size_t)z->N * (cplx ? 2 : 1) * sizeof(T);
-        if (i0 < o1 && o0 < i1) return bad(cplx ? "analytic: in and out overlap" : "analytic: in and out overlap without being equal");
+        const size_t in_bytes = batch * (size_t)z->N * sizeof(T);
+        if (ranges_overlap((uintptr_t)in, in_bytes, (uintptr_t)out, in_bytes * (cplx ? 2 : 1))) return bad(cplx ? "analytic: in and out overlap" : "analytic: in and out overlap without being equal");
     }
     int rc = analytic_ensure<T>(z, st);
     if (rc || batch == 0) return rc;

@@ -138,16 +138,10 @@ static int any_composed(AnySetup* a, const T* in, T* out, size_t batch, int cj, 
     return bluestein_composed<T>(
         a->inner, a->pad, (const T*)a->d_H.as<T>(), M, batch, st,
         [&](cx<T>* X, size_t v0, size_t cnt) {
-            hipLaunchKernelGGL((any_pad_kernel<T>), dim3(stream_grid(cnt * M)), dim3(256), 0, st, reinterpret_cast<const cx<T>*>(in) + v0 * N, X,
-                               w, cnt, N, M, cj);
-            PF_CHECK(hipGetLastError());
-            return 0;
+            return stream_launch(any_pad_kernel<T>, cnt * M, st, reinterpret_cast<const cx<T>*>(in) + v0 * N, X, w, cnt, N, M, cj);
         },
         [&](cx<T>* X, size_t v0, size_t cnt) {
-            hipLaunchKernelGGL((any_crop_kernel<T>), dim3(stream_grid(cnt * N)), dim3(256), 0, st, (const cx<T>*)X,
-                               reinterpret_cast<cx<T>*>(out) + v0 * N, w, cnt, N, M, cj);
-            PF_CHECK(hipGetLastError());
-            return 0;
+            return stream_launch(any_crop_kernel<T>, cnt * N, st, (const cx<T>*)X, reinterpret_cast<cx<T>*>(out) + v0 * N, w, cnt, N, M, cj);
         });
 }
 
@@ -171,16 +165,9 @@ static int any_real_composed(AnySetup* a, const T* in, T* out, size_t batch, int
     const cx<T>* w = a->d_chirp.as<cx<T>>();
     return bluestein_composed<T>(
         a->inner, a->pad, (const T*)(back ? a->d_Hr : a->d_H).template as<T>(), M, batch, st,
+        [&](cx<T>* X, size_t v0, size_t cnt) { return stream_launch(any_real_pad_kernel<T>, cnt * M, st, in + v0 * rin, X, w, cnt, N, H, M, back); },
         [&](cx<T>* X, size_t v0, size_t cnt) {
-            hipLaunchKernelGGL((any_real_pad_kernel<T>), dim3(stream_grid(cnt * M)), dim3(256), 0, st, in + v0 * rin, X, w, cnt, N, H, M, back);
-            PF_CHECK(hipGetLastError());
-            return 0;
-        },
-        [&](cx<T>* X, size_t v0, size_t cnt) {
-            hipLaunchKernelGGL((any_real_crop_kernel<T>), dim3(stream_grid(cnt * (back ? N : H))), dim3(256), 0, st, (const cx<T>*)X,
-                               out + v0 * rout, w, cnt, N, H, M, back);
-            PF_CHECK(hipGetLastError());
-            return 0;
+            return stream_launch(any_real_crop_kernel<T>, cnt * (back ? N : H), st, (const cx<T>*)X, out + v0 * rout, w, cnt, N, H, M, back);
         });
 }
 
@@ -191,16 +178,10 @@ static int any_real_direct(AnySetup* a, const T* in, T* out, size_t batch, int b
     return chunked_scratch<T>(a->pad, st, batch, N * sizeof(T), "the scratch image", [&](T* S, size_t v0, size_t cnt) {
         if (!back) {
             if (int rc = transform_batch_any(a->inner, in + v0 * N, S, cnt, PFFFT_FORWARD, 1, st)) return rc;
-            hipLaunchKernelGGL((any_real_unpack_kernel<T>), dim3(stream_grid(cnt * H)), dim3(256), 0, st, (const T*)S,
-                               reinterpret_cast<cx<T>*>(out) + v0 * H, cnt, N);
-            PF_CHECK(hipGetLastError());
-        } else {
-            hipLaunchKernelGGL((any_real_pack_kernel<T>), dim3(stream_grid(cnt * H)), dim3(256), 0, st, reinterpret_cast<const cx<T>*>(in) + v0 * H, S,
-                               cnt, N);
-            PF_CHECK(hipGetLastError());
-            return transform_batch_any(a->inner, S, out + v0 * N, cnt, PFFFT_BACKWARD, 1, st);
+            return stream_launch(any_real_unpack_kernel<T>, cnt * H, st, (const T*)S, reinterpret_cast<cx<T>*>(out) + v0 * H, cnt, N);
         }
-        return 0;
+        if (int rc = stream_launch(any_real_pack_kernel<T>, cnt * H, st, reinterpret_cast<const cx<T>*>(in) + v0 * H, S, cnt, N)) return rc;
+        return transform_batch_any(a->inner, S, out + v0 * N, cnt, PFFFT_BACKWARD, 1, st);
     });
 }
 

@@ -1,7 +1,8 @@
-// Host code shared by the translation units that run Bluestein's algorithm on the library's own convolution (any_tu.hip, zoom_tu.hip):
-// the handle types of the inner setups, the spectrum of the fixed filter, the launch of fft_conv_kernel with a loader / store policy
-// (the fused route) and the pad -> convolve_batch -> crop sequence through a per-stream scratch image (the composed route).  The handle
-// base, the slices and the chunked scratch are pf_compose.h's.
+// Host code shared by the translation units that put a loader / store policy around the library's own convolution: Bluestein's algorithm
+// (any_tu.hip, zoom_tu.hip), the analytic signals (analytic_tu.hip) and, for the walk of the fused lengths alone, the correlations
+// (xcorr_tu.hip).  The spectrum of the fixed filter, the launch of fft_conv_kernel with a policy (the fused route) and the pad ->
+// convolve_batch -> crop sequence through a per-stream scratch image (the composed route).  The handle base, the inner setup's device
+// test and typed entries, the slices and the chunked scratch are pf_compose.h's.
 #pragma once
 #include <vector>
 
@@ -18,8 +19,7 @@ static int bluestein_filter_spectrum(Setup* inner, size_t M, std::vector<cx<doub
     if (rc) return rc;
     if constexpr (sizeof(T) == 8) {
         PF_CHECK(hipMemcpy(dst.get(), b.data(), M * sizeof(cx<double>), hipMemcpyHostToDevice));
-        if ((rc = pffftd_hip_transform_batch(static_cast<PFFFTD_Setup*>(inner), dst.as<double>(), dst.as<double>(), 1, PFFFT_FORWARD, 0, nullptr)))
-            return rc;
+        if ((rc = inner_transform_batch<T>(inner, dst.as<T>(), dst.as<T>(), 1, PFFFT_FORWARD, 0, nullptr))) return rc;
     } else {
         // float: the filter spectrum from the DOUBLE transform, rounded once (a float transform of b would add its error to every output);
         // the permutation into the internal layout is exact
@@ -42,7 +42,7 @@ static int bluestein_filter_spectrum(Setup* inner, size_t M, std::vector<cx<doub
         std::vector<cx<float>> bf(M);
         for (size_t m = 0; m < M; ++m) bf[m] = mk<float>((float)b[m].x, (float)b[m].y);
         PF_CHECK(hipMemcpy(tmpf.get(), bf.data(), M * sizeof(cx<float>), hipMemcpyHostToDevice));
-        rc = pffft_hip_zreorder_batch(static_cast<PFFFT_Setup*>(inner), tmpf.as<float>(), dst.as<float>(), 1, PFFFT_BACKWARD, nullptr);
+        rc = inner_zreorder_batch<float>(inner, tmpf.as<float>(), dst.as<float>(), 1, PFFFT_BACKWARD, nullptr);
         e = hipStreamSynchronize(nullptr);   // (the permutation reads tmpf: it has finished before the temporaries go)
         if (rc) return rc;
         if (e != hipSuccess) return fail(e, "the filter spectrum of a Bluestein setup");
@@ -57,13 +57,9 @@ static int bluestein_filter_spectrum(Setup* inner, size_t M, std::vector<cx<doub
 // setup of length M, H the filter spectrum in its internal layout
 template <class C, class IO>
 static int bluestein_fused_launch(Setup* s, const IO& io, const float* H, size_t batch, int M, hipStream_t st) {
-    auto k = fft_conv_kernel<C, 0, IO>;
-    LoopLaunch ll;
-    if (int rc = loop_launch(s, st, k, C::WG_THREADS, C::LDS_BYTES, (batch + C::T_PER_WG - 1) / C::T_PER_WG, CONV_ONESHOT, &ll)) return rc;
     const cx<float>* tw = s->d_tw.as<cx<float>>();
-    hipLaunchKernelGGL(k, dim3(ll.grid), dim3(C::WG_THREADS), C::LDS_BYTES, st, io, H, (unsigned)batch, 1.0f / (float)M, tw, tw, ll.ctr);
-    PF_CHECK(hipGetLastError());
-    return 0;
+    return loop_launch_last(s, st, fft_conv_kernel<C, 0, IO>, C::WG_THREADS, C::LDS_BYTES, (batch + C::T_PER_WG - 1) / C::T_PER_WG, CONV_ONESHOT, io, H,
+                            (unsigned)batch, 1.0f / (float)M, tw, tw);
 }
 
 // The fused route of a float setup whose convolution length M is one of the fused lengths: the inner setup must hold its tables on the
@@ -72,13 +68,7 @@ static int bluestein_fused_launch(Setup* s, const IO& io, const float* H, size_t
 template <class F>
 static int bluestein_fused(Setup* inner, int M, size_t batch, F&& launch) {
     typedef ConvPick<float> P;
-    Setup* s = for_device(inner);
-    if (s != inner) {
-        g_last_error = "pffft_hip: this setup holds its tables on another device";
-        return (int)hipErrorInvalidDevice;
-    }
-    int rc = ensure_device_any(s);
-    if (rc) return rc;
+    if (int rc = inner_on_device(inner)) return rc;
     return for_slices(batch, [&](size_t b0, size_t nb) {
         switch (M) {
             case 512: return launch(CfgTag<P::C512>(), b0, nb);
@@ -98,13 +88,9 @@ template <typename T, class PadK, class CropK>
 static int bluestein_composed(Setup* inner, StreamScratch& pad, const T* H, size_t M, size_t batch, hipStream_t st, PadK&& pad_k, CropK&& crop_k) {
     const T scaling = (T)1 / (T)M;
     return chunked_scratch<cx<T>>(pad, st, batch, M * sizeof(cx<T>), "the scratch image", [&](cx<T>* X, size_t v0, size_t cnt) {
-        int rc = pad_k(X, v0, cnt);
-        if (rc) return rc;
-        if constexpr (sizeof(T) == 8)
-            rc = pffftd_hip_convolve_batch(static_cast<PFFFTD_Setup*>(inner), (const double*)X, H, (double*)X, scaling, cnt, 0, 1, st);
-        else
-            rc = pffft_hip_convolve_batch(static_cast<PFFFT_Setup*>(inner), (const float*)X, H, (float*)X, scaling, cnt, 0, 1, st);
-        return rc ? rc : crop_k(X, v0, cnt);
+        if (int rc = pad_k(X, v0, cnt)) return rc;
+        if (int rc = inner_convolve_batch<T>(inner, (const T*)X, H, (T*)X, scaling, cnt, st)) return rc;
+        return crop_k(X, v0, cnt);
     });
 }
 

@@ -9,14 +9,9 @@ namespace pf {
 
 template <typename T, class C, int REAL>
 static int conv_launch_io(Setup* s, const T* in, const T* H, T* out, size_t batch, T scaling, int accumulate, hipStream_t st) {
-    auto k = fft_conv_kernel<C, REAL>;
-    LoopLaunch ll;
-    if (int rc = loop_launch(s, st, k, C::WG_THREADS, C::LDS_BYTES, (batch + C::T_PER_WG - 1) / C::T_PER_WG, CONV_ONESHOT, &ll)) return rc;
     const ConvDenseIO<C, REAL> io{in, out, accumulate};
-    hipLaunchKernelGGL(k, dim3(ll.grid), dim3(C::WG_THREADS), C::LDS_BYTES, st, io, H, (unsigned)batch, scaling,
-                       (const cx<T>*)s->d_tw.as<cx<T>>(), (const cx<T>*)s->d_twr.as<cx<T>>(), ll.ctr);
-    PF_CHECK(hipGetLastError());
-    return 0;
+    return loop_launch_last(s, st, fft_conv_kernel<C, REAL>, C::WG_THREADS, C::LDS_BYTES, (batch + C::T_PER_WG - 1) / C::T_PER_WG, CONV_ONESHOT, io, H,
+                            (unsigned)batch, scaling, (const cx<T>*)s->d_tw.as<cx<T>>(), (const cx<T>*)s->d_twr.as<cx<T>>());
 }
 
 template <typename T, class C>

@@ -125,19 +125,16 @@ static int csd_batch(Setup* s, const T* x, size_t x_stride, const T* y, size_t y
             if ((rc = transform_batch_any(s, X, X, 2 * nfr, PFFFT_FORWARD, 1, st))) return rc;
             return with_flag(a.real, [&](auto R) {
                 return with_what(kwhat, [&](auto K) {
-                    hipLaunchKernelGGL((csd_runs_kernel<T, decltype(R)::value, decltype(K)::value>), dim3(stream_grid(cnt * P)), dim3(256), 0, st, X, Y,
-                                       (unsigned)row, r, cnt, navg, p.rpg, dst, dstride, scale);
-                    return 0;
+                    return stream_launch(csd_runs_kernel<T, decltype(R)::value, decltype(K)::value>, cnt * P, st, X, Y, (unsigned)row, r, cnt, navg, p.rpg,
+                                         dst, dstride, scale);
                 });
             });
         },
         [&](T* part, size_t rows, T* out_rows) {
             if (what == CSD_COHERENCE)
-                hipLaunchKernelGGL((csd_coherence_reduce_kernel<T>), dim3(stream_grid(rows * P)), dim3(256), 0, st, part, p.rpg, (unsigned)P, rows,
-                                   out_rows, out_stride);
-            else   // cross and all-four rows: the sum of the partial rows, scalar by scalar
-                hipLaunchKernelGGL((psd_reduce_kernel<T>), dim3(stream_grid(rows * W)), dim3(256), 0, st, part, p.rpg, (unsigned)W, rows, scaling,
-                                   out_rows, out_stride);
+                return stream_launch(csd_coherence_reduce_kernel<T>, rows * P, st, part, p.rpg, (unsigned)P, rows, out_rows, out_stride);
+            // cross and all-four rows: the sum of the partial rows, scalar by scalar
+            return stream_launch(psd_reduce_kernel<T>, rows * W, st, part, p.rpg, (unsigned)W, rows, scaling, out_rows, out_stride);
         });
 }
 

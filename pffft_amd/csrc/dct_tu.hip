@@ -83,8 +83,7 @@ static bool dct_fused_default(int N, int kind) {
 }
 
 static bool dct_fused_now(const DctSetup* z, const AbSel& sel) {
-    if (sel.is(AB_DCT_COMPOSED) || !dct_fusable(z, nullptr)) return false;
-    return sel.is(AB_DCT_FUSED) || dct_fused_default(z->N, z->kind);
+    return fused_selected(sel, AB_DCT_COMPOSED, AB_DCT_FUSED, dct_fusable(z, nullptr), dct_fused_default(z->N, z->kind));
 }
 
 static DctSetup* dct_new_setup(int N, int kind, int norm, int is_double) {
@@ -115,14 +114,9 @@ static int dct_composed_kind(DctSetup* z, Setup* s, const T* in, T* out, size_t 
     constexpr bool III = dct_type3(KIND);
     const size_t N = (size_t)z->N;
     return chunked_scratch<T>(z->scratch, st, batch, N * sizeof(T), "dct: the scratch image", [&](T* X, size_t v0, size_t cnt) {
-        hipLaunchKernelGGL((dct_pre_kernel<T, KIND>), dim3(stream_grid(cnt * (III ? N / 8 : N / 4))), dim3(256), 0, st, in + v0 * N, X, tab, cnt,
-                           (unsigned)N);
-        PF_CHECK(hipGetLastError());
+        if (int rc = stream_launch(dct_pre_kernel<T, KIND>, cnt * (III ? N / 8 : N / 4), st, in + v0 * N, X, tab, cnt, (unsigned)N)) return rc;
         if (int rc = transform_batch_any(s, X, X, cnt, III ? PFFFT_BACKWARD : PFFFT_FORWARD, 1, st)) return rc;
-        hipLaunchKernelGGL((dct_post_kernel<T, KIND>), dim3(stream_grid(cnt * (III ? N / 4 : N / 8))), dim3(256), 0, st, (const T*)X, out + v0 * N,
-                           tab, cnt, (unsigned)N);
-        PF_CHECK(hipGetLastError());
-        return 0;
+        return stream_launch(dct_post_kernel<T, KIND>, cnt * (III ? N / 4 : N / 8), st, (const T*)X, out + v0 * N, tab, cnt, (unsigned)N);
     });
 }
 
@@ -144,10 +138,8 @@ static int dct_transform_batch(void* setup, const T* in, T* out, size_t batch, h
     if (batch == 0) return 0;
     if (!in || !out) return bad("dct: NULL in / out");
     if (((uintptr_t)in | (uintptr_t)out) & 15) return bad("dct: in / out not aligned to 16 bytes");
-    if (in != out) {   // the same rows in place, or rows that do not overlap
-        const uintptr_t i0 = (uintptr_t)in, o0 = (uintptr_t)out, len = batch * (size_t)z->N * sizeof(T);
-        if (i0 < o0 + len && o0 < i0 + len) return bad("dct: in and out overlap without being equal");
-    }
+    const size_t len = batch * (size_t)z->N * sizeof(T);   // the same rows in place, or rows that do not overlap
+    if (in != out && ranges_overlap((uintptr_t)in, len, (uintptr_t)out, len)) return bad("dct: in and out overlap without being equal");
     Setup* s = for_device(z->inner);   // the object that holds the inner setup's tables on the calling thread's device
     int rc = ensure_device_any(s);
     if (rc) return rc;

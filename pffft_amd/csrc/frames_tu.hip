@@ -101,10 +101,8 @@ static int frames_transform_batch(Setup* s, const T* signal, size_t signal_strid
 template <typename T>
 static int launch_ola(const T* y, size_t fbase, size_t fpitch, size_t nframes, size_t hop, size_t N, size_t spp, const T* window, T scaling,
                       T* signal, size_t signal_stride, size_t nsignals, size_t s0, size_t s1, hipStream_t st) {
-    hipLaunchKernelGGL((frames_ola_kernel<T>), dim3(stream_grid(nsignals * (s1 - s0) * spp)), dim3(256), 0, st, y, fbase, fpitch, nframes, hop,
-                       (unsigned)N, (int)spp, window, scaling, signal, signal_stride, nsignals, s0, s1);
-    PF_CHECK(hipGetLastError());
-    return 0;
+    return stream_launch(frames_ola_kernel<T>, nsignals * (s1 - s0) * spp, st, y, fbase, fpitch, nframes, hop, (unsigned)N, (int)spp, window, scaling,
+                         signal, signal_stride, nsignals, s0, s1);
 }
 
 template <typename T>

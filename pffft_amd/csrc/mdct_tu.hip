@@ -81,8 +81,7 @@ static bool mdct_fused_default(int M, int what) {
 }
 
 static bool mdct_fused_now(const MdctSetup* z, int what, const AbSel& sel) {
-    if (sel.is(AB_MDCT_COMPOSED) || !mdct_fusable(z, MDCT_ROW, nullptr)) return false;
-    return sel.is(AB_MDCT_FUSED) || mdct_fused_default(z->M, what);
+    return fused_selected(sel, AB_MDCT_COMPOSED, AB_MDCT_FUSED, mdct_fusable(z, MDCT_ROW, nullptr), mdct_fused_default(z->M, what));
 }
 
 static MdctSetup* mdct_new_setup(int M, int is_double) {
@@ -121,22 +120,14 @@ static int mdct_composed_rows(MdctSetup* z, Setup* s, const T* in, size_t in_str
                               size_t out_stride, size_t v0, size_t cnt, T gain, const MdctTabs& tb, hipStream_t st) {
     constexpr size_t U = 16 / sizeof(T);
     const size_t M = (size_t)z->M;
-    const cx<T>* ta = static_cast<const cx<T>*>(tb.a);
-    const unsigned grid = stream_grid(cnt * (M / 8));
-    if (in_stride % U == 0)
-        hipLaunchKernelGGL((mdct_fold_kernel<T, LOAD, true>), dim3(grid), dim3(256), 0, st, in, in_stride, nframes, window, X, ta, v0, cnt, (unsigned)M);
-    else
-        hipLaunchKernelGGL((mdct_fold_kernel<T, LOAD, false>), dim3(grid), dim3(256), 0, st, in, in_stride, nframes, window, X, ta, v0, cnt, (unsigned)M);
-    PF_CHECK(hipGetLastError());
+    const cx<T>*ta = static_cast<const cx<T>*>(tb.a), *tbb = static_cast<const cx<T>*>(tb.b);
+    const size_t items = cnt * (M / 8);
+    if (int rc = stream_launch(in_stride % U == 0 ? mdct_fold_kernel<T, LOAD, true> : mdct_fold_kernel<T, LOAD, false>, items, st, in, in_stride, nframes,
+                               window, X, ta, v0, cnt, (unsigned)M))
+        return rc;
     if (int rc = transform_batch_any(s, X, X, cnt, PFFFT_FORWARD, 1, st)) return rc;
-    if (out_stride % U == 0)
-        hipLaunchKernelGGL((mdct_post_kernel<T, true>), dim3(grid), dim3(256), 0, st, (const T*)X, out, out_stride, static_cast<const cx<T>*>(tb.b),
-                           gain, cnt, (unsigned)M);
-    else
-        hipLaunchKernelGGL((mdct_post_kernel<T, false>), dim3(grid), dim3(256), 0, st, (const T*)X, out, out_stride, static_cast<const cx<T>*>(tb.b),
-                           gain, cnt, (unsigned)M);
-    PF_CHECK(hipGetLastError());
-    return 0;
+    return stream_launch(out_stride % U == 0 ? mdct_post_kernel<T, true> : mdct_post_kernel<T, false>, items, st, (const T*)X, out, out_stride, tbb, gain,
+                         cnt, (unsigned)M);
 }
 
 // the object that holds the inner setup's tables on the calling thread's device, and the handle's own tables there
@@ -159,10 +150,8 @@ static int mdct_dct4_batch(void* setup, const T* in, T* out, size_t rows, hipStr
     if (!in || !out) return bad("mdct: NULL in / out");
     if (((uintptr_t)in | (uintptr_t)out) & 15) return bad("mdct: in / out not aligned to 16 bytes");
     const size_t M = (size_t)z->M;
-    if (in != out) {   // the same rows in place, or rows that do not overlap
-        const uintptr_t i0 = (uintptr_t)in, o0 = (uintptr_t)out, len = rows * M * sizeof(T);
-        if (i0 < o0 + len && o0 < i0 + len) return bad("mdct: in and out overlap without being equal");
-    }
+    const size_t len = rows * M * sizeof(T);   // the same rows in place, or rows that do not overlap
+    if (in != out && ranges_overlap((uintptr_t)in, len, (uintptr_t)out, len)) return bad("mdct: in and out overlap without being equal");
     Setup* s = nullptr;
     MdctTabs tb;
     if (int rc = mdct_open<T>(z, st, &s, &tb)) return rc;
@@ -238,15 +227,8 @@ static int mdct_overlap_add_batch(void* setup, const T* coefs, size_t coefs_stri
         return mdct_composed_rows<T, MDCT_ROW>(z, s, coefs, coefs_stride, 0, nullptr, V, V, M, r0, cnt, (T)1, tb, st);
     };
     auto gather = [&](const T* V, size_t fbase, size_t fpitch, size_t fend, T* sig, size_t sig_stride, size_t nsig, size_t s0, size_t s1) {
-        const unsigned grid = stream_grid(nsig * (s1 - s0) / 4);
-        if (aligned16(sig) && sig_stride % U == 0)
-            hipLaunchKernelGGL((mdct_ola_kernel<T, true>), dim3(grid), dim3(256), 0, st, V, fbase, fpitch, fend, (unsigned)M, window, scaling, sig,
-                               sig_stride, nsig, s0, s1);
-        else
-            hipLaunchKernelGGL((mdct_ola_kernel<T, false>), dim3(grid), dim3(256), 0, st, V, fbase, fpitch, fend, (unsigned)M, window, scaling, sig,
-                               sig_stride, nsig, s0, s1);
-        PF_CHECK(hipGetLastError());
-        return 0;
+        return stream_launch(aligned16(sig) && sig_stride % U == 0 ? mdct_ola_kernel<T, true> : mdct_ola_kernel<T, false>, nsig * (s1 - s0) / 4, st, V,
+                             fbase, fpitch, fend, (unsigned)M, window, scaling, sig, sig_stride, nsig, s0, s1);
     };
     std::lock_guard<std::mutex> lk(z->scratch.mu);
     void* buf = nullptr;

@@ -1,8 +1,11 @@
-// The one host path of the entries that are COMPOSED on top of pf::Setup (frames_tu.hip, psd_tu.hip, csd_tu.hip, pfb_tu.hip, any_tu.hip,
-// zoom_tu.hip, dct_tu.hip, mdct_tu.hip): how much scratch one launch sequence may hold, how a batch walks through it, how a fused launch is
-// cut into slices, the frame-matrix routes of analysis and synthesis, the run walk of the averages, the lookup of the register-tiled
-// configuration a fused kernel must share with transform_batch, and the handle that owns an inner setup.  Every decision is written here once;
-// each unit keeps its validation texts, its route decision and its own typed kernel launches.  Every function is internal to its includer.
+// The one host path of the entries that are COMPOSED on top of pf::Setup (frames_tu.hip, psd_tu.hip, csd_tu.hip, pfb_tu.hip, dct_tu.hip,
+// mdct_tu.hip; through bluestein_host.h any_tu.hip, zoom_tu.hip, analytic_tu.hip, xcorr_tu.hip; through fft2d_host.h fft2_tu.hip,
+// rfft2_tu.hip): how much scratch one launch sequence may hold, how a batch walks through it, how a fused launch is cut into slices, the
+// overlap test of two address ranges, the selector rule of a fused / composed pair, the launch of an element-wise kernel, the frame-matrix
+// routes of analysis and synthesis, the run walk of the averages, the lookup of the register-tiled configuration a fused kernel must share
+// with transform_batch, and the handle that owns inner setups with their device test and typed public entries.  Every decision is written
+// here once; each unit keeps its validation texts, its measured defaults and the arguments of its kernels.  Every function is internal to
+// its includer.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -105,6 +108,22 @@ static_assert(avg_plan(ROW_SLICE + 1, 16, 8196, 16384, true).vstep == ROW_SLICE 
               avg_plan(10, (size_t)1 << 37, 4, 16384, true).vstep == 1, "a fused launch holds at most ROW_SLICE runs, and at least one group");
 static_assert(first_frame(3, 100, 4) == 96 && first_frame(4, 100, 4) == 100 && first_frame(7, 100, 4) == 196 && first_frame(5, 16, 1) == 80, "a group of 100: runs of 32, 32, 32, 4");
 
+// ------------------------------------------------------------------------------------------------ guards
+// Do the byte ranges [a, a + alen) and [b, b + blen) share a byte?  Each entry keeps its own guard (in != out, batch != 0) and text.
+constexpr bool ranges_overlap(uintptr_t a, size_t alen, uintptr_t b, size_t blen) { return a < b + blen && b < a + alen; }
+static_assert(!ranges_overlap(0, 64, 64, 64) && !ranges_overlap(64, 64, 0, 64), "touching ranges, either one first");
+static_assert(ranges_overlap(0, 65, 64, 64) && ranges_overlap(64, 64, 0, 65), "one byte of overlap, either one first");
+static_assert(ranges_overlap(0, 256, 64, 16) && ranges_overlap(64, 16, 0, 256), "one range inside the other");
+static_assert(!ranges_overlap(0, 16, 16, 256) && ranges_overlap(0, 17, 16, 256) && !ranges_overlap(272, 16, 16, 256) && ranges_overlap(271, 16, 16, 256),
+              "different lengths: each side ends by its own");
+
+// The selector rule of a fused / composed pair: composed where the kernel cannot run or the composed selector asks; else fused where the
+// fused selector asks or the unit's measured default (its *_fused_default table) says so.
+inline bool fused_selected(const AbSel& sel, AbValue composed, AbValue fused, bool fusable, bool by_default) {
+    if (!fusable || sel.is(composed)) return false;
+    return sel.is(fused) || by_default;
+}
+
 // ------------------------------------------------------------------------------------------------ shared launches
 inline int bad_in(const char* prefix, const char* what, hipError_t e = hipErrorInvalidValue) {
     return bad((std::string(prefix) + what).c_str(), e);
@@ -113,6 +132,13 @@ inline int bad_in(const char* prefix, const char* what, hipError_t e = hipErrorI
 // grid of a grid-stride kernel of 256 threads over `items`
 static unsigned stream_grid(size_t items) {
     return (unsigned)std::max<size_t>(1, std::min<size_t>((items + 255) / 256, (size_t)num_cus() * 16));
+}
+// ... and its launch on `st`; a site that picks between two instantiations of a kernel does so before it calls
+template <typename K, typename... Args>
+static int stream_launch(K kernel, size_t items, hipStream_t st, const Args&... args) {
+    hipLaunchKernelGGL(kernel, dim3(stream_grid(items)), dim3(256), 0, st, args...);
+    PF_CHECK(hipGetLastError());
+    return 0;
 }
 
 // `batch` rows through the buffer of `st` in `pool`, chunk_rows at a time: body(X, first row, rows) enqueues one chunk and returns 0 or
@@ -131,10 +157,7 @@ static int chunked_scratch(StreamScratch& pool, hipStream_t st, size_t batch, si
 template <typename T, int MODE>
 static int launch_rows(const T* src, size_t src_stride, T* dst, size_t dst_stride, size_t count, size_t row, hipStream_t st) {
     const size_t per = MODE == 0 ? row : MODE == 1 ? row / 2 + 1 : row / 2;
-    hipLaunchKernelGGL((frames_rows_kernel<T, MODE>), dim3(stream_grid(count * per)), dim3(256), 0, st, src, src_stride, dst, dst_stride,
-                       count, (unsigned)row);
-    PF_CHECK(hipGetLastError());
-    return 0;
+    return stream_launch(frames_rows_kernel<T, MODE>, count * per, st, src, src_stride, dst, dst_stride, count, (unsigned)row);
 }
 
 // dense spectra rows of X -> out: copied (ordered / internal) or as |X|^2 of a real / complex spectrum
@@ -149,14 +172,9 @@ template <typename T>
 static int launch_gather(const T* signal, size_t signal_stride, size_t nframes, size_t hop_s, size_t spp, const T* window, T* X, size_t v0,
                          size_t cnt, size_t row, hipStream_t st) {
     constexpr int U = 16 / (int)sizeof(T);
-    if (aligned16(signal) && signal_stride % U == 0 && hop_s % U == 0)
-        hipLaunchKernelGGL((frames_gather_kernel<T, U>), dim3(stream_grid(cnt * row / U)), dim3(256), 0, st, signal, signal_stride, nframes,
-                           hop_s, (int)spp, window, X, v0, cnt, (unsigned)row);
-    else
-        hipLaunchKernelGGL((frames_gather_kernel<T, 1>), dim3(stream_grid(cnt * row)), dim3(256), 0, st, signal, signal_stride, nframes,
-                           hop_s, (int)spp, window, X, v0, cnt, (unsigned)row);
-    PF_CHECK(hipGetLastError());
-    return 0;
+    const bool wide = aligned16(signal) && signal_stride % U == 0 && hop_s % U == 0;
+    return stream_launch(wide ? frames_gather_kernel<T, U> : frames_gather_kernel<T, 1>, wide ? cnt * row / U : cnt * row, st, signal, signal_stride,
+                         nframes, hop_s, (int)spp, window, X, v0, cnt, (unsigned)row);
 }
 
 // ------------------------------------------------------------------------------------------------ analysis (frames, pfb, psd)
@@ -258,7 +276,7 @@ static int synthesis_runs(Setup* s, const T* spectra, size_t spectra_stride, siz
 // The run walk of avg_plan.  Takes the partial buffer of `st` (Setup::psd, where rpg > 1) and then the frame matrix (Setup::frames, where
 // composed), always in this order, and hands the runs of each pass to fused(dst, dstride, first output row, runs, scale) or, in chunks, to
 // composed(X, first run, runs, first frame, frames, dst, dstride, scale): a run stores into `out` with the scaling (rpg == 1) or into its
-// partial row, which reduce(part, rows, out rows) sums after the pass.  The callables enqueue on `st`; the first two return 0 or an error.
+// partial row, which reduce(part, rows, out rows) sums after the pass.  The callables enqueue on `st` and return 0 or an error.
 // part_row, frame_row: the scalars behind the plan's two byte counts (a partial row; a frame row times the frame sets).
 template <typename T, class Fused, class Composed, class Reduce>
 static int averaged_runs(Setup* s, hipStream_t st, const AvgPlan& p, size_t part_row, size_t frame_row, T* out, size_t out_stride, T scaling,
@@ -285,13 +303,10 @@ static int averaged_runs(Setup* s, hipStream_t st, const AvgPlan& p, size_t part
             for (size_t r = ra; r < rb; r += p.crun) {
                 const size_t cnt = std::min(rb - r, p.crun), fa = first_frame(r, p.navg, rpg), nfr = first_frame(r + cnt, p.navg, rpg) - fa;
                 if (int rc = composed((T*)X, r, cnt, fa, nfr, dst + (r - ra) * dstride, dstride, scale)) return rc;
-                PF_CHECK(hipGetLastError());
             }
         }
-        if (rpg > 1) {
-            reduce((T*)part, rows, out + v0 * out_stride);
-            PF_CHECK(hipGetLastError());
-        }
+        if (rpg > 1)
+            if (int rc = reduce((T*)part, rows, out + v0 * out_stride)) return rc;
     }
     return 0;
 }
@@ -301,8 +316,8 @@ static int averaged_runs(Setup* s, hipStream_t st, const AvgPlan& p, size_t part
 template <class Fusable>
 static bool averaged_route_fused(const AbSel& sel, AbValue composed, AbValue fused, Fusable&& fusable, size_t hop, size_t stride_a, size_t stride_b,
                                  size_t navg, bool by_default) {
-    if (sel.is(composed) || !fusable() || hop % 4 || stride_a % 4 || stride_b % 4 || navg > 0xffffffffull) return false;
-    return sel.is(fused) || by_default;
+    if (hop % 4 || stride_a % 4 || stride_b % 4 || navg > 0xffffffffull) return false;
+    return fused_selected(sel, composed, fused, fusable(), by_default);
 }
 
 // the setup a `*_route` export answers for; NULL: it answers ""
@@ -339,28 +354,66 @@ static bool visit_tiled_cfg_complex(const Setup* s, const Route& r, Visit&& visi
 }
 
 // ------------------------------------------------------------------------------------------------ handles that own an inner setup
-// Base of the any-length, zoom, DCT and MDCT handles: the magic word first, the owned PFFFT_Setup / PFFFTD_Setup.  A handle type H names itself
-// in H::KIND for the refusal text.
+// Base of every derived handle: the magic word first, the owned PFFFT_Setup / PFFFTD_Setup objects.  `inner` is the first one (new_inner, which
+// fixes the precision); a handle that needs more asks add_inner and keeps the pointers it wants.  drop_inner destroys them all, in the
+// order they were created.  A handle type H names itself in H::KIND for the refusal text.
 template <uint32_t MAGIC_>
 struct InnerOwner {
     static constexpr uint32_t HANDLE_MAGIC = MAGIC_;
     uint32_t magic = MAGIC_;
     int is_double = 0;
     Setup* inner = nullptr;
+    std::vector<Setup*> owned;
     ~InnerOwner() { drop_inner(); }
+    Setup* add_inner(int len, int transform) {
+        Setup* s = is_double ? static_cast<Setup*>(pffftd_new_setup(len, (pffft_transform_t)transform))
+                             : static_cast<Setup*>(pffft_new_setup(len, (pffft_transform_t)transform));
+        if (s) owned.push_back(s);
+        return s;
+    }
     bool new_inner(int len, int transform, int dbl) {
         is_double = dbl;
-        inner = dbl ? static_cast<Setup*>(pffftd_new_setup(len, (pffft_transform_t)transform))
-                    : static_cast<Setup*>(pffft_new_setup(len, (pffft_transform_t)transform));
-        return inner != nullptr;
+        return (inner = add_inner(len, transform)) != nullptr;
     }
     void drop_inner() {
-        if (!inner) return;
-        if (is_double) pffftd_destroy_setup(static_cast<PFFFTD_Setup*>(inner));
-        else pffft_destroy_setup(static_cast<PFFFT_Setup*>(inner));
+        for (Setup* s : owned) {
+            if (is_double) pffftd_destroy_setup(static_cast<PFFFTD_Setup*>(s));
+            else pffft_destroy_setup(static_cast<PFFFT_Setup*>(s));
+        }
+        owned.clear();
         inner = nullptr;
     }
 };
+
+// `inner` with its tables on the calling thread's device, for a handle that serves one device: where for_device would answer with a
+// replica, the handle's own tables are on another device and the call is refused
+inline int inner_on_device(Setup* inner) {
+    if (for_device(inner) != inner) return bad("this setup holds its tables on another device", hipErrorInvalidDevice);
+    return ensure_device_any(inner);
+}
+
+// The PUBLIC entries on an inner setup of the scalar type T (they validate and resolve the device: transform_batch_any and its kin do not)
+template <typename T>
+static int inner_transform_batch(Setup* inner, const T* in, T* out, size_t batch, int dir, int ordered, hipStream_t st) {
+    if constexpr (sizeof(T) == 8)
+        return pffftd_hip_transform_batch(static_cast<PFFFTD_Setup*>(inner), in, out, batch, (pffft_direction_t)dir, ordered, st);
+    else
+        return pffft_hip_transform_batch(static_cast<PFFFT_Setup*>(inner), in, out, batch, (pffft_direction_t)dir, ordered, st);
+}
+template <typename T>
+static int inner_convolve_batch(Setup* inner, const T* in, const T* H, T* out, T scaling, size_t batch, hipStream_t st) {   // one H, no accumulation
+    if constexpr (sizeof(T) == 8)
+        return pffftd_hip_convolve_batch(static_cast<PFFFTD_Setup*>(inner), in, H, out, scaling, batch, 0, 1, st);
+    else
+        return pffft_hip_convolve_batch(static_cast<PFFFT_Setup*>(inner), in, H, out, scaling, batch, 0, 1, st);
+}
+template <typename T>
+static int inner_zreorder_batch(Setup* inner, const T* in, T* out, size_t batch, int dir, hipStream_t st) {
+    if constexpr (sizeof(T) == 8)
+        return pffftd_hip_zreorder_batch(static_cast<PFFFTD_Setup*>(inner), in, out, batch, (pffft_direction_t)dir, st);
+    else
+        return pffft_hip_zreorder_batch(static_cast<PFFFT_Setup*>(inner), in, out, batch, (pffft_direction_t)dir, st);
+}
 
 template <class H>
 static H* checked_handle(const void* p) {

@@ -1,6 +1,6 @@
 // The one host launch path of the persistent ("loop") kernels: resident workgroups pull groups of vectors in order from a {next, done}
 // counter pair, and short launches run one group per workgroup in hardware dispatch order instead.  Every launcher of such a kernel
-// takes its grid and its counters from here and keeps only its own typed hipLaunchKernelGGL line.  The tile passes, launch_one, the
+// takes its grid and its counters from here and keeps only its own typed hipLaunchKernelGGL line, or leaves that to loop_launch_last too.  The tile passes, launch_one, the
 // N = 1024 launchers, the compile-time path of launch_stock and the zreorder / zconvolve launches follow other rules and stay on their own.
 // Also here: the dispatchers from run-time (direction, layout) flags to the template arguments of a kernel.
 #pragma once
@@ -10,7 +10,8 @@
 
 namespace pf {
 
-// conv_tu.hip and bluestein_host.h (fft_conv_kernel): a constant, NOT env().oneshot - PFFFT_HIP_ONESHOT does not move these launches
+// The launch rule of the convolution kernel, followed by conv_tu.hip and bluestein_host.h (fft_conv_kernel), xcorr_tu.hip (fft_xcorr_kernel)
+// and fft2d_host.h (fft_fft2_kernel, fft_rfft2_kernel): a constant, NOT env().oneshot - PFFFT_HIP_ONESHOT does not move these launches
 // (tests/launch_shapes.py fused_long_batch mirrors it)
 constexpr int CONV_ONESHOT = 4;
 
@@ -56,6 +57,17 @@ static int loop_launch(Setup* s, hipStream_t st, K kernel, int threads, size_t l
     size_t resident = 0;
     if (int rc = loop_resident(kernel, threads, lds, &resident)) return rc;
     *ll = loop_take(s, st, resident, groups, oneshot);
+    return 0;
+}
+
+// ... and the launch itself, for a kernel whose counter pointer is its LAST parameter: `args` are the parameters before it.  A site whose
+// counters sit elsewhere, or that asks loop_resident once for several slices, keeps its own hipLaunchKernelGGL line.
+template <typename K, typename... Args>
+static int loop_launch_last(Setup* s, hipStream_t st, K kernel, int threads, size_t lds, size_t groups, int oneshot, const Args&... args) {
+    LoopLaunch ll;
+    if (int rc = loop_launch(s, st, kernel, threads, lds, groups, oneshot, &ll)) return rc;
+    hipLaunchKernelGGL(kernel, dim3(ll.grid), dim3(threads), lds, st, args..., ll.ctr);
+    PF_CHECK(hipGetLastError());
     return 0;
 }
 

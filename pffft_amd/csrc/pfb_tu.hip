@@ -112,10 +112,7 @@ static int launch_syn_form(bool xcd, const T* y, size_t fbase, size_t fpitch, si
     if (units == 0) return 0;
     const unsigned hop_mod = (unsigned)((hop * SPP) % (N * SPP));
     auto k = xcd ? pfb_syn_kernel<T, U, SPP, 1> : pfb_syn_kernel<T, U, SPP, 0>;
-    hipLaunchKernelGGL(k, dim3(stream_grid(units)), dim3(256), 0, st, y, fbase, fpitch, nframes, hop, (unsigned)N, span, hop_mod, g, scaling,
-                       signal, signal_stride, nsignals, s0, s1);
-    PF_CHECK(hipGetLastError());
-    return 0;
+    return stream_launch(k, units, st, y, fbase, fpitch, nframes, hop, (unsigned)N, span, hop_mod, g, scaling, signal, signal_stride, nsignals, s0, s1);
 }
 
 struct SynForm { bool wide, xcd; };

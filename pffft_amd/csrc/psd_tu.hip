@@ -80,14 +80,11 @@ static int psd_batch(Setup* s, const T* signal, size_t signal_stride, size_t nsi
             if ((rc = launch_gather<T>(signal, signal_stride, nframes, hop_s, spp, window, X, fa, nfr, row, st))) return rc;
             if ((rc = transform_batch_any(s, X, X, nfr, PFFFT_FORWARD, 1, st))) return rc;
             return with_flag(a.real, [&](auto R) {
-                hipLaunchKernelGGL((psd_runs_kernel<T, decltype(R)::value>), dim3(stream_grid(cnt * P)), dim3(256), 0, st, X, (unsigned)row, r, cnt,
-                                   navg, p.rpg, dst, dstride, scale);
-                return 0;
+                return stream_launch(psd_runs_kernel<T, decltype(R)::value>, cnt * P, st, X, (unsigned)row, r, cnt, navg, p.rpg, dst, dstride, scale);
             });
         },
         [&](T* part, size_t rows, T* out_rows) {
-            hipLaunchKernelGGL((psd_reduce_kernel<T>), dim3(stream_grid(rows * P)), dim3(256), 0, st, part, p.rpg, (unsigned)P, rows, scaling, out_rows,
-                               out_stride);
+            return stream_launch(psd_reduce_kernel<T>, rows * P, st, part, p.rpg, (unsigned)P, rows, scaling, out_rows, out_stride);
         });
 }
 

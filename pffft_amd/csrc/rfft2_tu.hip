@@ -6,7 +6,7 @@
 // Kernels: fft_rfft2.h.
 #include <memory>
 
-#include "pf_compose.h"
+#include "fft2d_host.h"
 #include "fft_rfft2.h"
 
 namespace pf {
@@ -24,13 +24,6 @@ struct Rfft2Setup : InnerOwner<RFFT2_MAGIC> {
     Setup* inner64 = nullptr;
     DeviceBinding bound;
     StreamScratch pad;             // the composed route's image: one per stream, pad.mu held while a call enqueues
-    ~Rfft2Setup() {
-        for (Setup* s : {inner_rows, inner64}) {
-            if (!s) continue;
-            if (is_double) pffftd_destroy_setup(static_cast<PFFFTD_Setup*>(s));
-            else pffft_destroy_setup(static_cast<PFFFT_Setup*>(s));
-        }
-    }
 };
 
 // ------------------------------------------------------------------------------------------------ plan
@@ -50,12 +43,7 @@ static bool rfft2_fused_default(int rows, int cols) {
 }
 
 static bool rfft2_fused_now(const Rfft2Setup* z, const AbSel& sel) {
-    if (!z->fusable || sel.is(AB_RFFT2_COMPOSED)) return false;
-    return sel.is(AB_RFFT2_FUSED) || rfft2_fused_default(z->rows, z->cols);
-}
-
-static Setup* rfft2_complex_setup(int len, int is_double) {
-    return is_double ? static_cast<Setup*>(pffftd_new_setup(len, PFFFT_COMPLEX)) : static_cast<Setup*>(pffft_new_setup(len, PFFFT_COMPLEX));
+    return fused_selected(sel, AB_RFFT2_COMPOSED, AB_RFFT2_FUSED, z->fusable, rfft2_fused_default(z->rows, z->cols));
 }
 
 static Rfft2Setup* rfft2_new_setup(int rows, int cols, int is_double) {
@@ -64,77 +52,32 @@ static Rfft2Setup* rfft2_new_setup(int rows, int cols, int is_double) {
     z->rows = rows; z->cols = cols;
     z->fusable = !is_double && rfft2_fused_shape(rows, cols);
     if (!z->new_inner(cols, PFFFT_REAL, is_double)) return nullptr;
-    if (!(z->inner_rows = rfft2_complex_setup(rows, is_double))) return nullptr;
+    if (!(z->inner_rows = z->add_inner(rows, PFFFT_COMPLEX))) return nullptr;
     if (z->fusable && cols == 64 && rows != 64)
-        if (!(z->inner64 = rfft2_complex_setup(64, is_double))) return nullptr;
+        if (!(z->inner64 = z->add_inner(64, PFFFT_COMPLEX))) return nullptr;
     return z.release();
 }
 
 // ------------------------------------------------------------------------------------------------ the routes
-template <int R, int C, int DIR>
-static int rfft2_fused_launch(Setup* s, const cx<float>* tw64, const float* in, float* out, size_t batch, float scaling, hipStream_t st) {
-    typedef Rfft2Cfg<R, C> Cf;
-    auto k = fft_rfft2_kernel<R, C, DIR, rfft2_pf<R, C, DIR>()>;
-    LoopLaunch ll;
-    if (int rc = loop_launch(s, st, k, Cf::WG, Cf::LDS_BYTES, (batch + Cf::SLOTS - 1) / Cf::SLOTS, CONV_ONESHOT, &ll)) return rc;
-    hipLaunchKernelGGL(k, dim3(ll.grid), dim3(Cf::WG), Cf::LDS_BYTES, st, in, out, (unsigned)batch, scaling, tw64, ll.ctr);
-    PF_CHECK(hipGetLastError());
-    return 0;
-}
-
-// the inner setup with its tables on the calling thread's device
-static int rfft2_inner_ready(Setup* inner) {
-    if (for_device(inner) != inner) {
-        g_last_error = "pffft_hip: this setup holds its tables on another device";
-        return (int)hipErrorInvalidDevice;
-    }
-    return ensure_device_any(inner);
-}
-
-// The counters come from the columns' inner setup; the W_64 values from the table W_64^j of whichever complex setup has length 64.  The
-// batch goes out in slices on the same stream (for_slices): the kernel counts images in 32 bits.
+// The counters come from the columns' inner setup; the W_64 values from the table W_64^j of whichever complex setup has length 64.
 static int rfft2_fused(Rfft2Setup* z, const float* in, float* out, size_t batch, int dir, float scaling, hipStream_t st) {
-    if (int rc = rfft2_inner_ready(z->inner_rows)) return rc;
+    if (int rc = inner_on_device(z->inner_rows)) return rc;
     if (z->inner64)
-        if (int rc = rfft2_inner_ready(z->inner64)) return rc;
+        if (int rc = inner_on_device(z->inner64)) return rc;
     Setup* s64 = z->rows == 64 ? z->inner_rows : z->inner64;
     const cx<float>* tw64 = s64 ? s64->d_tw.as<cx<float>>() : nullptr;
     const size_t real_image = (size_t)z->rows * z->cols, spec_image = (size_t)z->rows * (z->cols / 2 + 1) * 2;
     const bool back = dir == PFFFT_BACKWARD;
-    return for_slices(batch, [&](size_t b0, size_t nb) {
-        const float* pi = in + b0 * (back ? spec_image : real_image);
-        float* po = out + b0 * (back ? real_image : spec_image);
+    return fft2d_fused(in, back ? spec_image : real_image, out, back ? real_image : spec_image, batch, [&](const float* pi, float* po, size_t nb) {
         return with_one_of<16, 32, 64>(z->rows, [&](auto R) {
             return with_flag(z->cols == 64, [&](auto W) {
                 return with_flag(back, [&](auto D) {
-                    return rfft2_fused_launch<decltype(R)::value, decltype(W)::value ? 64 : 32, decltype(D)::value>(z->inner_rows, tw64, pi, po, nb,
-                                                                                                                   scaling, st);
+                    constexpr int r = decltype(R)::value, c = decltype(W)::value ? 64 : 32, d = decltype(D)::value;
+                    return fft2d_fused_launch<Rfft2Cfg<r, c>>(z->inner_rows, fft_rfft2_kernel<r, c, d, rfft2_pf<r, c, d>()>, tw64, pi, po, nb, scaling, st);
                 });
             });
         });
     });
-}
-
-template <typename T>
-static int rfft2_transform(Setup* inner, const T* in, T* out, size_t lines, int dir, hipStream_t st) {
-    if constexpr (sizeof(T) == 8)
-        return pffftd_hip_transform_batch(static_cast<PFFFTD_Setup*>(inner), in, out, lines, (pffft_direction_t)dir, 1, st);
-    else
-        return pffft_hip_transform_batch(static_cast<PFFFT_Setup*>(inner), in, out, lines, (pffft_direction_t)dir, 1, st);
-}
-
-static unsigned rfft2_tile_grid(size_t images, size_t a, size_t b) {
-    const size_t tiles = images * ((a + 31) / 32) * ((b + 31) / 32);
-    return (unsigned)std::max<size_t>(1, std::min<size_t>(tiles, (size_t)num_cus() * 32));
-}
-
-// [a][b] -> [b][a] per image with the transposing kernel of the complex 2-D entry
-template <typename T, int SCALE>
-static int rfft2_transpose(const cx<T>* src, cx<T>* dst, size_t images, size_t a, size_t b, T s, hipStream_t st) {
-    hipLaunchKernelGGL((fft2_transpose_kernel<T, SCALE>), dim3(rfft2_tile_grid(images, a, b)), dim3(256), 0, st, src, dst, images, (unsigned)a,
-                       (unsigned)b, s);
-    PF_CHECK(hipGetLastError());
-    return 0;
 }
 
 // One image of rows x bins complex values of the scratch per image of a chunk; `in` is read only.  Forward, the packed row spectra wait in
@@ -147,21 +90,18 @@ static int rfft2_composed(Rfft2Setup* z, const T* in, T* out, size_t batch, int 
         if (dir == PFFFT_FORWARD) {
             const T* src = in + v0 * R * C;
             T* dst = out + v0 * R * bins * 2;
-            if (int rc = rfft2_transform<T>(z->inner, src, dst, cnt * R, dir, st)) return rc;
-            hipLaunchKernelGGL((rfft2_unpack_kernel<T>), dim3(rfft2_tile_grid(cnt, R, bins)), dim3(256), 0, st,
-                               reinterpret_cast<const cx<T>*>(dst), X, cnt, (unsigned)R, (unsigned)H);
-            PF_CHECK(hipGetLastError());
-            if (int rc = rfft2_transform<T>(z->inner_rows, (const T*)X, (T*)X, cnt * bins, dir, st)) return rc;
-            return rfft2_transpose<T, 1>(X, reinterpret_cast<cx<T>*>(dst), cnt, bins, R, s, st);
+            if (int rc = inner_transform_batch<T>(z->inner, src, dst, cnt * R, dir, 1, st)) return rc;
+            if (int rc = fft2d_tile_launch(rfft2_unpack_kernel<T>, cnt, R, bins, st, reinterpret_cast<const cx<T>*>(dst), X, cnt, (unsigned)R, (unsigned)H))
+                return rc;
+            if (int rc = inner_transform_batch<T>(z->inner_rows, (const T*)X, (T*)X, cnt * bins, dir, 1, st)) return rc;
+            return fft2d_transpose<T, 1>(X, reinterpret_cast<cx<T>*>(dst), cnt, bins, R, s, st);
         }
         const T* src = in + v0 * R * bins * 2;
         T* dst = out + v0 * R * C;
-        if (int rc = rfft2_transpose<T, 0>(reinterpret_cast<const cx<T>*>(src), X, cnt, R, bins, (T)1, st)) return rc;
-        if (int rc = rfft2_transform<T>(z->inner_rows, (const T*)X, (T*)X, cnt * bins, dir, st)) return rc;
-        hipLaunchKernelGGL((rfft2_pack_kernel<T>), dim3(rfft2_tile_grid(cnt, H, R)), dim3(256), 0, st, X, reinterpret_cast<cx<T>*>(dst), cnt,
-                           (unsigned)R, (unsigned)H, s);
-        PF_CHECK(hipGetLastError());
-        return rfft2_transform<T>(z->inner, dst, dst, cnt * R, dir, st);
+        if (int rc = fft2d_transpose<T, 0>(reinterpret_cast<const cx<T>*>(src), X, cnt, R, bins, (T)1, st)) return rc;
+        if (int rc = inner_transform_batch<T>(z->inner_rows, (const T*)X, (T*)X, cnt * bins, dir, 1, st)) return rc;
+        if (int rc = fft2d_tile_launch(rfft2_pack_kernel<T>, cnt, H, R, st, X, reinterpret_cast<cx<T>*>(dst), cnt, (unsigned)R, (unsigned)H, s)) return rc;
+        return inner_transform_batch<T>(z->inner, dst, dst, cnt * R, dir, 1, st);
     });
 }
 
@@ -170,18 +110,13 @@ template <typename T>
 static int rfft2_batch(void* setup, const T* in, T* out, size_t batch, int dir, T scaling, hipStream_t st) {
     Rfft2Setup* z = typed_handle<Rfft2Setup, T>(setup);
     if (!z) return (int)hipErrorInvalidHandle;
-    if (dir != PFFFT_FORWARD && dir != PFFFT_BACKWARD) return bad("rfft2: unknown direction");
-    if (batch == 0) return 0;
-    if (!in || !out) return bad("rfft2: NULL in / out");
-    if (!aligned16(in) || !aligned16(out)) return bad("rfft2: in / out not aligned to 16 bytes");
-    {
-        const size_t real_bytes = batch * (size_t)z->rows * (size_t)z->cols * sizeof(T);
-        const size_t spec_bytes = batch * (size_t)z->rows * (size_t)(z->cols / 2 + 1) * 2 * sizeof(T);
-        const size_t in_bytes = dir == PFFFT_FORWARD ? real_bytes : spec_bytes, out_bytes = dir == PFFFT_FORWARD ? spec_bytes : real_bytes;
-        const uintptr_t i0 = (uintptr_t)in, o0 = (uintptr_t)out;
-        if (i0 < o0 + out_bytes && o0 < i0 + in_bytes) return bad("rfft2: out overlaps in (the two sides differ in size: there is no in-place form)");
-    }
-    if (int rc = bind_device_once(z->bound, "rfft2: ", st, [] { return 0; })) return rc;   // (no tables: nothing is built beyond the binding)
+    if (int rc = fft2d_args("rfft2: ", in, out, batch, dir)) return rc == ARGS_EMPTY ? 0 : rc;
+    const size_t real_bytes = batch * (size_t)z->rows * (size_t)z->cols * sizeof(T);
+    const size_t spec_bytes = batch * (size_t)z->rows * (size_t)(z->cols / 2 + 1) * 2 * sizeof(T);
+    const bool fwd = dir == PFFFT_FORWARD;
+    if (ranges_overlap((uintptr_t)in, fwd ? real_bytes : spec_bytes, (uintptr_t)out, fwd ? spec_bytes : real_bytes))
+        return bad("rfft2: out overlaps in (the two sides differ in size: there is no in-place form)");
+    if (int rc = fft2d_bind(z->bound, "rfft2: ", st)) return rc;
     if constexpr (sizeof(T) == 4) {
         if (rfft2_fused_now(z, ab())) return rfft2_fused(z, in, out, batch, dir, scaling, st);
     }

@@ -39,8 +39,7 @@ static bool xcorr_fused_default(int N, int real, int weight, int is_auto) {
 }
 
 static bool xcorr_fused_now(const XcorrSetup* z, int weight, int is_auto, const AbSel& sel) {
-    if (!z->fusable || sel.is(AB_XCORR_COMPOSED)) return false;
-    return sel.is(AB_XCORR_FUSED) || xcorr_fused_default(z->N, z->real, weight, is_auto);
+    return fused_selected(sel, AB_XCORR_COMPOSED, AB_XCORR_FUSED, z->fusable, xcorr_fused_default(z->N, z->real, weight, is_auto));
 }
 
 static XcorrSetup* xcorr_new_setup(int N, int real_rows, int len_x, int len_y, int lag0, int nlags, int is_double) {
@@ -57,12 +56,8 @@ static XcorrSetup* xcorr_new_setup(int N, int real_rows, int len_x, int len_y, i
 template <class C, int REAL, int AUTO>
 static int xcorr_fused_launch(Setup* s, const XcorrIO<C, REAL>& io, size_t batch, int weight, hipStream_t st) {
     auto k = fft_xcorr_kernel<C, XcorrIO<C, REAL>, AUTO, xcorr_xpf<C>(REAL != 0, AUTO != 0)>;
-    LoopLaunch ll;
-    if (int rc = loop_launch(s, st, k, C::WG_THREADS, C::LDS_BYTES, (batch + C::T_PER_WG - 1) / C::T_PER_WG, CONV_ONESHOT, &ll)) return rc;
     const cx<float>* tw = s->d_tw.as<cx<float>>();
-    hipLaunchKernelGGL(k, dim3(ll.grid), dim3(C::WG_THREADS), C::LDS_BYTES, st, io, (unsigned)batch, weight, tw, tw, ll.ctr);
-    PF_CHECK(hipGetLastError());
-    return 0;
+    return loop_launch_last(s, st, k, C::WG_THREADS, C::LDS_BYTES, (batch + C::T_PER_WG - 1) / C::T_PER_WG, CONV_ONESHOT, io, (unsigned)batch, weight, tw, tw);
 }
 
 template <int REAL, int AUTO>
@@ -76,14 +71,6 @@ static int xcorr_fused(XcorrSetup* z, const float* x, const float* y, float* out
     });
 }
 
-template <typename T>
-static int xcorr_transform(XcorrSetup* z, cx<T>* X, size_t rows, int dir, hipStream_t st) {
-    if constexpr (sizeof(T) == 8)
-        return pffftd_hip_transform_batch(static_cast<PFFFTD_Setup*>(z->inner), (const double*)X, (double*)X, rows, (pffft_direction_t)dir, 1, st);
-    else
-        return pffft_hip_transform_batch(static_cast<PFFFT_Setup*>(z->inner), (const float*)X, (float*)X, rows, (pffft_direction_t)dir, 1, st);
-}
-
 // Two N-point complex rows of the image per row pair (one for the autocorrelation), the cap holds for both together
 template <typename T, int REAL>
 static int xcorr_composed(XcorrSetup* z, const T* x, const T* y, T* out, size_t batch, int weight, bool is_auto, T s, hipStream_t st) {
@@ -91,17 +78,11 @@ static int xcorr_composed(XcorrSetup* z, const T* x, const T* y, T* out, size_t 
     const int sets = is_auto ? 1 : 2;
     return chunked_scratch<cx<T>>(z->pad, st, batch, (size_t)sets * N * sizeof(cx<T>), "the scratch image", [&](cx<T>* X, size_t v0, size_t cnt) {
         cx<T>* Y = is_auto ? X : X + cnt * N;   // (dense behind the x rows: ONE forward transform_batch over both)
-        hipLaunchKernelGGL((xcorr_pad_kernel<T, REAL>), dim3(stream_grid(cnt * N * sets)), dim3(256), 0, st, x + v0 * lx * spp, y + v0 * ly * spp, X,
-                           cnt, N, lx, ly, sets);
-        PF_CHECK(hipGetLastError());
-        if (int rc = xcorr_transform<T>(z, X, cnt * sets, PFFFT_FORWARD, st)) return rc;
-        hipLaunchKernelGGL((xcorr_product_kernel<T>), dim3(stream_grid(cnt * N)), dim3(256), 0, st, (const cx<T>*)X, Y, cnt * N, weight);
-        PF_CHECK(hipGetLastError());
-        if (int rc = xcorr_transform<T>(z, Y, cnt, PFFFT_BACKWARD, st)) return rc;
-        hipLaunchKernelGGL((xcorr_crop_kernel<T, REAL>), dim3(stream_grid(cnt * nl)), dim3(256), 0, st, (const cx<T>*)Y, out + v0 * nl * spp, cnt, N,
-                           (size_t)z->m0, nl, s);
-        PF_CHECK(hipGetLastError());
-        return 0;
+        if (int rc = stream_launch(xcorr_pad_kernel<T, REAL>, cnt * N * sets, st, x + v0 * lx * spp, y + v0 * ly * spp, X, cnt, N, lx, ly, sets)) return rc;
+        if (int rc = inner_transform_batch<T>(z->inner, (const T*)X, (T*)X, cnt * sets, PFFFT_FORWARD, 1, st)) return rc;
+        if (int rc = stream_launch(xcorr_product_kernel<T>, cnt * N, st, (const cx<T>*)X, Y, cnt * N, weight)) return rc;
+        if (int rc = inner_transform_batch<T>(z->inner, (const T*)Y, (T*)Y, cnt, PFFFT_BACKWARD, 1, st)) return rc;
+        return stream_launch(xcorr_crop_kernel<T, REAL>, cnt * nl, st, (const cx<T>*)Y, out + v0 * nl * spp, cnt, N, (size_t)z->m0, nl, s);
     });
 }
 
@@ -117,10 +98,10 @@ static int xcorr_batch(void* setup, const T* x, const T* y, T* out, size_t batch
     const size_t el = (z->real ? 1 : 2) * sizeof(T);
     if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)out) & (el - 1)) return bad("xcorr: x / y / out not aligned to one element");
     if (batch) {
-        const uintptr_t o0 = (uintptr_t)out, o1 = o0 + batch * (size_t)z->nlags * el;
-        const uintptr_t x0 = (uintptr_t)x, x1 = x0 + batch * (size_t)z->len_x * el;
-        const uintptr_t y0 = (uintptr_t)y, y1 = y0 + batch * (size_t)z->len_y * el;
-        if ((x0 < o1 && o0 < x1) || (y0 < o1 && o0 < y1)) return bad("xcorr: out overlaps x or y");
+        const uintptr_t o0 = (uintptr_t)out;
+        const size_t olen = batch * (size_t)z->nlags * el;
+        if (ranges_overlap((uintptr_t)x, batch * (size_t)z->len_x * el, o0, olen) || ranges_overlap((uintptr_t)y, batch * (size_t)z->len_y * el, o0, olen))
+            return bad("xcorr: out overlaps x or y");
     }
     int rc = bind_device_once(z->bound, "xcorr: ", st, [] { return 0; });   // (no tables: nothing is built beyond the binding)
     if (rc || batch == 0) return rc;

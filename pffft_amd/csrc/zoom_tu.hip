@@ -165,8 +165,7 @@ static ZoomSetup* zoom_new_setup(int N, int K, double f0, double df, int is_doub
 
 // the route of a call under the calling thread's selector
 static bool zoom_fused_now(const ZoomSetup* z, const AbSel& sel) {
-    if (!z->fusable || sel.is(AB_ZOOM_COMPOSED)) return false;
-    return sel.is(AB_ZOOM_FUSED) || zoom_fused_default(z->M);
+    return fused_selected(sel, AB_ZOOM_COMPOSED, AB_ZOOM_FUSED, z->fusable, zoom_fused_default(z->M));
 }
 
 // ------------------------------------------------------------------------------------------------ tables
@@ -213,16 +212,11 @@ static int zoom_composed(ZoomSetup* z, const T* in, T* out, size_t batch, int cj
     return bluestein_composed<T>(
         z->inner, z->pad, (const T*)z->d_H.as<T>(), M, batch, st,
         [&](cx<T>* X, size_t v0, size_t cnt) {
-            hipLaunchKernelGGL((zoom_pad_kernel<T>), dim3(stream_grid(cnt * M)), dim3(256), 0, st, reinterpret_cast<const cx<T>*>(in) + v0 * N, X,
-                               z->d_a.as<cx<T>>(), cnt, N, M, cj);
-            PF_CHECK(hipGetLastError());
-            return 0;
+            return stream_launch(zoom_pad_kernel<T>, cnt * M, st, reinterpret_cast<const cx<T>*>(in) + v0 * N, X, z->d_a.as<cx<T>>(), cnt, N, M, cj);
         },
         [&](cx<T>* X, size_t v0, size_t cnt) {
-            hipLaunchKernelGGL((zoom_crop_kernel<T>), dim3(stream_grid(cnt * K)), dim3(256), 0, st, (const cx<T>*)X,
-                               reinterpret_cast<cx<T>*>(out) + v0 * K, z->d_c.as<cx<T>>(), cnt, K, M, cj);
-            PF_CHECK(hipGetLastError());
-            return 0;
+            return stream_launch(zoom_crop_kernel<T>, cnt * K, st, (const cx<T>*)X, reinterpret_cast<cx<T>*>(out) + v0 * K, z->d_c.as<cx<T>>(), cnt, K, M,
+                                 cj);
         });
 }
 
@@ -234,12 +228,9 @@ static int zoom_transform_batch(void* setup, const T* in, T* out, size_t batch, 
     if (dir != PFFFT_FORWARD && dir != PFFFT_BACKWARD) return bad("zoom: bad direction");
     if (batch && (!in || !out)) return bad("zoom: NULL in / out");
     if (((uintptr_t)in | (uintptr_t)out) & (2 * sizeof(T) - 1)) return bad("zoom: in / out not aligned to one complex value");
-    if (batch) {
-        // rows of N in, rows of K out: the two must not overlap
-        const uintptr_t i0 = (uintptr_t)in, i1 = i0 + batch * (size_t)z->N * 2 * sizeof(T);
-        const uintptr_t o0 = (uintptr_t)out, o1 = o0 + batch * (size_t)z->K * 2 * sizeof(T);
-        if (i0 < o1 && o0 < i1) return bad("zoom: in and out overlap");
-    }
+    // rows of N in, rows of K out: the two must not overlap
+    if (batch && ranges_overlap((uintptr_t)in, batch * (size_t)z->N * 2 * sizeof(T), (uintptr_t)out, batch * (size_t)z->K * 2 * sizeof(T)))
+        return bad("zoom: in and out overlap");
     int rc = zoom_ensure<T>(z, st);
     if (rc || batch == 0) return rc;
     const int cj = dir == PFFFT_BACKWARD;
