@@ -789,7 +789,7 @@ const char *pffft_hip_xcorr_route(const void *setup, int weight, int is_auto);
  * hipErrorStreamCaptureUnsupported and launches nothing.
  * Real images with half-spectrum columns are the next entry (pffft[d]_hip_rfft2_*).  Strided or padded images, transforms along one axis
  * only, a fused double kernel, fused shapes beyond 64 and mixed-radix tiles, multi-device shards of one setup and 3-D transforms are not
- * offered. */
+ * offered.  Circular 2-D convolution / correlation of the images with a spectrum is pffft[d]_hip_fft2_convolve_batch below. */
 typedef struct PFFFT_HIP_Fft2Setup PFFFT_HIP_Fft2Setup;
 typedef struct PFFFTD_HIP_Fft2Setup PFFFTD_HIP_Fft2Setup;
 PFFFT_HIP_Fft2Setup *pffft_hip_fft2_new_setup(int rows, int cols);
@@ -802,6 +802,42 @@ int pffftd_hip_fft2_transform_batch(PFFFTD_HIP_Fft2Setup *, const double *in, do
                                     double scaling, void *stream);
 /* Host arithmetic only, handles of both precisions: "fused" / "composed" under the calling thread's selector; "" for an invalid handle. */
 const char *pffft_hip_fft2_route(const void *setup);
+
+/* ---- batched 2-D spectral convolution on the fft2 handle (numpy: ifft2(fft2(x) * G) of a batch of images)
+ *     out = scaling * IFFT2u( FFT2(in) . G ),   G = H where conj_h == 0, G = conj(H) otherwise
+ * FFT2 and IFFT2u are the forward and the UNNORMALISED backward transform of pffft[d]_hip_fft2_transform_batch: scaling = 1 / (rows * cols)
+ * gives numpy's ifft2(fft2(x) * G).  conj_h != 0 is the circular cross-correlation against the template whose spectrum is H.  Images are
+ * those of the fft2 entry (rows x cols interleaved complex values, dense, row-major, natural order); H is a spectrum in that same natural
+ * order, as fft2_transform_batch forward writes it: ONE image of it serves every image of the batch where h_broadcast != 0, `batch` images
+ * of it are read otherwise.  There is no accumulate form.  The product is a.x h.x - a.y h.y, a.x h.y + a.y h.x (conj_h: a.x h.x + a.y h.y,
+ * a.y h.x - a.x h.y), every product and sum rounded once, on every route; `scaling` is ONE product per stored component in the last kernel
+ * of either route: scaling == 1 changes no bit.
+ * in, H, out are device pointers, non-NULL for batch > 0, ALIGNED TO 16 BYTES.  in == out (in place) is legal on every route; any other
+ * overlap of in and out is refused, and so is H overlapping out.  `in` and H are never written (in: unless it is out).  batch == 0 returns 0.
+ * The call is asynchronous on `stream`; 0, else a hipError_t with its text in pffft_hip_last_error() (it opens with "fft2 convolve: ").
+ * Validation happens before any device is touched, in this order: the handle (hipErrorInvalidHandle: NULL, foreign, the other
+ * precision's), the empty call, NULL pointers, alignment, the two overlap rules (hipErrorInvalidValue) -> nothing launched.
+ * Routes (pffft_hip_fft2_convolve_route names the one a call takes under the calling thread's selector):
+ *   "fused"     float, h_broadcast != 0, rows and cols out of 16 / 32 / 64: ONE kernel, one HBM read and one HBM write per image.  The image
+ *               stays in LDS between the transforms: row pass forward, a column step that transforms a column forward, multiplies by G and
+ *               transforms it backward in registers (64 points: through the transposed 8 x 8 network, digit-reversed in, natural out), row
+ *               pass backward, 16-byte stores from natural positions.  G sits in registers across a workgroup's images.  Which shapes run
+ *               it by default is a measured table; pffft_hip_set_variant(153) runs it wherever it is legal, 152 never.
+ *   "composed"  every setup, either h_broadcast: the handle's own forward transform from in into out with scaling 1, a product kernel in
+ *               place in out, the handle's own backward transform in place in out with `scaling` - the transforms on whichever route
+ *               pffft_hip_fft2_route names under the calling thread's selector.  It equals those three steps made by hand bit for bit and
+ *               has no scratch of its own; what the inner transforms need (their scratch image, its capture rule) follows their rules.
+ * The two routes agree at the accuracy bar of a convolution of rows * cols points, not bit for bit.
+ * Device binding, first call and capture are the handle's (above): ONE device per setup, THE FIRST CALL ON A SETUP BINDS IT - make it
+ * before a stream capture.
+ * An accumulate form, real images, linear (zero-padded) convolution and cropping, two images that both change per call, a fused per-image
+ * H or double kernel and shapes beyond 64 are not offered. */
+int pffft_hip_fft2_convolve_batch(PFFFT_HIP_Fft2Setup *, const float *in, const float *H, float *out, float scaling, size_t batch, int conj_h,
+                                  int h_broadcast, void *stream);
+int pffftd_hip_fft2_convolve_batch(PFFFTD_HIP_Fft2Setup *, const double *in, const double *H, double *out, double scaling, size_t batch,
+                                   int conj_h, int h_broadcast, void *stream);
+/* Host arithmetic only, handles of both precisions: "fused" / "composed" under the calling thread's selector; "" for an invalid handle. */
+const char *pffft_hip_fft2_convolve_route(const void *setup, int h_broadcast);
 
 /* ---- batched 2-D real transforms (numpy.fft.rfft2 / irfft2 of a batch of images)
  * pffft[d]_hip_rfft2_new_setup(rows, cols): rows must be a length a COMPLEX setup of that precision takes, cols one a REAL setup takes

@@ -130,6 +130,8 @@ def lib():
         g("hip_fft2_destroy_setup").restype = None; g("hip_fft2_destroy_setup").argtypes = [C.c_void_p]
         g("hip_fft2_transform_batch").restype = C.c_int
         g("hip_fft2_transform_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, ct, C.c_void_p]
+        g("hip_fft2_convolve_batch").restype = C.c_int
+        g("hip_fft2_convolve_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, ct, C.c_size_t, C.c_int, C.c_int, C.c_void_p]
         g("hip_rfft2_new_setup").restype = C.c_void_p; g("hip_rfft2_new_setup").argtypes = [C.c_int, C.c_int]
         g("hip_rfft2_destroy_setup").restype = None; g("hip_rfft2_destroy_setup").argtypes = [C.c_void_p]
         g("hip_rfft2_transform_batch").restype = C.c_int
@@ -180,6 +182,7 @@ def lib():
     L.pffft_hip_analytic_table.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
     L.pffft_hip_xcorr_route.restype = C.c_char_p; L.pffft_hip_xcorr_route.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.pffft_hip_fft2_route.restype = C.c_char_p; L.pffft_hip_fft2_route.argtypes = [C.c_void_p]
+    L.pffft_hip_fft2_convolve_route.restype = C.c_char_p; L.pffft_hip_fft2_convolve_route.argtypes = [C.c_void_p, C.c_int]
     L.pffft_hip_rfft2_route.restype = C.c_char_p; L.pffft_hip_rfft2_route.argtypes = [C.c_void_p]
     L.pffft_hip_kernel_name.restype = C.c_char_p; L.pffft_hip_kernel_name.argtypes = [C.c_void_p]
     L.pffft_hip_describe.restype = C.c_int; L.pffft_hip_describe.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
@@ -956,6 +959,27 @@ class Fft2Setup(_Handle):
         assert self._whole_rows(out, self.image_scalars) == batch, "x and out hold different numbers of images"
         _check(self._fn("hip_fft2_transform_batch")(self.handle, x.data_ptr(), out.data_ptr(), batch, int(d), float(scaling), self._stream()),
                "hip_fft2_transform_batch")
+        return out
+
+    def convolve_route(self, h_broadcast=True) -> str:
+        """pffft_hip_fft2_convolve_route: "fused" / "composed" under the calling thread's selector.  Host arithmetic only."""
+        return self._L.pffft_hip_fft2_convolve_route(self.handle, int(bool(h_broadcast))).decode()
+
+    def convolve_batch(self, x, H, out=None, scaling=1.0, conj_h=False):
+        """out = scaling * IFFT2u(FFT2(x) . G), G = H or conj(H) (conj_h), IFFT2u the unnormalised backward transform: scaling =
+        1 / (rows cols) is numpy's ifft2(fft2(x) * G).  x, out as in transform_batch (out may be x).  H: contiguous CUDA tensor of the
+        setup's dtype holding a spectrum in natural order, ONE image of it (broadcast over the batch) or as many images as x; any other
+        size raises ValueError."""
+        import torch
+        batch = self._whole_rows(x, self.image_scalars)
+        images = self._whole_rows(H, self.image_scalars)
+        if images != 1 and images != batch:
+            raise ValueError(f"H holds {images} images: it must hold 1 (broadcast) or as many as x ({batch})")
+        if out is None:
+            out = torch.empty_like(x)
+        assert self._whole_rows(out, self.image_scalars) == batch, "x and out hold different numbers of images"
+        _check(self._fn("hip_fft2_convolve_batch")(self.handle, x.data_ptr(), H.data_ptr(), out.data_ptr(), float(scaling), batch,
+                                                   int(bool(conj_h)), int(images == 1), self._stream()), "hip_fft2_convolve_batch")
         return out
 
 

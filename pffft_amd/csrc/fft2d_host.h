@@ -51,5 +51,12 @@ template <class Cf, typename K>
 static int fft2d_fused_launch(Setup* s, K kernel, const cx<float>* tw64, const float* in, float* out, size_t batch, float scaling, hipStream_t st) {
     return loop_launch_last(s, st, kernel, Cf::WG, Cf::LDS_BYTES, (batch + Cf::SLOTS - 1) / Cf::SLOTS, CONV_ONESHOT, in, out, (unsigned)batch, scaling, tw64);
 }
+// ... its sibling for the spectral convolution kernel (fft_fft2c.h), which also takes the spectrum H and conj_h
+template <class Cf, typename K>
+static int fft2d_fused_conv_launch(Setup* s, K kernel, const cx<float>* tw64, const float* in, const cx<float>* H, float* out, size_t batch,
+                                   float scaling, int conj_h, hipStream_t st) {
+    return loop_launch_last(s, st, kernel, Cf::WG, Cf::LDS_BYTES, (batch + Cf::SLOTS - 1) / Cf::SLOTS, CONV_ONESHOT, in, H, out, (unsigned)batch, scaling,
+                            conj_h, tw64);
+}
 
 }  // namespace pf

@@ -36,7 +36,8 @@
 // elements of ONE row: two lanes per bank pair), the row passes of a thread group that spans 8 rows x 4 j (16 x 64, 32 x 64), and the
 // digit-reversed reads of the store.  No access is worse than 2-way.
 //
-// Real input with half-spectrum columns is fft_rfft2.h (pffft[d]_hip_rfft2_*).  Out of scope: strided or padded images, transforms along one axis only, a fused double
+// Real input with half-spectrum columns is fft_rfft2.h (pffft[d]_hip_rfft2_*); forward x spectrum x backward in one kernel is fft_fft2c.h
+// (pffft[d]_hip_fft2_convolve_batch).  Out of scope: strided or padded images, transforms along one axis only, a fused double
 // kernel, fused shapes beyond 64 (128 x 128 = 128 KiB is one image per CU) and mixed-radix tiles, multi-device shards of one setup, 3-D.
 #pragma once
 #include "cxmath.h"

@@ -93,6 +93,8 @@ enum AbValue : int {
     AB_FFT2_FUSED = 149,        // ... the fused LDS-resident 2-D kernel wherever it is legal, whatever the measured default of the shape is
     AB_RFFT2_COMPOSED = 150,    // pffft_hip_rfft2_transform_batch: never the fused kernel (real transform_batch + unpacking kernel + transform_batch + transposing kernel)
     AB_RFFT2_FUSED = 151,       // ... the fused LDS-resident 2-D real kernel wherever it is legal, whatever the measured default of the shape is
+    AB_FFT2CONV_COMPOSED = 152, // pffft_hip_fft2_convolve_batch: never the fused kernel (the handle's forward transform + product kernel + its backward transform)
+    AB_FFT2CONV_FUSED = 153,    // ... the fused LDS-resident 2-D convolution kernel wherever it is legal (float, one broadcast H), whatever the measured default of the shape is
     AB_FAKE_DEVICE = 130,    // the calling thread counts as being on ANOTHER device than its current one (key + 64): exercises the per-device
                                 // replicas of a shared setup on a box with one GPU (tests/test_gpu_round6.py)
 };
