@@ -830,8 +830,9 @@ const char *pffft_hip_fft2_route(const void *setup);
  * The two routes agree at the accuracy bar of a convolution of rows * cols points, not bit for bit.
  * Device binding, first call and capture are the handle's (above): ONE device per setup, THE FIRST CALL ON A SETUP BINDS IT - make it
  * before a stream capture.
- * An accumulate form, real images, linear (zero-padded) convolution and cropping, two images that both change per call, a fused per-image
- * H or double kernel and shapes beyond 64 are not offered. */
+ * Real images are pffft[d]_hip_rfft2_convolve_batch on the rfft2 handle (below): half the bytes and half the arithmetic.  An accumulate
+ * form, linear (zero-padded) convolution and cropping, two images that both change per call, a fused per-image H or double kernel and
+ * shapes beyond 64 are not offered. */
 int pffft_hip_fft2_convolve_batch(PFFFT_HIP_Fft2Setup *, const float *in, const float *H, float *out, float scaling, size_t batch, int conj_h,
                                   int h_broadcast, void *stream);
 int pffftd_hip_fft2_convolve_batch(PFFFTD_HIP_Fft2Setup *, const double *in, const double *H, double *out, double scaling, size_t batch,
@@ -893,6 +894,52 @@ int pffftd_hip_rfft2_transform_batch(PFFFTD_HIP_Rfft2Setup *, const double *in, 
                                      double scaling, void *stream);
 /* Host arithmetic only, handles of both precisions: "fused" / "composed" under the calling thread's selector; "" for an invalid handle. */
 const char *pffft_hip_rfft2_route(const void *setup);
+
+/* ---- batched 2-D spectral convolution of real images on the rfft2 handle (numpy: irfft2(rfft2(x) * G, s = (rows, cols)) of a batch)
+ *     out = scaling * rows * cols * numpy.fft.irfft2( numpy.fft.rfft2(in) . G, s = (rows, cols) ),   G = H where conj_h == 0, else conj(H)
+ * in and out are `batch` dense row-major images of rows x cols reals, as the rfft2 entry takes them; H is a half-spectrum of rows x bins
+ * interleaved complex values (bins = cols / 2 + 1) in natural order, as rfft2_transform_batch forward writes it: ONE of it serves every
+ * image of the batch where h_broadcast != 0, `batch` of them are read otherwise.  scaling = 1 / (rows * cols) gives numpy's
+ * irfft2(rfft2(x) * G); conj_h != 0 is the circular cross-correlation against the real template whose half-spectrum is H.  There is no
+ * accumulate form.
+ * H NEED NOT BE HERMITIAN in the columns 0 and cols / 2: the result is what numpy's irfft2 makes of the product - only the Hermitian part
+ * (Y[u] + conj Y[rows - u]) / 2 along u of those two product columns counts (the backward rule of the rfft2 entry).  Every route obeys it.
+ * The product is a.x h.x - a.y h.y, a.x h.y + a.y h.x (conj_h: a.x h.x + a.y h.y, a.y h.x - a.x h.y), every product and sum rounded
+ * once, on every route.  `scaling` follows the backward transform's rule above: ONE product per stored component, scaling == 1 changes
+ * no bit; in the store of the fused kernel, and on the composed route where the backward transform of the handle applies it (composed
+ * inner transform: ahead of its last transform_batch, so there a power of two reproduces the product of the unscaled result bit for bit,
+ * any other factor to rounding).
+ * in, H, out are device pointers, non-NULL for batch > 0, ALIGNED TO 16 BYTES.  The two sides have the same size, so in == out (in place)
+ * is legal on every route; any other overlap of in and out is refused, and so is H (one half-spectrum where it is broadcast, `batch` of
+ * them otherwise) overlapping out.  `in` and H are never written (in: unless it is out).  batch == 0 returns 0.  The call is asynchronous
+ * on `stream`; 0, else a hipError_t with its text in pffft_hip_last_error() (it opens with "rfft2 convolve: ").  Validation happens before
+ * any device is touched, in this order: the handle (hipErrorInvalidHandle: NULL, foreign, the other precision's), the empty call, NULL
+ * pointers, alignment, the two overlap rules (hipErrorInvalidValue) -> nothing launched.
+ * Routes (pffft_hip_rfft2_convolve_route names the one a call takes under the calling thread's selector):
+ *   "fused"     float, h_broadcast != 0, the six fused shapes of the rfft2 entry (rows 16 / 32 / 64, cols 32 / 64): ONE kernel, one HBM read
+ *               and one HBM write of 4 rows cols bytes per image.  The image stays in LDS: the real-side load, a row pass over rows / 2
+ *               lines, the untangling step, a column step that transforms a column forward, multiplies by G and transforms it backward
+ *               (64 rows: through the transposed 8 x 8 network), the rebuilding step, the backward row pass, the real-side store.  The
+ *               columns 0 and cols / 2 travel as one packed column, whose product takes the Hermitian parts named above.  Which shapes run
+ *               it by default is a measured table; pffft_hip_set_variant(155) runs it wherever it is legal, 154 never.
+ *   "composed"  every setup, either h_broadcast.  Per chunk of whole images through a second per-stream scratch of the handle, which holds
+ *               the half-spectra (at most 256 MiB; longer batches go through it in chunks on the stream): the handle's own forward
+ *               transform from in into the scratch with scaling 1, a product kernel in place there, the handle's own backward transform
+ *               into out with `scaling` - the transforms on whichever route pffft_hip_rfft2_route names under the calling thread's
+ *               selector.  It equals those three calls made by hand bit for bit.  A call that would have to grow either scratch (this one,
+ *               or the scratch image of a composed inner transform) on a capturing stream returns hipErrorStreamCaptureUnsupported before
+ *               anything is launched: run the call once on the stream before capturing.
+ * The two routes agree at the accuracy bar of a convolution of rows * cols points, not bit for bit.
+ * Device binding, first call and capture are the handle's (above): ONE device per setup, THE FIRST CALL ON A SETUP BINDS IT - make it
+ * before a stream capture.
+ * An accumulate form, linear (zero-padded) convolution and valid-region cropping, two images that both change per call (2-D correlation
+ * of image pairs, PHAT), a fused per-image H or double kernel, cols = 16, shapes beyond 64 and strided images are not offered. */
+int pffft_hip_rfft2_convolve_batch(PFFFT_HIP_Rfft2Setup *, const float *in, const float *H, float *out, float scaling, size_t batch, int conj_h,
+                                   int h_broadcast, void *stream);
+int pffftd_hip_rfft2_convolve_batch(PFFFTD_HIP_Rfft2Setup *, const double *in, const double *H, double *out, double scaling, size_t batch,
+                                    int conj_h, int h_broadcast, void *stream);
+/* Host arithmetic only, handles of both precisions: "fused" / "composed" under the calling thread's selector; "" for an invalid handle. */
+const char *pffft_hip_rfft2_convolve_route(const void *setup, int h_broadcast);
 
 /* Overlap-save FIR on device-resident signal/output (same block schedule as pffastconv_apply,
  * src/pffastconv.c:204-261): returns the number of output samples written, or -1 on error. */

@@ -136,6 +136,8 @@ def lib():
         g("hip_rfft2_destroy_setup").restype = None; g("hip_rfft2_destroy_setup").argtypes = [C.c_void_p]
         g("hip_rfft2_transform_batch").restype = C.c_int
         g("hip_rfft2_transform_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, ct, C.c_void_p]
+        g("hip_rfft2_convolve_batch").restype = C.c_int
+        g("hip_rfft2_convolve_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, ct, C.c_size_t, C.c_int, C.c_int, C.c_void_p]
         getattr(L, f"validate_{pfx}_simd").restype = C.c_int
         getattr(L, f"validate_{pfx}_simd_ex").restype = C.c_int
         getattr(L, f"validate_{pfx}_simd_ex").argtypes = [C.c_void_p]
@@ -184,6 +186,7 @@ def lib():
     L.pffft_hip_fft2_route.restype = C.c_char_p; L.pffft_hip_fft2_route.argtypes = [C.c_void_p]
     L.pffft_hip_fft2_convolve_route.restype = C.c_char_p; L.pffft_hip_fft2_convolve_route.argtypes = [C.c_void_p, C.c_int]
     L.pffft_hip_rfft2_route.restype = C.c_char_p; L.pffft_hip_rfft2_route.argtypes = [C.c_void_p]
+    L.pffft_hip_rfft2_convolve_route.restype = C.c_char_p; L.pffft_hip_rfft2_convolve_route.argtypes = [C.c_void_p, C.c_int]
     L.pffft_hip_kernel_name.restype = C.c_char_p; L.pffft_hip_kernel_name.argtypes = [C.c_void_p]
     L.pffft_hip_describe.restype = C.c_int; L.pffft_hip_describe.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.pffft_hip_route_occupancy.restype = C.c_int; L.pffft_hip_route_occupancy.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -1014,6 +1017,28 @@ class Rfft2Setup(_Handle):
         assert self._whole_rows(out, row_out) == batch, "x and out hold different numbers of images"
         _check(self._fn("hip_rfft2_transform_batch")(self.handle, x.data_ptr(), out.data_ptr(), batch, int(d), float(scaling), self._stream()),
                "hip_rfft2_transform_batch")
+        return out
+
+    def convolve_route(self, h_broadcast=True) -> str:
+        """pffft_hip_rfft2_convolve_route: "fused" / "composed" under the calling thread's selector.  Host arithmetic only."""
+        return self._L.pffft_hip_rfft2_convolve_route(self.handle, int(bool(h_broadcast))).decode()
+
+    def convolve_batch(self, x, H, out=None, scaling=1.0, conj_h=False):
+        """out = scaling * rows * cols * irfft2(rfft2(x) . G), G = H or conj(H) (conj_h): scaling = 1 / (rows cols) is numpy's
+        irfft2(rfft2(x) * G, s=(rows, cols)).  x: contiguous CUDA tensor of the setup's dtype holding whole real images (image_scalars
+        each); out: None (a new tensor shaped like x), another such tensor, or x itself (in place).  H: contiguous CUDA tensor of the
+        setup's dtype holding half-spectra in natural order (spectrum_scalars each, as transform_batch forward writes them), ONE of them
+        (broadcast over the batch) or as many as x holds images; any other size raises ValueError."""
+        import torch
+        batch = self._whole_rows(x, self.image_scalars)
+        images = self._whole_rows(H, self.spectrum_scalars)
+        if images != 1 and images != batch:
+            raise ValueError(f"H holds {images} half-spectra: it must hold 1 (broadcast) or as many as x ({batch})")
+        if out is None:
+            out = torch.empty_like(x)
+        assert self._whole_rows(out, self.image_scalars) == batch, "x and out hold different numbers of images"
+        _check(self._fn("hip_rfft2_convolve_batch")(self.handle, x.data_ptr(), H.data_ptr(), out.data_ptr(), float(scaling), batch,
+                                                    int(bool(conj_h)), int(images == 1), self._stream()), "hip_rfft2_convolve_batch")
         return out
 
 

@@ -145,14 +145,20 @@ static int fft2conv_fused(Fft2Setup* z, const float* in, const float* H, float* 
     });
 }
 
+template <typename T>
+int fft2conv_product(cx<T>* X, const cx<T>* H, size_t total, size_t himage, int conj_h, hipStream_t st) {
+    return stream_launch(fft2conv_product_kernel<T>, total, st, X, H, total, himage, conj_h);
+}
+template int fft2conv_product<float>(cx<float>*, const cx<float>*, size_t, size_t, int, hipStream_t);
+template int fft2conv_product<double>(cx<double>*, const cx<double>*, size_t, size_t, int, hipStream_t);
+
 // The handle's own forward transform from in into out, the product in place there, the handle's own backward transform in place with the
 // scaling: the transforms take whichever route pffft_hip_fft2_route names under the calling thread's selector.  No scratch of its own.
 template <typename T>
 static int fft2conv_composed(Fft2Setup* z, const T* in, const T* H, T* out, T scaling, size_t batch, int conj_h, int h_broadcast, hipStream_t st) {
     const size_t plane = (size_t)z->rows * (size_t)z->cols, total = batch * plane;
     if (int rc = fft2_run<T>(z, in, out, batch, PFFFT_FORWARD, (T)1, st)) return rc;
-    if (int rc = stream_launch(fft2conv_product_kernel<T>, total, st, reinterpret_cast<cx<T>*>(out), reinterpret_cast<const cx<T>*>(H), total,
-                               h_broadcast ? plane : total, conj_h))
+    if (int rc = fft2conv_product<T>(reinterpret_cast<cx<T>*>(out), reinterpret_cast<const cx<T>*>(H), total, h_broadcast ? plane : total, conj_h, st))
         return rc;
     return fft2_run<T>(z, out, out, batch, PFFFT_BACKWARD, scaling, st);
 }

@@ -59,4 +59,9 @@ static int fft2d_fused_conv_launch(Setup* s, K kernel, const cx<float>* tw64, co
                             conj_h, tw64);
 }
 
+// The product kernel of the composed convolutions (fft_fft2c.h fft2conv_product_kernel): X[i] = X[i] . G[i mod himage] in place on `st`.
+// Defined and instantiated for float and double in fft2_tu.hip, so that the library holds the kernel once; rfft2_tu.hip calls it too.
+template <typename T>
+int fft2conv_product(cx<T>* X, const cx<T>* H, size_t total, size_t himage, int conj_h, hipStream_t st);
+
 }  // namespace pf

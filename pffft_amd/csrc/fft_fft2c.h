@@ -36,7 +36,8 @@
 // half passes in the other order, the in-register column step those of the column pass, the store reads what the load wrote.  No access
 // is worse than 2-way.
 //
-// Out of scope: an accumulate form, real images, linear (zero-padded) convolution and cropping, two images that both change per call,
+// Real images are fft_rfft2c.h (pffft[d]_hip_rfft2_convolve_batch), which reuses fft2conv_mul, fft2conv_product_kernel and fft2_half_t2.
+// Out of scope: an accumulate form, linear (zero-padded) convolution and cropping, two images that both change per call,
 // a fused per-image-H path, fused double, shapes beyond 64.
 #pragma once
 #include "fft_fft2.h"

@@ -95,7 +95,9 @@ enum AbValue : int {
     AB_RFFT2_FUSED = 151,       // ... the fused LDS-resident 2-D real kernel wherever it is legal, whatever the measured default of the shape is
     AB_FFT2CONV_COMPOSED = 152, // pffft_hip_fft2_convolve_batch: never the fused kernel (the handle's forward transform + product kernel + its backward transform)
     AB_FFT2CONV_FUSED = 153,    // ... the fused LDS-resident 2-D convolution kernel wherever it is legal (float, one broadcast H), whatever the measured default of the shape is
-    AB_FAKE_DEVICE = 130,    // the calling thread counts as being on ANOTHER device than its current one (key + 64): exercises the per-device
+    AB_RFFT2CONV_COMPOSED = 154, // pffft_hip_rfft2_convolve_batch: never the fused kernel (the handle's forward transform + product kernel + its backward transform)
+    AB_RFFT2CONV_FUSED = 155,   // ... the fused LDS-resident 2-D real convolution kernel wherever it is legal (float, one broadcast H), whatever the measured default of the shape is
+    AB_FAKE_DEVICE = 130,   // the calling thread counts as being on ANOTHER device than its current one (key + 64): exercises the per-device
                                 // replicas of a shared setup on a box with one GPU (tests/test_gpu_round6.py)
 };
 struct AbSel {

@@ -3,11 +3,13 @@
 // a complex one of length rows and no tables; the fused kernel's launch (one kernel per call, float, rows 16 / 32 / 64, cols 32 / 64) and
 // the composed route (ordered real transform_batch over the rows, an unpacking + transposing kernel into a chunked scratch image,
 // transform_batch over the columns, the transposing kernel of fft_fft2.h back, times the scaling; backward the mirror).
-// Kernels: fft_rfft2.h.
+// Kernels: fft_rfft2.h.  On the same handle the spectral convolution of real images out = s rows cols irfft2(rfft2(in) . G)
+// (pffft[d]_hip_rfft2_convolve_batch): its fused kernel's launch and the composed route on the handle's own transforms around the product
+// kernel of fft_fft2c.h, through a second scratch for the half-spectra.  Kernels: fft_rfft2c.h.
 #include <memory>
 
 #include "fft2d_host.h"
-#include "fft_rfft2.h"
+#include "fft_rfft2c.h"
 
 namespace pf {
 
@@ -24,6 +26,7 @@ struct Rfft2Setup : InnerOwner<RFFT2_MAGIC> {
     Setup* inner64 = nullptr;
     DeviceBinding bound;
     StreamScratch pad;             // the composed route's image: one per stream, pad.mu held while a call enqueues
+    StreamScratch spec;            // the composed convolution's half-spectra: one per stream, spec.mu held (outside pad.mu) while a call enqueues
 };
 
 // ------------------------------------------------------------------------------------------------ plan
@@ -106,6 +109,15 @@ static int rfft2_composed(Rfft2Setup* z, const T* in, T* out, size_t batch, int 
 }
 
 // ------------------------------------------------------------------------------------------------ the entry
+// a validated call on a bound handle: the route of the calling thread's selector
+template <typename T>
+static int rfft2_run(Rfft2Setup* z, const T* in, T* out, size_t batch, int dir, T scaling, hipStream_t st) {
+    if constexpr (sizeof(T) == 4) {
+        if (rfft2_fused_now(z, ab())) return rfft2_fused(z, in, out, batch, dir, scaling, st);
+    }
+    return rfft2_composed<T>(z, in, out, batch, dir, scaling, st);
+}
+
 template <typename T>
 static int rfft2_batch(void* setup, const T* in, T* out, size_t batch, int dir, T scaling, hipStream_t st) {
     Rfft2Setup* z = typed_handle<Rfft2Setup, T>(setup);
@@ -117,10 +129,79 @@ static int rfft2_batch(void* setup, const T* in, T* out, size_t batch, int dir, 
     if (ranges_overlap((uintptr_t)in, fwd ? real_bytes : spec_bytes, (uintptr_t)out, fwd ? spec_bytes : real_bytes))
         return bad("rfft2: out overlaps in (the two sides differ in size: there is no in-place form)");
     if (int rc = fft2d_bind(z->bound, "rfft2: ", st)) return rc;
+    return rfft2_run<T>(z, in, out, batch, dir, scaling, st);
+}
+
+// ------------------------------------------------------------------------------------------------ spectral convolution of real images
+// Shapes where the fused convolution kernel is the default for one broadcast H: a shape is in it where tests/test_gpu_rfft2conv.py
+// test_default_cells holds selector 155 faster than selector 154 on the device by more than the spread of the composed route's
+// round-bests.  A shape that loses returns false here and stays reachable through AB_RFFT2CONV_FUSED.  Measured on an
+// MI355X at 64 MiB of images: fused wins all six shapes, 1.86 x (32 x 64) to 2.24 x (64 x 64), against a spread of the composed
+// route's round-bests of at most 1.01.
+static bool rfft2conv_fused_default(int rows, int cols) {
+    (void)rows; (void)cols;
+    return true;
+}
+
+// the fused kernel takes float images of the six shapes and ONE half-spectrum; per-image H is always composed
+static bool rfft2conv_fused_now(const Rfft2Setup* z, int h_broadcast, const AbSel& sel) {
+    return fused_selected(sel, AB_RFFT2CONV_COMPOSED, AB_RFFT2CONV_FUSED, z->fusable && h_broadcast != 0, rfft2conv_fused_default(z->rows, z->cols));
+}
+
+static int rfft2conv_fused(Rfft2Setup* z, const float* in, const float* H, float* out, float scaling, size_t batch, int conj_h, hipStream_t st) {
+    if (int rc = inner_on_device(z->inner_rows)) return rc;
+    if (z->inner64)
+        if (int rc = inner_on_device(z->inner64)) return rc;
+    Setup* s64 = z->rows == 64 ? z->inner_rows : z->inner64;
+    const cx<float>* tw64 = s64 ? s64->d_tw.as<cx<float>>() : nullptr;
+    const cx<float>* G = reinterpret_cast<const cx<float>*>(H);
+    const size_t image = (size_t)z->rows * z->cols;
+    return fft2d_fused(in, image, out, image, batch, [&](const float* pi, float* po, size_t nb) {
+        return with_one_of<16, 32, 64>(z->rows, [&](auto R) {
+            return with_flag(z->cols == 64, [&](auto W) {
+                constexpr int r = decltype(R)::value, c = decltype(W)::value ? 64 : 32;
+                typedef Rfft2ConvForm<r, c> Form;
+                return fft2d_fused_conv_launch<Rfft2Cfg<r, c>>(z->inner_rows, fft_rfft2conv_kernel<r, c, Form::PF, Form::HREG>, tw64, pi, G, po, nb,
+                                                              scaling, conj_h, st);
+            });
+        });
+    });
+}
+
+// Per chunk of whole images through the half-spectrum scratch: the handle's own forward transform from in into the scratch, the product
+// in place there (H modulo one half-spectrum where it is broadcast, offset by the chunk where it is per image), the handle's own
+// backward transform into out with the scaling.  The transforms take whichever route pffft_hip_rfft2_route names under the calling
+// thread's selector; composed, each takes the handle's scratch image (pad) inside, and refuses to grow it during a capture before it
+// launches anything - the forward transform of the first chunk is the first launch of the call.
+template <typename T>
+static int rfft2conv_composed(Rfft2Setup* z, const T* in, const T* H, T* out, T scaling, size_t batch, int conj_h, int h_broadcast, hipStream_t st) {
+    const size_t real_image = (size_t)z->rows * (size_t)z->cols, half = (size_t)z->rows * (size_t)(z->cols / 2 + 1);
+    return chunked_scratch<cx<T>>(z->spec, st, batch, half * sizeof(cx<T>), "the half-spectrum scratch", [&](cx<T>* X, size_t v0, size_t cnt) {
+        if (int rc = rfft2_run<T>(z, in + v0 * real_image, reinterpret_cast<T*>(X), cnt, PFFFT_FORWARD, (T)1, st)) return rc;
+        const cx<T>* G = reinterpret_cast<const cx<T>*>(H) + (h_broadcast ? 0 : v0 * half);
+        if (int rc = fft2conv_product<T>(X, G, cnt * half, h_broadcast ? half : cnt * half, conj_h, st)) return rc;
+        return rfft2_run<T>(z, reinterpret_cast<const T*>(X), out + v0 * real_image, cnt, PFFFT_BACKWARD, scaling, st);
+    });
+}
+
+template <typename T>
+static int rfft2conv_batch(void* setup, const T* in, const T* H, T* out, T scaling, size_t batch, int conj_h, int h_broadcast, hipStream_t st) {
+    const char* pre = "rfft2 convolve: ";
+    Rfft2Setup* z = typed_handle<Rfft2Setup, T>(setup);
+    if (!z) return (int)hipErrorInvalidHandle;
+    if (batch == 0) return 0;
+    if (!in || !H || !out) return bad_in(pre, "NULL in / H / out");
+    if (!aligned16(in) || !aligned16(H) || !aligned16(out)) return bad_in(pre, "in / H / out not aligned to 16 bytes");
+    const size_t bytes = batch * (size_t)z->rows * (size_t)z->cols * sizeof(T);
+    const size_t himage = (size_t)z->rows * (size_t)(z->cols / 2 + 1) * 2 * sizeof(T);
+    if (in != out && ranges_overlap((uintptr_t)in, bytes, (uintptr_t)out, bytes))
+        return bad_in(pre, "out overlaps in (in == out, in place, is the one legal overlap)");
+    if (ranges_overlap((uintptr_t)H, h_broadcast ? himage : batch * himage, (uintptr_t)out, bytes)) return bad_in(pre, "H overlaps out");
+    if (int rc = fft2d_bind(z->bound, pre, st)) return rc;
     if constexpr (sizeof(T) == 4) {
-        if (rfft2_fused_now(z, ab())) return rfft2_fused(z, in, out, batch, dir, scaling, st);
+        if (rfft2conv_fused_now(z, h_broadcast, ab())) return rfft2conv_fused(z, in, H, out, scaling, batch, conj_h != 0, st);
     }
-    return rfft2_composed<T>(z, in, out, batch, dir, scaling, st);
+    return rfft2conv_composed<T>(z, in, H, out, scaling, batch, conj_h != 0, h_broadcast, st);
 }
 
 }  // namespace pf
@@ -145,4 +226,17 @@ PF_EXPORT const char* pffft_hip_rfft2_route(const void* setup) {
     const pf::Rfft2Setup* z = pf::checked_handle<pf::Rfft2Setup>(setup);
     if (!z) return "";
     return pf::rfft2_fused_now(z, pf::ab()) ? "fused" : "composed";
+}
+PF_EXPORT int pffft_hip_rfft2_convolve_batch(PFFFT_HIP_Rfft2Setup* s, const float* in, const float* H, float* out, float scaling, size_t batch,
+                                             int conj_h, int h_broadcast, void* stream) {
+    return pf::rfft2conv_batch<float>(s, in, H, out, scaling, batch, conj_h, h_broadcast, (hipStream_t)stream);
+}
+PF_EXPORT int pffftd_hip_rfft2_convolve_batch(PFFFTD_HIP_Rfft2Setup* s, const double* in, const double* H, double* out, double scaling, size_t batch,
+                                              int conj_h, int h_broadcast, void* stream) {
+    return pf::rfft2conv_batch<double>(s, in, H, out, scaling, batch, conj_h, h_broadcast, (hipStream_t)stream);
+}
+PF_EXPORT const char* pffft_hip_rfft2_convolve_route(const void* setup, int h_broadcast) {
+    const pf::Rfft2Setup* z = pf::checked_handle<pf::Rfft2Setup>(setup);
+    if (!z) return "";
+    return pf::rfft2conv_fused_now(z, h_broadcast, pf::ab()) ? "fused" : "composed";
 }

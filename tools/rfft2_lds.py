@@ -6,7 +6,11 @@ columns 0 and cols / 2, the reads of the store - with the addresses the kernel f
 access the worst wave-instruction in LDS cycles against the conflict-free count; a ratio above 2 fails (exit status 1).  The layout (half-line
 pitch HP and image stride in complex elements; a line of cols points is 2 HP; whether odd threads take a half-spectrum chunk's two bins in
 the other order) is read from the RFFT2_LAYOUT lines of the header, so the table is the kernel's.  --search prints the best (HP, image
-stride, chunk orders) per shape instead.  No GPU needed:  python tools/rfft2_lds.py"""
+stride, chunk orders) per shape instead.  Then the same for fft_rfft2conv_kernel (pffft_amd/csrc/fft_rfft2c.h) on the same
+layouts: the real-side load, the forward row pass and the untangling step as above, the column step (one round trip of a dft16 / dft32
+column, or the forward half passes, the packed column's exchange through the spare position H and the two half passes of the transposed
+network), the rebuilding step reading NATURAL row positions, the backward row pass and the real-side store.
+No GPU needed:  python tools/rfft2_lds.py"""
 import os
 import re
 import sys
@@ -34,8 +38,8 @@ def perm(L, u):
     return 8 * (u % 8) + u // 8 if L == 64 else u
 
 
-def accesses(R, C, hp, img, lsw, ssw):
-    """[(name, kind, [64 byte addresses per wave-instruction ...])]"""
+def accesses(R, C, hp, img, lsw, ssw, conv=False):
+    """[(name, kind, [64 byte addresses per wave-instruction ...])] of fft_rfft2_kernel, both directions; conv: of fft_rfft2conv_kernel"""
     PT = points_per_thread(R, C)
     T = R * C // 2 // PT
     H, pitch = C // 2, 2 * hp
@@ -99,6 +103,56 @@ def accesses(R, C, hp, img, lsw, ssw):
                 l, v = k // H, k % H
                 return 8 * ((2 * l + which) * hp + v)
             per_wave("forward untangle write", "w64", wr)
+    if conv:
+        if R < 64:
+            axis("convolve", "column", R, H, 1, hp)                 # read, forward, x G, backward, write: one round trip
+        else:
+            G = T // 8
+            for i in range(H // G):
+                for q in range(8):
+                    def a(t, i=i, q=q):
+                        return 8 * ((t % G + G * i) + (t // G + 8 * q) * hp)
+                    def b(t, i=i, q=q):
+                        return 8 * ((t % G + G * i) + (8 * (t // G) + q) * hp)
+                    per_wave("convolve column 8x8 forward first half read", "r64", a)
+                    per_wave("convolve column 8x8 forward first half write", "w64", a)
+                    per_wave("convolve column 8x8 forward second half read", "r64", b)
+                    per_wave("convolve column 8x8 transposed first half write", "w64", b)
+                    per_wave("convolve column 8x8 transposed second half read", "r64", a)
+                    per_wave("convolve column 8x8 transposed second half write", "w64", a)
+            sp = 2 if hp - H >= 2 else 1            # spare positions of a half line the exchange spreads over (fft_rfft2c.h)
+            for k2 in range(8):
+                def xw(t, k2=k2):
+                    k1 = t // G
+                    return 8 * ((8 * k1 + k2) * hp + H + (k1 >> 2) % sp) if t % G == 0 else None
+                def xr(t, k2=k2):
+                    k1 = t // G
+                    kp, k2p = (8 - k1) % 8, ((8 - k2) % 8 if k1 == 0 else 7 - k2)
+                    return 8 * ((8 * kp + k2p) * hp + H + (kp >> 2) % sp) if t % G == 0 else None
+                per_wave("convolve packed column exchange write", "w64", xw)
+                per_wave("convolve packed column exchange read", "r64", xr)
+        for i in range(npair):
+            for which in (0, 1):
+                def rd(t, i=i, which=which):
+                    k = t + T * i
+                    l, v = k // H, k % H
+                    return 8 * ((2 * l + which) * hp + v)
+                per_wave("convolve rebuild read", "r64", rd)
+
+                def wr(t, i=i, which=which):
+                    k = t + T * i
+                    l, v = k // H, k % H
+                    return 8 * (l * pitch + ((H if v == 0 else C - v) if which else v))
+                per_wave("convolve rebuild write", "w64", wr)
+        axis("backward", "row", C, R // 2, pitch, 1)
+        for i in range(ch_real // T):
+            for j in range(4):
+                def st(t, i=i, j=j):
+                    e = 4 * (t + T * i)
+                    r, c = e // C, e % C
+                    return 4 * (2 * ((r // 2) * pitch + perm(C, c + j)) + r % 2)
+                per_wave("backward store read", "r32", st)
+        return out
     axis("forward", "column", R, H, 1, hp)
     for i in range((ch_spec + T - 1) // T):
         for half in (0, 1):
@@ -166,10 +220,10 @@ def accesses(R, C, hp, img, lsw, ssw):
     return out
 
 
-def worst(R, C, hp, img, lsw, ssw, limit=None):
+def worst(R, C, hp, img, lsw, ssw, limit=None, conv=False):
     """{access name: (worst cycles of a wave-instruction, conflict-free cycles)}; None as soon as one is above `limit` times conflict-free"""
     res = {}
-    for name, kind, addrs in accesses(R, C, hp, img, lsw, ssw):
+    for name, kind, addrs in accesses(R, C, hp, img, lsw, ssw, conv):
         c = lds_sim.cycles(kind, addrs)
         if limit is not None and c > limit * lds_sim.ideal(kind):
             return None
@@ -203,17 +257,20 @@ def main() -> int:
         return 0
     table = layouts()
     bad = 0
-    for R, C in SHAPES:
-        hp, img, lsw, ssw = table[(R, C)]
-        assert hp >= C // 2 + 1 and img >= R * hp, (R, C, hp, img)
-        res = worst(R, C, hp, img, lsw, ssw)
-        print(f"{R} x {C}: half-line pitch {hp}, image stride {img} complex elements, chunk order alternating on load {lsw} / store {ssw}, "
-              f"{points_per_thread(R, C)} points per thread")
-        for name, (c, i) in res.items():
-            note = "" if c == i else f"  ({c / i:.2g}-way)"
-            if c > 2 * i:
-                note, bad = note + "  <- MORE THAN 2-WAY", 1
-            print(f"    {name:48s} {c} cycles, conflict-free {i}{note}")
+    for conv in (False, True):
+        if conv:
+            print("fft_rfft2conv_kernel (fft_rfft2c.h) on the same layouts")
+        for R, C in SHAPES:
+            hp, img, lsw, ssw = table[(R, C)]
+            assert hp >= C // 2 + 1 and img >= R * hp, (R, C, hp, img)
+            res = worst(R, C, hp, img, lsw, ssw, conv=conv)
+            print(f"{R} x {C}: half-line pitch {hp}, image stride {img} complex elements, chunk order alternating on load {lsw} / store {ssw}, "
+                  f"{points_per_thread(R, C)} points per thread")
+            for name, (c, i) in res.items():
+                note = "" if c == i else f"  ({c / i:.2g}-way)"
+                if c > 2 * i:
+                    note, bad = note + "  <- MORE THAN 2-WAY", 1
+                print(f"    {name:52s} {c} cycles, conflict-free {i}{note}")
     return bad
 
 
