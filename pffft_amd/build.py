@@ -14,7 +14,7 @@ OBJDIR = os.path.join(HERE, "..", "build", "obj")
 # the PFDSP mixers are their own library, like the reference's PFDSP target (CMakeLists.txt:206)
 DSP_LIB = os.path.join(HERE, "libpfdsp_hip.so")
 DSP_SRC = os.path.join(CSRC, "pfdsp_hip.hip")
-DSP_DEPS = [DSP_SRC, os.path.join(CSRC, "pfdsp_mix.h"), os.path.join(HERE, "..", "include", "pfdsp_hip.h"),
+DSP_DEPS = [DSP_SRC, os.path.join(CSRC, "pfdsp_mix.h"), os.path.join(CSRC, "pf_handout.h"), os.path.join(HERE, "..", "include", "pfdsp_hip.h"),
             os.path.join(CSRC, "exports_dsp.map")]
 # the PFDSP carriers and CIC down-converter (pf_carrier.h, pf_cic.h): a companion library, so that libpfdsp_hip.so keeps the
 # mixers' exported set

@@ -13,6 +13,7 @@
 #pragma once
 #include "fft_stock.h"
 #include "fft_tiled.h"  // ChunkOps
+#include "pf_handout.h"
 
 namespace pf {
 
@@ -142,10 +143,7 @@ zconvolve_dyn_kernel(const T* a, const T* b, T* ab, unsigned long long Q, unsign
     const unsigned long long nchunks = (Q + ZD_CHUNK - 1) / ZD_CHUNK;
     const bool need_rem = BCAST || is_real;
     unsigned pend = 0;
-    // the first TWO groups of a workgroup are static (its index, and that plus the grid); the counter hands out what follows: value v =
-    // group 2 grid + v.  (Every workgroup used to open with two grabs: ~2 000 atomics on one address, served at ~80 M/s, stood between the
-    // launch and the last workgroup's first load - 25-35 us of every launch, tools/r4_small_batch.py.)
-    pend = blockIdx.x + gridDim.x;
+    pend = blockIdx.x + gridDim.x;   // hand-out: pf_handout.h
     __syncthreads();
     unsigned g = blockIdx.x;
     V xa[ZD_ROWS], xb[ZD_ROWS], xc[ZD_ROWS];
@@ -170,12 +168,9 @@ zconvolve_dyn_kernel(const T* a, const T* b, T* ab, unsigned long long Q, unsign
     };
     load_chunk((unsigned long long)g * ZD_WAVES + wave, xa, xb, xc, rem);
     for (unsigned it = 0; (unsigned long long)g * ZD_WAVES < nchunks; ++it) {
-        if (threadIdx.x == 0) {
-            s_next[(it + 1) & 1] = pend;
-            pend = 2u * gridDim.x + atomicAdd(&ctr[0], 1u);
-        }
+        if (threadIdx.x == 0) pend = handout_grab(s_next, it, pend, ctr);
         __syncthreads();
-        const unsigned gn = s_next[(it + 1) & 1];
+        const unsigned gn = s_next[(it + 1) & 1];   // hand-out: pf_handout.h, kept inline: handout_next(true, ..) changes this kernel
         const unsigned long long c = (unsigned long long)g * ZD_WAVES + wave;
         V na[ZD_ROWS], nb[ZD_ROWS], nc[ZD_ROWS];
         unsigned nrem[ZD_ROWS];
@@ -200,11 +195,7 @@ zconvolve_dyn_kernel(const T* a, const T* b, T* ab, unsigned long long Q, unsign
         for (int r = 0; r < ZD_ROWS; ++r) { xa[r] = na[r]; xb[r] = nb[r]; if (ACC) xc[r] = nc[r]; rem[r] = nrem[r]; }
         g = gn;
     }
-    if (threadIdx.x == 0) {
-        __threadfence();
-        unsigned d = atomicAdd(&ctr[1], 1u);
-        if (d == gridDim.x - 1) { atomicExch(&ctr[0], 0u); atomicExch(&ctr[1], 0u); }
-    }
+    if (threadIdx.x == 0) handout_rearm(ctr);
 }
 
 // zreorder through the padded block image: G vectors per pass.  to_canonical: internal -> canonical (PFFFT_FORWARD).
@@ -341,10 +332,7 @@ zreorder_dyn_kernel(const T* in, T* out, size_t batch, int n, int is_real, int G
     const size_t last_chunk = batch * (size_t)nchk - 1;
     const size_t gchunks = (size_t)G * nchk;
     unsigned pend = 0;
-    // the first TWO groups of a workgroup are static (its index, and that plus the grid); the counter hands out what follows: value v =
-    // group 2 grid + v.  (Every workgroup used to open with two grabs: ~2 000 atomics on one address, served at ~80 M/s, stood between the
-    // launch and the last workgroup's first load - 25-35 us of every launch, tools/r4_small_batch.py.)
-    pend = blockIdx.x + gridDim.x;
+    pend = blockIdx.x + gridDim.x;   // hand-out: pf_handout.h
     __syncthreads();
     unsigned g = blockIdx.x;
     chunk16 v[ZRD_U];
@@ -359,10 +347,7 @@ zreorder_dyn_kernel(const T* in, T* out, size_t batch, int n, int is_real, int G
     };
     load_group(g);
     for (unsigned it = 0; g < ngroups; ++it) {
-        if (tid == 0) {
-            s_next[(it + 1) & 1] = pend;
-            pend = 2u * gridDim.x + atomicAdd(&ctr[0], 1u);
-        }
+        if (tid == 0) pend = handout_grab(s_next, it, pend, ctr);
         const size_t t0 = (size_t)g * G;
         const int cnt = (int)((batch - t0) < (size_t)G ? (batch - t0) : (size_t)G);
         const int tot = cnt * nchk;
@@ -406,7 +391,7 @@ zreorder_dyn_kernel(const T* in, T* out, size_t batch, int n, int is_real, int G
             }
         }
         __syncthreads();
-        const unsigned gn = s_next[(it + 1) & 1];
+        const unsigned gn = s_next[(it + 1) & 1];   // hand-out: pf_handout.h, kept inline: handout_next(true, ..) changes this kernel
         load_group(gn);                           // in flight during phase 2
         // ---- phase 2: out of the image, linear 16-byte stores
         chunk16* dst = out16 + t0 * nchk;
@@ -420,11 +405,7 @@ zreorder_dyn_kernel(const T* in, T* out, size_t batch, int n, int is_real, int G
         __syncthreads();
         g = gn;
     }
-    if (tid == 0) {
-        __threadfence();
-        unsigned d = atomicAdd(&ctr[1], 1u);
-        if (d == gridDim.x - 1) { atomicExch(&ctr[0], 0u); atomicExch(&ctr[1], 0u); }
-    }
+    if (tid == 0) handout_rearm(ctr);
 }
 
 }  // namespace pf

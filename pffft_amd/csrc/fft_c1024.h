@@ -30,6 +30,7 @@
 #pragma once
 #include "cxmath.h"
 #include "fft_tiled.h"   // lds_ld_c
+#include "pf_handout.h"
 
 namespace pf {
 
@@ -231,7 +232,7 @@ __device__ __forceinline__ void c1024_load_twiddles(const cx<float>* __restrict_
 }
 
 // ---- dynamic in-order distribution + prefetch (default) ----
-// ctr[0] = next group of 8 transforms, ctr[1] = workgroups finished (the last one re-arms both)
+// groups of 8 transforms, handed out as pf_handout.h describes
 // exp(j 2 pi frac(turns)): the reduction in double, the residue of the float conversion as a first-order rotation
 __device__ __forceinline__ cx<float> c1024_unit(double turns) {
     turns -= rint(turns);
@@ -265,10 +266,7 @@ __device__ __forceinline__ void c1024_dyn_body(const float* in, float* out, unsi
         }
     }
     unsigned pend = 0;
-    // the first TWO groups of a workgroup are static (its index, and that plus the grid); the counter hands out what follows: value v =
-    // group 2 grid + v.  (Every workgroup used to open with two grabs: ~2 000 atomics on one address, served at ~80 M/s, stood between the
-    // launch and the last workgroup's first load - 25-35 us of every launch, tools/r4_small_batch.py.)
-    pend = blockIdx.x + gridDim.x;
+    pend = blockIdx.x + gridDim.x;   // hand-out: pf_handout.h
     __syncthreads();
     unsigned g = blockIdx.x;
     const size_t last = (size_t)batch - 1;
@@ -278,10 +276,7 @@ __device__ __forceinline__ void c1024_dyn_body(const float* in, float* out, unsi
         c1024_load(raw, in, t0 < last ? t0 : last, L);
     }
     for (unsigned it = 0; (size_t)g * C1024_WAVES < batch; ++it) {
-        if (threadIdx.x == 0) {  // publish the index of iteration it+1, grab the one of it+2
-            s_next[(it + 1) & 1] = pend;
-            pend = 2u * gridDim.x + atomicAdd(&ctr[0], 1u);
-        }
+        if (threadIdx.x == 0) pend = handout_grab(s_next, it, pend, ctr);
         const size_t t = (size_t)g * C1024_WAVES + wave;
         const bool active = t < batch;  // wave-uniform
         if constexpr (MIX != 0) {
@@ -291,17 +286,13 @@ __device__ __forceinline__ void c1024_dyn_body(const float* in, float* out, unsi
             c1024_part_a<DIR, IN_INTERNAL>(raw, wl, wf, w1, L);
         }
         __syncthreads();
-        const unsigned gn = s_next[(it + 1) & 1];
+        const unsigned gn = s_next[(it + 1) & 1];   // hand-out: pf_handout.h, kept inline: handout_next(true, ..) changes this kernel
         const size_t tn = (size_t)gn * C1024_WAVES + wave;
         c1024_load(raw, in, tn < last ? tn : last, L);  // in flight while this transform finishes
         if (active) c1024_part_b<DIR, OUT_INTERNAL>(out, t, wl, wf, w2, L);
         g = gn;
     }
-    if (threadIdx.x == 0) {
-        __threadfence();  // my last (unused) grab has landed before I report done
-        unsigned d = atomicAdd(&ctr[1], 1u);
-        if (d == gridDim.x - 1) { atomicExch(&ctr[0], 0u); atomicExch(&ctr[1], 0u); }
-    }
+    if (threadIdx.x == 0) handout_rearm(ctr);
 }
 
 template <int DIR, int IN_INTERNAL, int OUT_INTERNAL>

@@ -14,6 +14,7 @@
 // fft_tiled_kernel (persistent workgroups, in-order pull, next vector in flight).
 #pragma once
 #include "fft_tiled.h"
+#include "pf_handout.h"
 
 namespace pf {
 
@@ -142,10 +143,7 @@ fft_conv_kernel(const IO io, const typename C::real_t* __restrict__ H, unsigned 
     const bool dyn = ctr != nullptr;
     unsigned pend = 0;
     unsigned g = blockIdx.x;
-    // the first TWO groups of a workgroup are static (its index, and that plus the grid); the counter hands out what follows: value v =
-    // group 2 grid + v.  (Every workgroup used to open with two grabs: ~2 000 atomics on one address, served at ~80 M/s, stood between the
-    // launch and the last workgroup's first load - 25-35 us of every launch, tools/r4_small_batch.py.)
-    pend = blockIdx.x + gridDim.x;
+    pend = blockIdx.x + gridDim.x;   // hand-out: pf_handout.h
     __syncthreads();
     const size_t last = (size_t)batch - 1;
     chunk16 raw[NCH];
@@ -156,10 +154,7 @@ fft_conv_kernel(const IO io, const typename C::real_t* __restrict__ H, unsigned 
         io.load(raw, t0 < last ? t0 : last, t);
     }
     for (unsigned it = 0; (size_t)g * C::T_PER_WG < batch; ++it) {
-        if (dyn && threadIdx.x == 0) {
-            s_next[(it + 1) & 1] = pend;
-            pend = 2u * gridDim.x + atomicAdd(&ctr[0], 1u);
-        }
+        if (dyn && threadIdx.x == 0) pend = handout_grab(s_next, it, pend, ctr);
         const size_t tr = (size_t)g * C::T_PER_WG + slot;
         const bool active = tr < batch;  // inactive slots recompute the last vector and never store
         const size_t dv = active ? tr : last;
@@ -170,7 +165,7 @@ fft_conv_kernel(const IO io, const typename C::real_t* __restrict__ H, unsigned 
         KF::template butterflies<0>(v, t, wf, twt);
         if constexpr (NS > 1) KF::template xwrite<0>(v, t, img);
         __syncthreads();  // publishes s_next; first half of exchange 0
-        const unsigned gn = dyn ? s_next[(it + 1) & 1] : g + gridDim.x;
+        const unsigned gn = handout_next(dyn, s_next, it, g);
         if constexpr (C::PREFETCH) {  // the loads of the next vector fly while this one is finished
             const size_t tn = (size_t)gn * C::T_PER_WG + slot;
             io.load(raw, tn < last ? tn : last, t);
@@ -204,11 +199,7 @@ fft_conv_kernel(const IO io, const typename C::real_t* __restrict__ H, unsigned 
         }
         g = gn;
     }
-    if (dyn && threadIdx.x == 0) {
-        __threadfence();
-        unsigned d = atomicAdd(&ctr[1], 1u);
-        if (d == gridDim.x - 1) { atomicExch(&ctr[0], 0u); atomicExch(&ctr[1], 0u); }
-    }
+    if (dyn && threadIdx.x == 0) handout_rearm(ctr);
 }
 
 // configurations: the register-tiled ones of fft_tiled.h with one base twiddle per butterfly in registers (two transforms and

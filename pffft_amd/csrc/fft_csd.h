@@ -18,6 +18,7 @@
 // term, then the run partials ascending.  No atomics, no FMA (-ffp-contract=off), so every route gives the same bits.
 #pragma once
 #include "fft_psd.h"
+#include "pf_handout.h"
 
 namespace pf {
 
@@ -69,7 +70,7 @@ fft_csd_kernel(const float* xsig, size_t x_stride, const float* ysig, size_t y_s
     }
     const bool dyn = ctr != nullptr;
     unsigned g = blockIdx.x;
-    unsigned pend = blockIdx.x + gridDim.x;   // the first two groups of a workgroup are static, the counter hands out what follows
+    unsigned pend = blockIdx.x + gridDim.x;   // hand-out: pf_handout.h
     __syncthreads();
     const unsigned rpg = (navg + PSD_RUN - 1) / PSD_RUN;
     const size_t last = (size_t)nruns - 1;
@@ -103,10 +104,7 @@ fft_csd_kernel(const float* xsig, size_t x_stride, const float* ysig, size_t y_s
     chunk16 raw[NCH];
     K::load_raw(raw, xbase, t, true);
     for (unsigned it = 0; (size_t)g * C::T_PER_WG < nruns; ++it) {
-        if (dyn && threadIdx.x == 0) {
-            s_next[(it + 1) & 1] = pend;
-            pend = 2u * gridDim.x + atomicAdd(&ctr[0], 1u);
-        }
+        if (dyn && threadIdx.x == 0) pend = handout_grab(s_next, it, pend, ctr);
         const size_t tr = (size_t)g * C::T_PER_WG + slot;
         const bool active = tr < nruns;
         unsigned gn = 0;
@@ -152,7 +150,7 @@ fft_csd_kernel(const float* xsig, size_t x_stride, const float* ysig, size_t y_s
             K::template butterflies<0>(v, t, w, twt);
             if constexpr (C::NS > 1) K::template xwrite<0>(v, t, img);
             __syncthreads();  // publishes s_next; first half of exchange 0
-            if (fi == 0) gn = dyn ? s_next[(it + 1) & 1] : g + gridDim.x;
+            if (fi == 0) gn = handout_next(dyn, s_next, it, g);
             // the y frame of this step (a shorter run repeats its last one)
             const T* ysrc = ybase + (size_t)(fi < len ? fi : len - 1) * hop;
             if constexpr (C::PREFETCH) K::load_raw(raw, ysrc, t, true);
@@ -241,11 +239,7 @@ fft_csd_kernel(const float* xsig, size_t x_stride, const float* ysig, size_t y_s
         len = len_of((size_t)g * C::T_PER_WG + slot);
         bound = bound_of(g);
     }
-    if (dyn && threadIdx.x == 0) {
-        __threadfence();
-        unsigned d = atomicAdd(&ctr[1], 1u);
-        if (d == gridDim.x - 1) { atomicExch(&ctr[0], 0u); atomicExch(&ctr[1], 0u); }
-    }
+    if (dyn && threadIdx.x == 0) handout_rearm(ctr);
 }
 
 // ------------------------------------------------------------------------------------------------ composed route

@@ -15,6 +15,7 @@
 //                       the streaming kernels of the COMPOSED route around transform_batch (canonical layout) in a scratch image.
 #pragma once
 #include "fft_tiled.h"
+#include "pf_handout.h"
 
 namespace pf {
 
@@ -65,17 +66,14 @@ fft_dct_kernel(const float* in, float* out, unsigned batch, const cx<float>* __r
 
     const bool dyn = ctr != nullptr;
     unsigned g = blockIdx.x;
-    unsigned pend = blockIdx.x + gridDim.x;   // the first two groups of a workgroup are static, the counter hands out what follows
+    unsigned pend = blockIdx.x + gridDim.x;   // hand-out: pf_handout.h
     __syncthreads();
     const size_t last = (size_t)batch - 1;
     auto src_of = [&](size_t tr) -> const T* { return in + (tr < last ? tr : last) * (size_t)N; };
     chunk16 raw[NCH];
     K::load_raw(raw, src_of((size_t)g * C::T_PER_WG + slot), t, false);   // dense chunks in lane order, each once
     for (unsigned it = 0; (size_t)g * C::T_PER_WG < batch; ++it) {
-        if (dyn && threadIdx.x == 0) {
-            s_next[(it + 1) & 1] = pend;
-            pend = 2u * gridDim.x + atomicAdd(&ctr[0], 1u);
-        }
+        if (dyn && threadIdx.x == 0) pend = handout_grab(s_next, it, pend, ctr);
         const size_t tr = (size_t)g * C::T_PER_WG + slot;
         const bool active = tr < batch;  // inactive slots recompute the last row and never store
         T* dst = out + (active ? tr : last) * (size_t)N;
@@ -128,7 +126,7 @@ fft_dct_kernel(const float* in, float* out, unsigned batch, const cx<float>* __r
         K::template butterflies<0>(v, t, w, twt);
         if constexpr (C::NS > 1) K::template xwrite<0>(v, t, img);
         __syncthreads();  // publishes s_next; first half of exchange 0
-        const unsigned gn = dyn ? s_next[(it + 1) & 1] : g + gridDim.x;
+        const unsigned gn = handout_next(dyn, s_next, it, g);
         if constexpr (C::PREFETCH) K::load_raw(raw, src_of((size_t)gn * C::T_PER_WG + slot), t, false);
         if constexpr (C::NS > 1) { K::template xread<0>(v, t, img); K::xsync(); K::template butterflies<1>(v, t, w, twt); }
         if constexpr (C::NS > 2) { K::template xwrite<1>(v, t, img); K::xsync(); K::template xread<1>(v, t, img); K::xsync(); K::template butterflies<2>(v, t, w, twt); }
@@ -185,11 +183,7 @@ fft_dct_kernel(const float* in, float* out, unsigned batch, const cx<float>* __r
         if constexpr (!C::PREFETCH) K::load_raw(raw, src_of((size_t)gn * C::T_PER_WG + slot), t, false);
         g = gn;
     }
-    if (dyn && threadIdx.x == 0) {
-        __threadfence();
-        unsigned d = atomicAdd(&ctr[1], 1u);
-        if (d == gridDim.x - 1) { atomicExch(&ctr[0], 0u); atomicExch(&ctr[1], 0u); }
-    }
+    if (dyn && threadIdx.x == 0) handout_rearm(ctr);
 }
 
 // LDS of fft_dct_kernel: the images and the counter slot of fft_tiled_kernel (these configurations have no twiddle table)

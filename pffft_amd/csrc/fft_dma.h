@@ -20,6 +20,7 @@
 #pragma once
 #include "fft_tiled.h"
 #include "fft_fir.h"
+#include "pf_handout.h"
 
 namespace pf {
 
@@ -127,10 +128,7 @@ fastconv_dma_kernel(const float* __restrict__ x, float* __restrict__ y, const cx
     const bool dyn = ctr != nullptr;
     unsigned pend = 0;
     unsigned g = blockIdx.x;
-    // the first TWO groups of a workgroup are static (its index, and that plus the grid); the counter hands out what follows: value v =
-    // group 2 grid + v.  (Every workgroup used to open with two grabs: ~2 000 atomics on one address, served at ~80 M/s, stood between the
-    // launch and the last workgroup's first load - 25-35 us of every launch, tools/r4_small_batch.py.)
-    pend = blockIdx.x + gridDim.x;
+    pend = blockIdx.x + gridDim.x;   // hand-out: pf_handout.h
     __syncthreads();
     const long long nblk_all = (long long)nblk * nsig;
     // the last 16 bytes a lane may read: copies that would run past the signal are clamped there (their samples are
@@ -153,15 +151,12 @@ fastconv_dma_kernel(const float* __restrict__ x, float* __restrict__ y, const cx
     issue(g, 0);
     int b = 0;
     for (unsigned it = 0; (long long)g * C::T_PER_WG < nblk_all; ++it) {
-        if (dyn && threadIdx.x == 0) {
-            s_next[(it + 1) & 1] = pend;
-            pend = 2u * gridDim.x + atomicAdd(&ctr[0], 1u);
-        }
+        if (dyn && threadIdx.x == 0) pend = handout_grab(s_next, it, pend, ctr);
         PF_DSTAMP(0);
         wait_vmcnt<0>();
         wg_sync_raw();
         PF_DSTAMP(1);
-        const unsigned gn = dyn ? s_next[(it + 1) & 1] : g + gridDim.x;
+        const unsigned gn = handout_next(dyn, s_next, it, g);
         if constexpr (!SPREAD) issue(gn, b ^ 1);
         PF_DSTAMP(2);
         const long long blk_all = (long long)g * C::T_PER_WG + slot;
@@ -257,11 +252,7 @@ fastconv_dma_kernel(const float* __restrict__ x, float* __restrict__ y, const cx
         b ^= 1;
     }
     wait_vmcnt<0>();
-    if (dyn && threadIdx.x == 0) {
-        __threadfence();
-        unsigned d = atomicAdd(&ctr[1], 1u);
-        if (d == gridDim.x - 1) { atomicExch(&ctr[0], 0u); atomicExch(&ctr[1], 0u); }
-    }
+    if (dyn && threadIdx.x == 0) handout_rearm(ctr);
 }
 
 // ------------------------------------------------------------------------------------------------------------------

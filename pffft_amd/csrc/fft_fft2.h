@@ -1,8 +1,8 @@
 // Batched 2-D complex transforms (include/pffft_hip.h: pffft[d]_hip_fft2_*):  out[u][v] = s sum_r sum_c in[r][c] exp(-/+ 2 pi j (u r / rows +
 // v c / cols)) of dense row-major images of rows x cols interleaved complex values, natural order in and out.  This file holds
 //   fft_fft2_kernel      the FUSED route (float; rows, cols in {16, 32, 64}): whole images live in LDS, ONE HBM read and ONE HBM write per
-//                        image, on the persistent loop of the fused family (static-then-counter hand-out, s_next, inactive slots, counter
-//                        reset; the launch is loop_launch with CONV_ONESHOT).  All nine shapes loop: none runs in dispatch order only.
+//                        image, on the persistent loop of the fused family (the hand-out of pf_handout.h, inactive slots; the launch is
+//                        loop_launch with CONV_ONESHOT).  All nine shapes loop: none runs in dispatch order only.
 //   fft2_transpose_kernel  the COMPOSED route's kernel around two ordered transform_batch calls (fft2_tu.hip): per image
 //                        [rows][cols] -> [cols][rows] through padded 32 x 32 LDS tiles, 64-bit indices, edge tiles predicated; the second
 //                        launch carries the scaling.
@@ -41,6 +41,7 @@
 // kernel, fused shapes beyond 64 (128 x 128 = 128 KiB is one image per CU) and mixed-radix tiles, multi-device shards of one setup, 3-D.
 #pragma once
 #include "cxmath.h"
+#include "pf_handout.h"
 
 namespace pf {
 
@@ -149,7 +150,7 @@ fft_fft2_kernel(const float* in, float* out, unsigned batch, float s, const cx<f
 
     const bool dyn = ctr != nullptr;
     unsigned g = blockIdx.x;
-    unsigned pend = blockIdx.x + gridDim.x;   // the first two groups of a workgroup are static, the counter hands out what follows
+    unsigned pend = blockIdx.x + gridDim.x;   // hand-out: pf_handout.h
     const size_t last = (size_t)batch - 1;
     chunk raw[NCH];
     auto load = [&](size_t image) {
@@ -162,10 +163,7 @@ fft_fft2_kernel(const float* in, float* out, unsigned batch, float s, const cx<f
         load(t0 < last ? t0 : last);
     }
     for (unsigned it = 0; (size_t)g * SLOTS < batch; ++it) {
-        if (dyn && threadIdx.x == 0) {
-            s_next[(it + 1) & 1] = pend;
-            pend = 2u * gridDim.x + atomicAdd(&ctr[0], 1u);
-        }
+        if (dyn && threadIdx.x == 0) pend = handout_grab(s_next, it, pend, ctr);
         const size_t tr = (size_t)g * SLOTS + slot;
         const bool active = tr < batch;  // inactive slots recompute the last image and never store
         const size_t dv = active ? tr : last;
@@ -178,7 +176,7 @@ fft_fft2_kernel(const float* in, float* out, unsigned batch, float s, const cx<f
             p[1] = mk<float>(raw[i].z, raw[i].w);
         }
         __syncthreads();  // publishes s_next
-        const unsigned gn = dyn ? s_next[(it + 1) & 1] : g + gridDim.x;
+        const unsigned gn = handout_next(dyn, s_next, it, g);
         const size_t tn = (size_t)gn * SLOTS + slot, nv = tn < last ? tn : last;
         // ---- rows: lines of C points, 1 apart, PITCH from line to line
         fft2_axis<C, R, PITCH, 1, T, DIR>(img, t, w);
@@ -204,11 +202,7 @@ fft_fft2_kernel(const float* in, float* out, unsigned batch, float s, const cx<f
         if constexpr (!PF) load(nv);
         g = gn;
     }
-    if (dyn && threadIdx.x == 0) {
-        __threadfence();
-        unsigned d = atomicAdd(&ctr[1], 1u);
-        if (d == gridDim.x - 1) { atomicExch(&ctr[0], 0u); atomicExch(&ctr[1], 0u); }
-    }
+    if (dyn && threadIdx.x == 0) handout_rearm(ctr);
 }
 
 // ------------------------------------------------------------------------------------------------ composed route

@@ -7,7 +7,7 @@
 //   fft2conv_product_kernel  the COMPOSED route's kernel between the handle's own forward and backward transforms: in place, grid stride,
 //                            64-bit indices, H indexed modulo one image where it is broadcast;
 //   fft_fft2conv_kernel      the FUSED route (float, broadcast H, rows and cols in {16, 32, 64}): fft_fft2_kernel's persistent loop
-//                            (static-then-counter hand-out, s_next, inactive slots, counter reset, chunked 16-byte loads and stores;
+//                            (the hand-out of pf_handout.h, inactive slots, chunked 16-byte loads and stores;
 //                            the launch is loop_launch with CONV_ONESHOT) on Fft2Cfg / Fft2Layout as they are, ONE HBM read and ONE HBM
 //                            write per image.
 // The routes run different butterfly networks: each is held to the float64 truth at the convolution bar, not to the other bit for bit.
@@ -41,6 +41,7 @@
 // a fused per-image-H path, fused double, shapes beyond 64.
 #pragma once
 #include "fft_fft2.h"
+#include "pf_handout.h"
 
 namespace pf {
 
@@ -235,7 +236,7 @@ fft_fft2conv_kernel(const float* in, const cx<float>* __restrict__ H, float* out
 
     const bool dyn = ctr != nullptr;
     unsigned g = blockIdx.x;
-    unsigned pend = blockIdx.x + gridDim.x;   // the first two groups of a workgroup are static, the counter hands out what follows
+    unsigned pend = blockIdx.x + gridDim.x;   // hand-out: pf_handout.h
     const size_t last = (size_t)batch - 1;
     chunk raw[NCH];
     auto load = [&](size_t image) {
@@ -248,10 +249,7 @@ fft_fft2conv_kernel(const float* in, const cx<float>* __restrict__ H, float* out
         load(t0 < last ? t0 : last);
     }
     for (unsigned it = 0; (size_t)g * SLOTS < batch; ++it) {
-        if (dyn && threadIdx.x == 0) {
-            s_next[(it + 1) & 1] = pend;
-            pend = 2u * gridDim.x + atomicAdd(&ctr[0], 1u);
-        }
+        if (dyn && threadIdx.x == 0) pend = handout_grab(s_next, it, pend, ctr);
         const size_t tr = (size_t)g * SLOTS + slot;
         const bool active = tr < batch;  // inactive slots recompute the last image and never store
         const size_t dv = active ? tr : last;
@@ -264,7 +262,7 @@ fft_fft2conv_kernel(const float* in, const cx<float>* __restrict__ H, float* out
             p[1] = mk<float>(raw[i].z, raw[i].w);
         }
         __syncthreads();  // publishes s_next
-        const unsigned gn = dyn ? s_next[(it + 1) & 1] : g + gridDim.x;
+        const unsigned gn = handout_next(dyn, s_next, it, g);
         const size_t tn = (size_t)gn * SLOTS + slot, nv = tn < last ? tn : last;
         // ---- rows forward: lines of C points, 1 apart, PITCH from line to line
         fft2_axis<C, R, PITCH, 1, T, FWD>(img, t, w);
@@ -294,11 +292,7 @@ fft_fft2conv_kernel(const float* in, const cx<float>* __restrict__ H, float* out
         if constexpr (!PF) load(nv);
         g = gn;
     }
-    if (dyn && threadIdx.x == 0) {
-        __threadfence();
-        unsigned d = atomicAdd(&ctr[1], 1u);
-        if (d == gridDim.x - 1) { atomicExch(&ctr[0], 0u); atomicExch(&ctr[1], 0u); }
-    }
+    if (dyn && threadIdx.x == 0) handout_rearm(ctr);
 }
 
 }  // namespace pf

@@ -14,6 +14,7 @@
 // (canonical order, pre-scaled by 1/Nfft) sits in registers for the whole persistent loop.
 #pragma once
 #include "fft_tiled.h"
+#include "pf_handout.h"
 
 namespace pf {
 
@@ -74,8 +75,7 @@ fastconv_fused_kernel(const float* __restrict__ x, float* __restrict__ y, const 
     const bool dyn = ctr != nullptr;
     unsigned pend = 0;
     unsigned g = blockIdx.x;
-    // (the first two groups of a workgroup are static - its index, and that plus the grid -, the counter hands out what follows: fft_tiled.h)
-    pend = blockIdx.x + gridDim.x;
+    pend = blockIdx.x + gridDim.x;   // hand-out: pf_handout.h
     const long long nblk_all = (long long)nblk * nsig;
     // ---- gather of block group grp: stage-0 operand order, zero beyond the end of the signal (src/pffastconv.c:231-233).
     //      The FIRST block's samples are requested before anything else: the twiddle / filter tables below are cold on a call
@@ -115,10 +115,7 @@ fastconv_fused_kernel(const float* __restrict__ x, float* __restrict__ y, const 
 #pragma unroll
         for (int d = 0; d < RL; ++d) h[u * RL + d] = Hc[KF::template jm<NS - 1>(t, u) + d * (n / RL)];
     for (unsigned it = 0; (long long)g * C::T_PER_WG < nblk_all; ++it) {
-        if (dyn && threadIdx.x == 0) {
-            s_next[(it + 1) & 1] = pend;
-            pend = 2u * gridDim.x + atomicAdd(&ctr[0], 1u);
-        }
+        if (dyn && threadIdx.x == 0) pend = handout_grab(s_next, it, pend, ctr);
         const long long blk_all = (long long)g * C::T_PER_WG + slot;
         const bool active = blk_all < nblk_all;
         int sig = nsig - 1, blk = nblk - 1;
@@ -139,7 +136,7 @@ fastconv_fused_kernel(const float* __restrict__ x, float* __restrict__ y, const 
         KF::template xwrite<0>(v, t, img);
         __syncthreads();
         PF_STAMP(3);
-        const unsigned gn = dyn ? s_next[(it + 1) & 1] : g + gridDim.x;
+        const unsigned gn = handout_next(dyn, s_next, it, g);
         KF::template xread<0>(v, t, img); KF::xsync(); KF::template butterflies<1>(v, t, wf, twg);
         if constexpr (NS > 2) { KF::template xwrite<1>(v, t, img); KF::xsync(); KF::template xread<1>(v, t, img); KF::xsync(); KF::template butterflies<2>(v, t, wf, twg); }
         if constexpr (NS > 3) { KF::template xwrite<2>(v, t, img); KF::xsync(); KF::template xread<2>(v, t, img); KF::xsync(); KF::template butterflies<3>(v, t, wf, twg); }
@@ -193,11 +190,7 @@ fastconv_fused_kernel(const float* __restrict__ x, float* __restrict__ y, const 
         g = gn;
         if ((long long)g * C::T_PER_WG < nblk_all) gather(g);
     }
-    if (dyn && threadIdx.x == 0) {
-        __threadfence();
-        unsigned d = atomicAdd(&ctr[1], 1u);
-        if (d == gridDim.x - 1) { atomicExch(&ctr[0], 0u); atomicExch(&ctr[1], 0u); }
-    }
+    if (dyn && threadIdx.x == 0) handout_rearm(ctr);
     (void)Nfft;
 }
 

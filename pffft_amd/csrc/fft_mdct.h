@@ -24,6 +24,7 @@
 #pragma once
 #include "fft_tiled.h"
 #include "fft_dct.h"   // Quad, Duo
+#include "pf_handout.h"
 
 namespace pf {
 
@@ -134,7 +135,7 @@ fft_mdct_kernel(const float* in, size_t in_stride, unsigned nframes, const float
 
     const bool dyn = ctr != nullptr;
     unsigned g = blockIdx.x;
-    unsigned pend = blockIdx.x + gridDim.x;   // the first two groups of a workgroup are static, the counter hands out what follows
+    unsigned pend = blockIdx.x + gridDim.x;   // hand-out: pf_handout.h
     __syncthreads();
     const size_t last = (size_t)batch - 1;
     auto src_of = [&](size_t tr) -> const T* {
@@ -162,10 +163,7 @@ fft_mdct_kernel(const float* in, size_t in_stride, unsigned nframes, const float
     };
     load(src_of((size_t)g * C::T_PER_WG + slot));
     for (unsigned it = 0; (size_t)g * C::T_PER_WG < batch; ++it) {
-        if (dyn && threadIdx.x == 0) {
-            s_next[(it + 1) & 1] = pend;
-            pend = 2u * gridDim.x + atomicAdd(&ctr[0], 1u);
-        }
+        if (dyn && threadIdx.x == 0) pend = handout_grab(s_next, it, pend, ctr);
         const size_t tr = (size_t)g * C::T_PER_WG + slot;
         const bool active = tr < batch;  // inactive slots recompute the last row and never store
         T* dst = out + (active ? tr : last) * out_stride;
@@ -213,7 +211,7 @@ fft_mdct_kernel(const float* in, size_t in_stride, unsigned nframes, const float
         K::template butterflies<0>(v, t, w, twt);
         if constexpr (C::NS > 1) K::template xwrite<0>(v, t, img);
         __syncthreads();  // publishes s_next; first half of exchange 0
-        const unsigned gn = dyn ? s_next[(it + 1) & 1] : g + gridDim.x;
+        const unsigned gn = handout_next(dyn, s_next, it, g);
         if constexpr (C::PREFETCH) load(src_of((size_t)gn * C::T_PER_WG + slot));
         if constexpr (C::NS > 1) { K::template xread<0>(v, t, img); K::xsync(); K::template butterflies<1>(v, t, w, twt); }
         if constexpr (C::NS > 2) { K::template xwrite<1>(v, t, img); K::xsync(); K::template xread<1>(v, t, img); K::xsync(); K::template butterflies<2>(v, t, w, twt); }
@@ -251,11 +249,7 @@ fft_mdct_kernel(const float* in, size_t in_stride, unsigned nframes, const float
         if constexpr (!C::PREFETCH) load(src_of((size_t)gn * C::T_PER_WG + slot));
         g = gn;
     }
-    if (dyn && threadIdx.x == 0) {
-        __threadfence();
-        unsigned d = atomicAdd(&ctr[1], 1u);
-        if (d == gridDim.x - 1) { atomicExch(&ctr[0], 0u); atomicExch(&ctr[1], 0u); }
-    }
+    if (dyn && threadIdx.x == 0) handout_rearm(ctr);
 }
 
 // LDS of fft_mdct_kernel: the images and the counter slot of fft_tiled_kernel (these configurations have no twiddle table); the frame

@@ -32,6 +32,7 @@
 #include "fft_c1024.h"
 #include "fft_frames.h"
 #include "fft_fir.h"
+#include "pf_handout.h"
 
 namespace pf {
 
@@ -80,7 +81,7 @@ fft_pfb_c1024_kernel(const float* signal, size_t signal_stride, unsigned nframes
     C w1[7][2], w2[15];
     c1024_load_twiddles(twg, L, w1, w2);
     for (unsigned i = threadIdx.x; i < taps * 512u; i += C1024_WAVES * 64) htab[i] = reinterpret_cast<const vec2<float>*>(prototype)[i];
-    unsigned pend = blockIdx.x + gridDim.x;   // the first two groups of a workgroup are static, the counter hands out what follows
+    unsigned pend = blockIdx.x + gridDim.x;   // hand-out: pf_handout.h
     __syncthreads();
     unsigned g = blockIdx.x;
     const size_t last = (size_t)batch - 1;
@@ -96,10 +97,7 @@ fft_pfb_c1024_kernel(const float* signal, size_t signal_stride, unsigned nframes
     for (int q = 0; q < PFB_SLOTS; ++q)
         if ((unsigned)q < taps) pfb_load_tap(slot[q], cur, q, L);
     for (unsigned it = 0; (size_t)g * C1024_WAVES < batch; ++it) {
-        if (threadIdx.x == 0) {  // publish the index of iteration it+1, grab the one of it+2
-            s_next[(it + 1) & 1] = pend;
-            pend = 2u * gridDim.x + atomicAdd(&ctr[0], 1u);
-        }
+        if (threadIdx.x == 0) pend = handout_grab(s_next, it, pend, ctr);
         const size_t t = (size_t)g * C1024_WAVES + wave;
         const bool active = t < batch;  // wave-uniform
         // ---- the fold: slot q holds tap p0 + q; a consumed slot is refilled with tap p + PFB_SLOTS of the same frame
@@ -116,7 +114,7 @@ fft_pfb_c1024_kernel(const float* signal, size_t signal_stride, unsigned nframes
         }
         c1024_part_a<FWD, 0>(raw, wl, wf, w1, L);
         __syncthreads();
-        const unsigned gn = s_next[(it + 1) & 1];
+        const unsigned gn = s_next[(it + 1) & 1];   // hand-out: pf_handout.h, kept inline: handout_next(true, ..) changes this kernel
         cur = frame_of((size_t)gn * C1024_WAVES + wave);
 #pragma unroll
         for (int q = 0; q < PFB_SLOTS; ++q)
@@ -124,11 +122,7 @@ fft_pfb_c1024_kernel(const float* signal, size_t signal_stride, unsigned nframes
         if (active) c1024_part_b<FWD, OUT_INTERNAL>(out + t * out_stride, 0, wl, wf, w2, L);
         g = gn;
     }
-    if (threadIdx.x == 0) {
-        __threadfence();  // my last (unused) grab has landed before I report done
-        unsigned d = atomicAdd(&ctr[1], 1u);
-        if (d == gridDim.x - 1) { atomicExch(&ctr[0], 0u); atomicExch(&ctr[1], 0u); }
-    }
+    if (threadIdx.x == 0) handout_rearm(ctr);
 }
 
 // ------------------------------------------------------------------------------------------------ composed route

@@ -14,6 +14,7 @@
 // No atomics, no FMA (the library is built with -ffp-contract=off), so both routes give the same bits.
 #pragma once
 #include "fft_frames.h"
+#include "pf_handout.h"
 
 namespace pf {
 
@@ -58,7 +59,7 @@ fft_psd_kernel(const float* signal, size_t signal_stride, unsigned G, unsigned n
     }
     const bool dyn = ctr != nullptr;
     unsigned g = blockIdx.x;
-    unsigned pend = blockIdx.x + gridDim.x;   // the first two groups of a workgroup are static, the counter hands out what follows
+    unsigned pend = blockIdx.x + gridDim.x;   // hand-out: pf_handout.h
     __syncthreads();
     const unsigned rpg = (navg + PSD_RUN - 1) / PSD_RUN;
     const size_t last = (size_t)nruns - 1;
@@ -89,10 +90,7 @@ fft_psd_kernel(const float* signal, size_t signal_stride, unsigned G, unsigned n
     chunk16 raw[NCH];
     K::load_raw(raw, base, t, true);
     for (unsigned it = 0; (size_t)g * C::T_PER_WG < nruns; ++it) {
-        if (dyn && threadIdx.x == 0) {
-            s_next[(it + 1) & 1] = pend;
-            pend = 2u * gridDim.x + atomicAdd(&ctr[0], 1u);
-        }
+        if (dyn && threadIdx.x == 0) pend = handout_grab(s_next, it, pend, ctr);
         const size_t tr = (size_t)g * C::T_PER_WG + slot;
         const bool active = tr < nruns;
         unsigned gn = 0;
@@ -125,7 +123,7 @@ fft_psd_kernel(const float* signal, size_t signal_stride, unsigned G, unsigned n
             K::template butterflies<0>(v, t, w, twt);
             if constexpr (C::NS > 1) K::template xwrite<0>(v, t, img);
             __syncthreads();  // publishes s_next; first half of exchange 0
-            if (fi == 0) gn = dyn ? s_next[(it + 1) & 1] : g + gridDim.x;
+            if (fi == 0) gn = handout_next(dyn, s_next, it, g);
             // what follows: the run's next frame (a shorter run repeats its last one), after the group's last pass the next run's first
             const T* nsrc;
             if (fi + 1 < bound) nsrc = base + (size_t)(fi + 1 < len ? fi + 1 : len - 1) * hop;
@@ -174,11 +172,7 @@ fft_psd_kernel(const float* signal, size_t signal_stride, unsigned G, unsigned n
         len = len_of((size_t)g * C::T_PER_WG + slot);
         bound = bound_of(g);
     }
-    if (dyn && threadIdx.x == 0) {
-        __threadfence();
-        unsigned d = atomicAdd(&ctr[1], 1u);
-        if (d == gridDim.x - 1) { atomicExch(&ctr[0], 0u); atomicExch(&ctr[1], 0u); }
-    }
+    if (dyn && threadIdx.x == 0) handout_rearm(ctr);
 }
 
 // ------------------------------------------------------------------------------------------------ composed route

@@ -4,8 +4,8 @@
 // columns 0 and cols / 2 counts).  Dense row-major images, natural order in and out.  This file holds
 //   fft_rfft2_kernel     the FUSED route (float; rows in {16, 32, 64}, cols in {32, 64}): whole images live in LDS, ONE HBM read and ONE
 //                        HBM write per image (4 R C bytes on the real side, 8 R bins on the spectrum side), on the persistent loop of the
-//                        fused family exactly as fft_fft2_kernel runs it (static-then-counter hand-out, s_next, inactive slots, counter
-//                        reset; the launch is loop_launch with CONV_ONESHOT).
+//                        fused family exactly as fft_fft2_kernel runs it (the hand-out of pf_handout.h, inactive slots; the launch is
+//                        loop_launch with CONV_ONESHOT).
 //   rfft2_unpack_kernel, rfft2_pack_kernel   the COMPOSED route's kernels between the real transform_batch over the rows and the complex
 //                        one over the columns (rfft2_tu.hip): canonical packed real spectra [rows][cols] (element 0 DC, element 1 Nyquist,
 //                        then re / im pairs) <-> [bins][rows] complex, through padded 32 x 32 LDS tiles like fft2_transpose_kernel.
@@ -41,6 +41,7 @@
 // tiles, transforms along one axis only, multi-device shards of one setup, 3-D.
 #pragma once
 #include "fft_fft2.h"
+#include "pf_handout.h"
 
 namespace pf {
 
@@ -105,7 +106,7 @@ fft_rfft2_kernel(const float* in, float* out, unsigned batch, float s, const cx<
 
     const bool dyn = ctr != nullptr;
     unsigned g = blockIdx.x;
-    unsigned pend = blockIdx.x + gridDim.x;   // the first two groups of a workgroup are static, the counter hands out what follows
+    unsigned pend = blockIdx.x + gridDim.x;   // hand-out: pf_handout.h
     const size_t last = (size_t)batch - 1;
     chunk raw[NI_IN];
 #pragma unroll
@@ -123,10 +124,7 @@ fft_rfft2_kernel(const float* in, float* out, unsigned batch, float s, const cx<
         load(t0 < last ? t0 : last);
     }
     for (unsigned it = 0; (size_t)g * SLOTS < batch; ++it) {
-        if (dyn && threadIdx.x == 0) {
-            s_next[(it + 1) & 1] = pend;
-            pend = 2u * gridDim.x + atomicAdd(&ctr[0], 1u);
-        }
+        if (dyn && threadIdx.x == 0) pend = handout_grab(s_next, it, pend, ctr);
         const size_t tr = (size_t)g * SLOTS + slot;
         const bool active = tr < batch;  // inactive slots recompute the last image and never store
         const size_t dv = active ? tr : last;
@@ -152,7 +150,7 @@ fft_rfft2_kernel(const float* in, float* out, unsigned batch, float s, const cx<
             }
         }
         __syncthreads();  // publishes s_next
-        const unsigned gn = dyn ? s_next[(it + 1) & 1] : g + gridDim.x;
+        const unsigned gn = handout_next(dyn, s_next, it, g);
         const size_t tn = (size_t)gn * SLOTS + slot, nv = tn < last ? tn : last;
         if constexpr (!DIR) {
             // ---- rows: R / 2 lines of C points, 1 apart, PITCH from line to line
@@ -261,11 +259,7 @@ fft_rfft2_kernel(const float* in, float* out, unsigned batch, float s, const cx<
         if constexpr (!PF) load(nv);
         g = gn;
     }
-    if (dyn && threadIdx.x == 0) {
-        __threadfence();
-        unsigned d = atomicAdd(&ctr[1], 1u);
-        if (d == gridDim.x - 1) { atomicExch(&ctr[0], 0u); atomicExch(&ctr[1], 0u); }
-    }
+    if (dyn && threadIdx.x == 0) handout_rearm(ctr);
 }
 
 // ------------------------------------------------------------------------------------------------ composed route

@@ -5,7 +5,7 @@
 // columns 0 and cols / 2 counts.  The COMPOSED route is host code (rfft2_tu.hip): the handle's forward transform into a scratch of
 // half-spectra, fft2conv_product_kernel of fft_fft2c.h in place there, the handle's backward transform.  This file holds
 //   fft_rfft2conv_kernel   the FUSED route (float, broadcast H, rows in {16, 32, 64}, cols in {32, 64}): fft_rfft2_kernel's persistent
-//                          loop (static-then-counter hand-out, s_next, inactive slots, counter reset, chunked 16-byte loads and stores;
+//                          loop (the hand-out of pf_handout.h, inactive slots, chunked 16-byte loads and stores;
 //                          the launch is loop_launch with CONV_ONESHOT) on Rfft2Cfg / Rfft2Layout as they are, ONE HBM read and ONE HBM
 //                          write of 4 rows cols bytes per image.
 // The routes run different butterfly networks: each is held to the float64 truth at the convolution bar, not to the other bit for bit.
@@ -52,6 +52,7 @@
 #pragma once
 #include "fft_fft2c.h"
 #include "fft_rfft2.h"
+#include "pf_handout.h"
 
 namespace pf {
 
@@ -239,7 +240,7 @@ fft_rfft2conv_kernel(const float* in, const cx<float>* __restrict__ H, float* ou
 
     const bool dyn = ctr != nullptr;
     unsigned g = blockIdx.x;
-    unsigned pend = blockIdx.x + gridDim.x;   // the first two groups of a workgroup are static, the counter hands out what follows
+    unsigned pend = blockIdx.x + gridDim.x;   // hand-out: pf_handout.h
     const size_t last = (size_t)batch - 1;
     chunk raw[NI];
     auto load = [&](size_t image) {
@@ -254,10 +255,7 @@ fft_rfft2conv_kernel(const float* in, const cx<float>* __restrict__ H, float* ou
         load(t0 < last ? t0 : last);
     }
     for (unsigned it = 0; (size_t)g * SLOTS < batch; ++it) {
-        if (dyn && threadIdx.x == 0) {
-            s_next[(it + 1) & 1] = pend;
-            pend = 2u * gridDim.x + atomicAdd(&ctr[0], 1u);
-        }
+        if (dyn && threadIdx.x == 0) pend = handout_grab(s_next, it, pend, ctr);
         const size_t tr = (size_t)g * SLOTS + slot;
         const bool active = tr < batch;  // inactive slots recompute the last image and never store
         const size_t dv = active ? tr : last;
@@ -278,7 +276,7 @@ fft_rfft2conv_kernel(const float* in, const cx<float>* __restrict__ H, float* ou
             }
         }
         __syncthreads();  // publishes s_next
-        const unsigned gn = dyn ? s_next[(it + 1) & 1] : g + gridDim.x;
+        const unsigned gn = handout_next(dyn, s_next, it, g);
         // the next image's index is formed where its chunks are requested: one register (gn) crosses the pass, not a 64-bit index
         auto next_image = [&]() {
             const size_t tn = (size_t)gn * SLOTS + slot;
@@ -359,11 +357,7 @@ fft_rfft2conv_kernel(const float* in, const cx<float>* __restrict__ H, float* ou
         if constexpr (!PF) load(next_image());
         g = gn;
     }
-    if (dyn && threadIdx.x == 0) {
-        __threadfence();
-        unsigned d = atomicAdd(&ctr[1], 1u);
-        if (d == gridDim.x - 1) { atomicExch(&ctr[0], 0u); atomicExch(&ctr[1], 0u); }
-    }
+    if (dyn && threadIdx.x == 0) handout_rearm(ctr);
 }
 
 }  // namespace pf

@@ -26,6 +26,7 @@
 #pragma once
 #include "cxmath.h"
 #include "fft_generic.h"  // bin_of
+#include "pf_handout.h"
 
 namespace pf {
 
@@ -491,10 +492,7 @@ fft_tiled_kernel(const typename C::real_t* in, typename C::real_t* out, unsigned
     const bool dyn = ctr != nullptr;
     unsigned pend = 0;
     unsigned g = blockIdx.x;
-    // the first TWO groups of a workgroup are static (its index, and that plus the grid); the counter hands out what follows: value v =
-    // group 2 grid + v.  (Every workgroup used to open with two grabs: ~2 000 atomics on one address, served at ~80 M/s, stood between the
-    // launch and the last workgroup's first load - 25-35 us of every launch, tools/r4_small_batch.py.)
-    pend = blockIdx.x + gridDim.x;
+    pend = blockIdx.x + gridDim.x;   // hand-out: pf_handout.h
     __syncthreads();
     const size_t last = (size_t)batch - 1;
     chunk16 raw[NCH];
@@ -503,10 +501,7 @@ fft_tiled_kernel(const typename C::real_t* in, typename C::real_t* out, unsigned
         K::load_raw(raw, in + (t0 < last ? t0 : last) * 2 * (size_t)n, t, plain_in);
     }
     for (unsigned it = 0; (size_t)g * C::T_PER_WG < batch; ++it) {
-        if (dyn && threadIdx.x == 0) {
-            s_next[(it + 1) & 1] = pend;
-            pend = 2u * gridDim.x + atomicAdd(&ctr[0], 1u);
-        }
+        if (dyn && threadIdx.x == 0) pend = handout_grab(s_next, it, pend, ctr);
         const size_t tr = (size_t)g * C::T_PER_WG + slot;
         const bool active = tr < batch;  // inactive slots recompute the last vector and never store
         T* dst = out + (active ? tr : last) * 2 * (size_t)n;
@@ -586,7 +581,7 @@ fft_tiled_kernel(const typename C::real_t* in, typename C::real_t* out, unsigned
         if constexpr (C::NS > 1) K::template xwrite<0>(v, t, img);
         __syncthreads();  // publishes s_next; first half of exchange 0
         PF_TSTAMP(3);
-        const unsigned gn = dyn ? s_next[(it + 1) & 1] : g + gridDim.x;
+        const unsigned gn = handout_next(dyn, s_next, it, g);
         if constexpr (C::PREFETCH) {  // the loads of the next transform fly while this one is finished
             const size_t tn = (size_t)gn * C::T_PER_WG + slot;
             K::load_raw(raw, in + (tn < last ? tn : last) * 2 * (size_t)n, t, plain_in);
@@ -688,11 +683,7 @@ fft_tiled_kernel(const typename C::real_t* in, typename C::real_t* out, unsigned
         }
         g = gn;
     }
-    if (dyn && threadIdx.x == 0) {
-        __threadfence();
-        unsigned d = atomicAdd(&ctr[1], 1u);
-        if (d == gridDim.x - 1) { atomicExch(&ctr[0], 0u); atomicExch(&ctr[1], 0u); }
-    }
+    if (dyn && threadIdx.x == 0) handout_rearm(ctr);
 }
 
 // ---- configurations: <T, log2 n, threads/transform, stages, R0..R3, PAD0, PADN, TWMODE, PREFETCH> ----

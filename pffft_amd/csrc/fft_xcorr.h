@@ -5,8 +5,8 @@
 //                       PHAT weighting c / |c| with its zero rule;
 //   XcorrIO             the two ends of the fused kernel: predicated element-sized loads of a row of `len` elements (zeros beyond), and
 //                       the scatter of the lag window, times s;
-//   fft_xcorr_kernel    the FUSED route - fft_conv_kernel's persistent loop (static-then-counter hand-out, s_next, inactive slots, counter
-//                       reset) around the forward stage sequence run TWICE per row pair (x, whose bins stay in registers, then y through
+//   fft_xcorr_kernel    the FUSED route - fft_conv_kernel's persistent loop (the hand-out of pf_handout.h, inactive slots)
+//                       around the forward stage sequence run TWICE per row pair (x, whose bins stay in registers, then y through
 //                       the same LDS image), the product and the backward sequence.  AUTO runs the forward sequence once.
 //   xcorr_pad_kernel / xcorr_product_kernel / xcorr_crop_kernel: the COMPOSED route's kernels around two transform_batch calls.
 // The routes run different butterfly networks (the register-tiled halves here, whatever transform_batch picks there): they agree at the
@@ -14,6 +14,7 @@
 // c_im = a - a = +0.
 #pragma once
 #include "fft_analytic.h"   // analytic_envelope: |c| in the one form every route uses
+#include "pf_handout.h"
 
 namespace pf {
 
@@ -149,7 +150,7 @@ fft_xcorr_kernel(const IO io, unsigned batch, int weight, const cx<typename C::r
 
     const bool dyn = ctr != nullptr;
     unsigned g = blockIdx.x;
-    unsigned pend = blockIdx.x + gridDim.x;   // the first two groups of a workgroup are static, the counter hands out what follows
+    unsigned pend = blockIdx.x + gridDim.x;   // hand-out: pf_handout.h
     __syncthreads();
     const size_t last = (size_t)batch - 1;
     chunk16 raw[NCH];
@@ -158,10 +159,7 @@ fft_xcorr_kernel(const IO io, unsigned batch, int weight, const cx<typename C::r
         io.load_x(raw, t0 < last ? t0 : last, t);
     }
     for (unsigned it = 0; (size_t)g * C::T_PER_WG < batch; ++it) {
-        if (dyn && threadIdx.x == 0) {
-            s_next[(it + 1) & 1] = pend;
-            pend = 2u * gridDim.x + atomicAdd(&ctr[0], 1u);
-        }
+        if (dyn && threadIdx.x == 0) pend = handout_grab(s_next, it, pend, ctr);
         const size_t tr = (size_t)g * C::T_PER_WG + slot;
         const bool active = tr < batch;  // inactive slots recompute the last row pair and never store
         const size_t dv = active ? tr : last;
@@ -178,7 +176,7 @@ fft_xcorr_kernel(const IO io, unsigned batch, int weight, const cx<typename C::r
         KF::template butterflies<0>(v, t, wf, twt);
         KF::template xwrite<0>(v, t, img);
         __syncthreads();  // publishes s_next; first half of exchange 0
-        const unsigned gn = dyn ? s_next[(it + 1) & 1] : g + gridDim.x;
+        const unsigned gn = handout_next(dyn, s_next, it, g);
         const size_t tn = (size_t)gn * C::T_PER_WG + slot, nv = tn < last ? tn : last;
         if constexpr (!AUTO) io.load_y(raw, dv, t);
         else if constexpr (XPF) io.load_x(raw, nv, t);
@@ -212,11 +210,7 @@ fft_xcorr_kernel(const IO io, unsigned batch, int weight, const cx<typename C::r
         if constexpr (!XPF) io.load_x(raw, nv, t);
         g = gn;
     }
-    if (dyn && threadIdx.x == 0) {
-        __threadfence();
-        unsigned d = atomicAdd(&ctr[1], 1u);
-        if (d == gridDim.x - 1) { atomicExch(&ctr[0], 0u); atomicExch(&ctr[1], 0u); }
-    }
+    if (dyn && threadIdx.x == 0) handout_rearm(ctr);
 }
 
 // ------------------------------------------------------------------------------------------------ composed route

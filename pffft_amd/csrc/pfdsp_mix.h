@@ -15,6 +15,8 @@
 #include <mutex>
 #include <string>
 
+#include "pf_handout.h"
+
 namespace pfmix {
 
 static thread_local std::string last_error;
@@ -107,7 +109,7 @@ mix_pairs_kernel(const f32x4* __restrict__ in, f32x4* __restrict__ out, unsigned
 // persistent workgroups of 8 wavefronts pull groups of 8 consecutive 8 KiB chunks from an atomic counter, so the chip
 // sweeps the stream in order (a copy with this pattern: 6.9 TB/s; hardware dispatch order: 5.5-6.0).  A wave moves 8 rows
 // of 1 KiB (one 16-byte access per lane and row); the phase is reduced once per chunk and lane, the other rows follow by
-// constant rotations.  ctr[0] = next group, ctr[1] = workgroups finished (the last one re-arms the pair).
+// constant rotations.  The groups are handed out as pf_handout.h describes.
 constexpr int MIX_DYN_WAVES = 8;
 constexpr unsigned long long MIX_CHUNK_PAIRS = 64ull * MIX_DYN_ROWS;   // 512 pairs = 1024 samples = 8 KiB
 
@@ -119,10 +121,7 @@ mix_dyn_kernel(const f32x4* in, f32x4* out, unsigned nchunks, MixArgs a, unsigne
     const int l0 = (2 * lane) % LANES;
     const float2 s0 = a.S[l0], s1 = a.S[LANES == 1 ? 0 : l0 + 1];
     unsigned pend = 0;
-    // the first TWO groups of a workgroup are static (its index, and that plus the grid); the counter hands out what follows: value v =
-    // group 2 grid + v.  (Every workgroup used to open with two grabs: ~2 000 atomics on one address, served at ~80 M/s, stood between the
-    // launch and the last workgroup's first load - 25-35 us of every launch, tools/r4_small_batch.py.)
-    pend = blockIdx.x + gridDim.x;
+    pend = blockIdx.x + gridDim.x;   // hand-out: pf_handout.h
     __syncthreads();
     unsigned g = blockIdx.x;
     const unsigned long long lastc = (unsigned long long)nchunks - 1;
@@ -134,12 +133,9 @@ mix_dyn_kernel(const f32x4* in, f32x4* out, unsigned nchunks, MixArgs a, unsigne
         for (int r = 0; r < MIX_DYN_ROWS; ++r) x[r] = GEN ? f32x4{1.f, 0.f, 1.f, 0.f} : __builtin_nontemporal_load(src + 64 * r);
     }
     for (unsigned it = 0; (unsigned long long)g * MIX_DYN_WAVES < nchunks; ++it) {
-        if (threadIdx.x == 0) {   // publish the group of iteration it+1, grab the one of it+2 (latency never exposed)
-            s_next[(it + 1) & 1] = pend;
-            pend = 2u * gridDim.x + atomicAdd(&ctr[0], 1u);
-        }
+        if (threadIdx.x == 0) pend = pf::handout_grab(s_next, it, pend, ctr);
         __syncthreads();
-        const unsigned gn = s_next[(it + 1) & 1];
+        const unsigned gn = s_next[(it + 1) & 1];   // hand-out: pf_handout.h, kept inline: handout_next(true, ..) changes this kernel
         const unsigned long long c = (unsigned long long)g * MIX_DYN_WAVES + wave;
         const unsigned long long cn = (unsigned long long)gn * MIX_DYN_WAVES + wave;
         f32x4 xn[MIX_DYN_ROWS];
@@ -166,11 +162,7 @@ mix_dyn_kernel(const f32x4* in, f32x4* out, unsigned nchunks, MixArgs a, unsigne
         for (int r = 0; r < MIX_DYN_ROWS; ++r) x[r] = xn[r];
         g = gn;
     }
-    if (threadIdx.x == 0) {
-        __threadfence();
-        unsigned d = atomicAdd(&ctr[1], 1u);
-        if (d == gridDim.x - 1) { atomicExch(&ctr[0], 0u); atomicExch(&ctr[1], 0u); }
-    }
+    if (threadIdx.x == 0) pf::handout_rearm(ctr);
 }
 
 // one ring of {next, done} counter pairs per device, created at the first long stream
