@@ -758,6 +758,54 @@ int pffftd_hip_xcorr_batch(PFFFTD_HIP_XcorrSetup *, const double *x, const doubl
  * selector; "" for an invalid handle or another weight. */
 const char *pffft_hip_xcorr_route(const void *setup, int weight, int is_auto);
 
+/* ---- batched Fourier resampling of rows: N samples in, M samples out over the same span (scipy.signal.resample(x, M))
+ * Matching a capture to the length a later setup takes, 2x / 4x / 8x interpolation before peak picking or delay estimation, decimating
+ * a band-limited block.  A setup fixes
+ *   N, M                  any lengths pffft[d]_new_setup(., PFFFT_COMPLEX) takes (so K = min(N, M) is even)
+ *   real_rows             non-zero: rows of N scalars in and M scalars out; zero: rows of interleaved (re, im) pairs in and out
+ * NULL for anything else.  Creating a setup touches no device; the handle owns a complex setup of N and one of M (one where N == M) and
+ * has no tables.  With X = DFT_N(x) (forward, unscaled) and h = K / 2 the M-point spectrum Y is
+ *     Y[k] = X[k], 0 <= k < h;      Y[M - k] = X[N - k], 1 <= k < h;      every other bin but those below is +0
+ *     N == M: Y[h] = X[h];    M < N: Y[h] = X[h] + X[N - h] (one addition per component, no fused multiply-add);
+ *     M > N: Y[h] = Y[M - h] = 0.5 X[h] (exact)
+ *     out = s IDFT_M(Y) (backward, unscaled),  s = (T)(scaling / N) formed in double, rounded once, ONE product per component
+ * Real rows: the real part of the same sum (the result of a real row is real in exact arithmetic).  scaling = 1 is
+ * scipy.signal.resample(x, M): rows are periodic blocks, no window, no continuity between rows.
+ * in, out are device pointers, non-NULL for batch > 0, aligned to ONE ELEMENT (4 / 8 bytes real, 8 / 16 bytes complex, float / double),
+ * rows dense.  out must not overlap in: there is no in-place form, not even at N == M.  batch == 0 binds the device and returns 0.  The
+ * call is asynchronous on `stream`; 0, else a hipError_t with its text in pffft_hip_last_error().  Validation happens before any device
+ * is touched: a NULL or foreign handle or the other precision's (hipErrorInvalidHandle), NULL pointers, misalignment, overlap
+ * (hipErrorInvalidValue) -> nothing launched.
+ * Routes (pffft_hip_resample_route names the one a call takes under the calling thread's selector):
+ *   "fused"     float, both kinds, N != M with both lengths from 512 / 1024 / 2048 / 4096: ONE kernel, 8N + 8M bytes of HBM per complex
+ *               row (4N + 4M real), no scratch buffer.  Two register-tiled halves of different lengths joined in LDS: a workgroup slot
+ *               of the larger length's threads takes r = max / min rows, runs the smaller transform on r sub-slots at once and the
+ *               larger one r times, the cropped / zero-filled spectra crossing between them in natural order through the slot's LDS
+ *               image.  Which cells run it by default is a measured table; pffft_hip_set_variant(157) runs it
+ *               wherever it is legal, 156 never.
+ *   "composed"  every setup: (real: a widening kernel,) a forward pffft[d]_hip_transform_batch (ordered) at N into a per-stream scratch
+ *               buffer, a map kernel that writes every one of the M bins times s, a backward transform_batch (ordered) at M (complex:
+ *               straight into out; real: a narrowing kernel).  N + M complex values of scratch per row, at most 256 MiB (longer
+ *               batches go through it in chunks on the stream); a call that would have to grow it on a capturing stream returns
+ *               hipErrorStreamCaptureUnsupported before any launch: run the call once before capturing.
+ * The routes run different butterfly networks: they agree at the accuracy bar, not bit for bit.  Within a route the real kind equals
+ * the real parts of the complex kind on the widened rows bit for bit.
+ * A setup serves ONE device, the one that is current at the first call (hipErrorInvalidDevice from another); any number of streams and
+ * threads of that device may share it.  THE FIRST CALL ON A SETUP BINDS IT (and the inner setups build their device tables at their
+ * first use): make it BEFORE a stream capture - during one it fails with hipErrorStreamCaptureUnsupported and launches nothing.
+ * Lengths the complex setup refuses, a spectral window, streaming continuity between rows, strided rows, two real rows per complex
+ * transform, in-place operation and a fused double or other-length kernel are not offered. */
+typedef struct PFFFT_HIP_ResampleSetup PFFFT_HIP_ResampleSetup;
+typedef struct PFFFTD_HIP_ResampleSetup PFFFTD_HIP_ResampleSetup;
+PFFFT_HIP_ResampleSetup *pffft_hip_resample_new_setup(int N, int M, int real_rows);
+PFFFTD_HIP_ResampleSetup *pffftd_hip_resample_new_setup(int N, int M, int real_rows);
+void pffft_hip_resample_destroy_setup(PFFFT_HIP_ResampleSetup *);     /* NULL-safe */
+void pffftd_hip_resample_destroy_setup(PFFFTD_HIP_ResampleSetup *);
+int pffft_hip_resample_batch(PFFFT_HIP_ResampleSetup *, const float *in, float *out, size_t batch, float scaling, void *stream);
+int pffftd_hip_resample_batch(PFFFTD_HIP_ResampleSetup *, const double *in, double *out, size_t batch, double scaling, void *stream);
+/* Host arithmetic only, handles of both precisions: "fused" / "composed" under the calling thread's selector; "" for an invalid handle. */
+const char *pffft_hip_resample_route(const void *setup);
+
 /* ---- batched 2-D complex transforms (numpy.fft.fft2 of a batch of images)
  * pffft[d]_hip_fft2_new_setup(rows, cols): both lengths must be ones a complex setup of that precision takes, NULL otherwise.  Creating a
  * setup touches no device; the handle owns one inner complex setup per distinct length (rows == cols shares one) and has no tables.

@@ -126,6 +126,10 @@ def lib():
         g("hip_xcorr_destroy_setup").restype = None; g("hip_xcorr_destroy_setup").argtypes = [C.c_void_p]
         g("hip_xcorr_batch").restype = C.c_int
         g("hip_xcorr_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, ct, C.c_void_p]
+        g("hip_resample_new_setup").restype = C.c_void_p; g("hip_resample_new_setup").argtypes = [C.c_int] * 3
+        g("hip_resample_destroy_setup").restype = None; g("hip_resample_destroy_setup").argtypes = [C.c_void_p]
+        g("hip_resample_batch").restype = C.c_int
+        g("hip_resample_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, ct, C.c_void_p]
         g("hip_fft2_new_setup").restype = C.c_void_p; g("hip_fft2_new_setup").argtypes = [C.c_int, C.c_int]
         g("hip_fft2_destroy_setup").restype = None; g("hip_fft2_destroy_setup").argtypes = [C.c_void_p]
         g("hip_fft2_transform_batch").restype = C.c_int
@@ -183,6 +187,7 @@ def lib():
     L.pffft_hip_analytic_table.restype = C.c_int
     L.pffft_hip_analytic_table.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
     L.pffft_hip_xcorr_route.restype = C.c_char_p; L.pffft_hip_xcorr_route.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.pffft_hip_resample_route.restype = C.c_char_p; L.pffft_hip_resample_route.argtypes = [C.c_void_p]
     L.pffft_hip_fft2_route.restype = C.c_char_p; L.pffft_hip_fft2_route.argtypes = [C.c_void_p]
     L.pffft_hip_fft2_convolve_route.restype = C.c_char_p; L.pffft_hip_fft2_convolve_route.argtypes = [C.c_void_p, C.c_int]
     L.pffft_hip_rfft2_route.restype = C.c_char_p; L.pffft_hip_rfft2_route.argtypes = [C.c_void_p]
@@ -931,6 +936,32 @@ class XcorrSetup(_Handle):
         out = self._dense_out(out, x, batch, self.nlags * self.spp)
         _check(self._fn("hip_xcorr_batch")(self.handle, x.data_ptr(), y.data_ptr(), out.data_ptr(), batch, w, float(scaling), self._stream()),
                "hip_xcorr_batch")
+        return out
+
+
+class ResampleSetup(_Handle):
+    """PFFFT_HIP_ResampleSetup / PFFFTD_HIP_ResampleSetup: Fourier resampling of rows, N samples in and M samples out over the same span
+    (include/pffft_hip.h); scaling = 1 is scipy.signal.resample(x, M).  real = True: rows of scalars in and out; else interleaved complex
+    rows.  Raises ValueError where pffft_hip_resample_new_setup returns NULL (a length no complex setup of the precision takes)."""
+
+    _new, _destroy = "hip_resample_new_setup", "hip_resample_destroy_setup"
+
+    def __init__(self, N: int, M: int, real: bool = False, dtype=np.float32):
+        self.N, self.M, self.dtype, self.real = int(N), int(M), np.dtype(dtype), bool(real)
+        self.spp = 1 if self.real else 2
+        self._open(_pfx(dtype), self.N, self.M, int(self.real), shown=f"pffft_hip_resample_new_setup({N}, {M}, {int(self.real)})")
+
+    def route(self) -> str:
+        """pffft_hip_resample_route: "fused" / "composed" under the calling thread's selector.  Host arithmetic only."""
+        return self._L.pffft_hip_resample_route(self.handle).decode()
+
+    def resample_batch(self, x, out=None, scaling=1.0):
+        """x: contiguous CUDA tensor of the setup's dtype holding `batch` rows of N elements (scalars, or interleaved complex pairs).  The
+        result has `batch` rows of M elements and must not overlap x (there is no in-place form)."""
+        batch = self._whole_rows(x, self.N * self.spp)
+        out = self._dense_out(out, x, batch, self.M * self.spp)
+        _check(self._fn("hip_resample_batch")(self.handle, x.data_ptr(), out.data_ptr(), batch, float(scaling), self._stream()),
+               "hip_resample_batch")
         return out
 
 

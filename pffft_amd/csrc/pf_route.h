@@ -97,6 +97,8 @@ enum AbValue : int {
     AB_FFT2CONV_FUSED = 153,    // ... the fused LDS-resident 2-D convolution kernel wherever it is legal (float, one broadcast H), whatever the measured default of the shape is
     AB_RFFT2CONV_COMPOSED = 154, // pffft_hip_rfft2_convolve_batch: never the fused kernel (the handle's forward transform + product kernel + its backward transform)
     AB_RFFT2CONV_FUSED = 155,   // ... the fused LDS-resident 2-D real convolution kernel wherever it is legal (float, one broadcast H), whatever the measured default of the shape is
+    AB_RESAMPLE_COMPOSED = 156, // pffft_hip_resample_batch: never the fused kernel (widening kernel + transform_batch at N + map kernel + transform_batch at M + narrowing kernel)
+    AB_RESAMPLE_FUSED = 157,    // ... the fused two-length resampling kernel wherever it is legal (float, N != M from 512 ... 4096), whatever the measured default of the cell is
     AB_FAKE_DEVICE = 130,   // the calling thread counts as being on ANOTHER device than its current one (key + 64): exercises the per-device
                                 // replicas of a shared setup on a box with one GPU (tests/test_gpu_round6.py)
 };
