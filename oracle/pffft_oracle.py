@@ -292,18 +292,43 @@ def zconvolve(a, b, ab, scaling, transform_: int, accumulate: bool, dtype=np.flo
 CPLX_INP_OUT, CPLX_FILTER, DIRECT_INP, DIRECT_OUT, CPLX_SINGLE_FFT, SYMMETRIC, CORRELATION = 1, 2, 4, 8, 16, 32, 64
 
 
-def fastconv_setup(taps, block_len: int, flags: int):
-    """pffastconv_new_setup (src/pffastconv.c:58-116).  Returns dict or None (NULL)."""
-    taps = np.asarray(taps, dtype=np.float32)
-    filter_len = taps.size
+def fastconv_geometry(filter_len: int, block_len: int, flags: int):
+    """The lengths pffastconv_new_setup derives (src/pffastconv.c:61-94): (Nfft, *blockLen, effective filter length, cplxFactor), or None
+    where it returns NULL.  No tables: tests/fir_routes.py takes the block schedule from here and from fastconv_blocks."""
     cf = 2 if (flags & CPLX_INP_OUT) and (flags & CPLX_SINGLE_FFT) else 1
     nfft = max(2 * next_power_of_two(filter_len - 1), 2 * SIMD_SZ * SIMD_SZ)
     if flags & CPLX_FILTER:
         return None
     if block_len > nfft:
         nfft = next_power_of_two(block_len)
-    out_block = nfft
-    nfft *= cf
+    return nfft * cf, nfft, (2 * filter_len - 1) if cf == 2 else filter_len, cf
+
+
+def fastconv_blocks(nfft: int, flen: int, cf: int, input_len: int, flush: bool):
+    """The block loop of pffastconv_apply (src/pffastconv.c:156-166, :204-210) without its arithmetic: [(offset, samples taken, samples
+    produced)] per block, `input_len` being the call's length times cplxFactor (:141)."""
+    max_off = (input_len - flen + 1) if flush else (input_len - nfft + 1)
+    blocks, off = [], 0
+    while off < max_off:
+        proc = min(nfft, input_len - off)
+        num_out = proc - flen + 1
+        if cf == 2:
+            num_out &= ~1
+            if not num_out:
+                break
+        blocks.append((off, proc, num_out))
+        off += num_out
+    return blocks
+
+
+def fastconv_setup(taps, block_len: int, flags: int):
+    """pffastconv_new_setup (src/pffastconv.c:58-116).  Returns dict or None (NULL)."""
+    taps = np.asarray(taps, dtype=np.float32)
+    filter_len = taps.size
+    geometry = fastconv_geometry(filter_len, block_len, flags)
+    if geometry is None:
+        return None
+    nfft, out_block, _, cf = geometry
     xt = np.zeros(nfft, dtype=np.float32)
     for i in range(filter_len):
         xt[(nfft - cf * i) & (nfft - 1)] = taps[i] if (flags & CORRELATION) else taps[filter_len - 1 - i]
@@ -319,16 +344,10 @@ def fastconv_apply(s, x, flush: bool):
     cplx = bool(flags & CPLX_INP_OUT)
     input_len = x.size if (cf == 2 or not cplx) else x.size // 2
     y = np.zeros(x.size, dtype=np.float32)
-    max_off = (input_len - flen + 1) if flush else (input_len - nfft + 1)
     parts = 2 if (cplx and cf == 1) else 1
-    off = 0
-    while off < max_off:
-        proc = min(nfft, input_len - off)
-        num_out = proc - flen + 1
-        if cf == 2:
-            num_out &= ~1
-            if not num_out:
-                break
+    end = 0
+    for off, proc, num_out in fastconv_blocks(nfft, flen, cf, input_len, flush):
+        end = off + num_out
         for part in range(parts):
             xt = np.zeros(nfft, dtype=np.float32)
             xt[:proc] = x[2 * off + part: 2 * (off + proc): 2] if parts == 2 else x[off: off + proc]
@@ -339,8 +358,7 @@ def fastconv_apply(s, x, flush: bool):
                 y[2 * off + part: 2 * (off + num_out): 2] = yt[:num_out]
             else:
                 y[off: off + num_out] = yt[:num_out]
-        off += num_out
-    produced = off // cf
+    produced = end // cf
     return y[: (2 * produced if cplx else produced)], produced
 
 

@@ -300,9 +300,9 @@ def test_fir_block_kernels_at_the_bar(ref, taps, L, nsig, flags, variant, kernel
     msg = f"FIR taps {taps} L {L} x{nsig} flags {flags} variant {variant} flush {flush}: GPU e_rms {r / math.sqrt(am.FIR_L):.2f} e_max {m / math.sqrt(am.FIR_L):.2f}"
     if nsig == 1 and L <= (1 << 22) + 12345:
         yr, nr, _ = ref.fastconv(xh[0], h, 0, flags, flush)
-        if nr == n:
-            rr, mr = _fir_figures(yr[None], want)
-            msg += f", reference e_rms {rr / math.sqrt(am.FIR_L):.2f} e_max {mr / math.sqrt(am.FIR_L):.2f}"
+        assert nr == n, (msg, "the reference produces", nr, "samples, this library", n)
+        rr, mr = _fir_figures(yr[None], want)
+        msg += f", reference e_rms {rr / math.sqrt(am.FIR_L):.2f} e_max {mr / math.sqrt(am.FIR_L):.2f}"
     print(msg + " x eps*sqrt(14); kernels " + ", ".join(sorted(set(ran))))
     assert _ran(ran, kernel), (kernel, ran)          # the block kernel this case stands for ran
     rb, mb = (FIR32_RMS_BAR, FIR32_MAX_BAR) if _ran(ran, FIR32) else (FIR_RMS_BAR, FIR_MAX_BAR)
