@@ -989,6 +989,52 @@ int pffftd_hip_rfft2_convolve_batch(PFFFTD_HIP_Rfft2Setup *, const double *in, c
 /* Host arithmetic only, handles of both precisions: "fused" / "composed" under the calling thread's selector; "" for an invalid handle. */
 const char *pffft_hip_rfft2_convolve_route(const void *setup, int h_broadcast);
 
+/* ---- batched 2-D cosine / sine transforms of types II and III (scipy.fft.dctn / idctn, dstn / idstn of a batch of real tiles)
+ * pffft[d]_hip_dct2d_new_setup(rows, cols, kind, norm): both lengths must be ones pffft_new_setup(N, PFFFT_REAL) of that precision takes
+ * (a multiple of 32, 2^a 3^b 5^c: at least 32); NULL, with the text in pffft_hip_last_error(), for any other length and for a kind or a
+ * norm out of range.  Creating a setup touches no device.  The handle owns two pffft[d]_hip_dct_* handles, one of length cols and one of
+ * length rows (one where they are equal): the tables t_k and the product are the 1-D entry's.
+ * in and out are `batch` dense row-major images of rows x cols reals.  out is the 1-D transform of the DCT definitions above (kind, norm)
+ * applied along the columns index (every row of an image), then along the rows index - kind and norm are the same on both axes:
+ *     scipy.fft.dctn / dstn(x, type = 2 | 3, norm = None | "ortho") over the last two axes.
+ * There is no scaling argument, as in the 1-D entry.  Unnormalised, type III after type II returns 4 rows cols x; with ORTHO it returns x.
+ * in, out are device pointers, non-NULL for batch > 0, ALIGNED TO 16 BYTES.  in == out (in place) IS LEGAL; any partial overlap of the two
+ * ranges of batch * rows * cols scalars is refused.  `in` is never written unless it is out.  batch == 0 returns 0.  The call is
+ * asynchronous on `stream`; 0, else a hipError_t with its text in pffft_hip_last_error() (it opens with "pffft_hip: dct2d: ").  Validation happens
+ * before any device is touched, in this order: a NULL or foreign handle (a 1-D dct handle is one) or the other precision's
+ * (hipErrorInvalidHandle), the empty call, NULL pointers, misalignment, overlap (hipErrorInvalidValue) -> nothing launched.
+ * Routes (pffft_hip_dct2d_route names the one a call takes under the calling thread's selector):
+ *   "fused"     float, rows and cols out of 32 / 64 (four shapes, all four kinds): ONE kernel, no scratch.  A workgroup holds whole images
+ *               in LDS: 16-byte loads of the image's dense run, Makhoul's permutation in the load's index map, the rows 2 l and 2 l + 1 as
+ *               the real and imaginary parts of one complex line, a row pass of rows / 2 lines, an untangling step that multiplies by t_k
+ *               of length cols and leaves two real columns per complex column, a column pass of cols / 2 columns, the same step with
+ *               t_k of length rows, 16-byte stores (type III the mirror).  One HBM read and one HBM write of 4 rows cols bytes per
+ *               image.  Both tables are the 1-D handles' device tables.  Which (shape, kind) cells run it by default is a measured table
+ *               (DESIGN.md §3.33); pffft_hip_set_variant(159) runs it wherever it is legal, 158 never.
+ *   "composed"  every setup: pffft[d]_hip_dct_transform_batch of length cols over batch * rows rows from in into out, a real transposing
+ *               kernel [rows][cols] -> [cols][rows] into a per-stream scratch image, dct_transform_batch of length rows over batch * cols
+ *               rows in place there, the transposing kernel back into out.  The inner calls take whichever 1-D route
+ *               pffft_hip_dct_route names under the calling thread's selector.  The result equals, bit for bit, the same four steps done
+ *               by hand.  The scratch holds at most 256 MiB (longer batches go through it in chunks of whole images on the stream); a
+ *               call that would have to grow it on a capturing stream returns hipErrorStreamCaptureUnsupported before any launch: run
+ *               the call once on the stream before capturing.
+ * The two routes run different networks: they agree at the accuracy bar of a transform of rows * cols points, not bit for bit.
+ * A setup serves ONE device, the one that is current at the first call (hipErrorInvalidDevice from another); any number of streams and
+ * threads of that device may share it.  THE FIRST CALL ON A SETUP BINDS IT: make it BEFORE a stream capture - during one it fails with
+ * hipErrorStreamCaptureUnsupported and launches nothing.
+ * Lengths below 32 (8 x 8 and 16 x 16 codec blocks), types I and IV, a different kind per axis, transforms along one axis only,
+ * strided images, a fused double kernel and fused lengths beyond 64 are not offered. */
+typedef struct PFFFT_HIP_Dct2dSetup PFFFT_HIP_Dct2dSetup;
+typedef struct PFFFTD_HIP_Dct2dSetup PFFFTD_HIP_Dct2dSetup;
+PFFFT_HIP_Dct2dSetup *pffft_hip_dct2d_new_setup(int rows, int cols, pffft_hip_dct_kind_t kind, pffft_hip_dct_norm_t norm);
+PFFFTD_HIP_Dct2dSetup *pffftd_hip_dct2d_new_setup(int rows, int cols, pffft_hip_dct_kind_t kind, pffft_hip_dct_norm_t norm);
+void pffft_hip_dct2d_destroy_setup(PFFFT_HIP_Dct2dSetup *);     /* NULL-safe */
+void pffftd_hip_dct2d_destroy_setup(PFFFTD_HIP_Dct2dSetup *);
+int pffft_hip_dct2d_transform_batch(PFFFT_HIP_Dct2dSetup *, const float *in, float *out, size_t batch, void *stream);
+int pffftd_hip_dct2d_transform_batch(PFFFTD_HIP_Dct2dSetup *, const double *in, double *out, size_t batch, void *stream);
+/* Host arithmetic only, handles of both precisions: "fused" / "composed" under the calling thread's selector; "" for an invalid handle. */
+const char *pffft_hip_dct2d_route(const void *setup);
+
 /* Overlap-save FIR on device-resident signal/output (same block schedule as pffastconv_apply,
  * src/pffastconv.c:204-261): returns the number of output samples written, or -1 on error. */
 int pffastconv_hip_apply_device(PFFASTCONV_Setup *, const float *d_input, int inputLen, float *d_output,

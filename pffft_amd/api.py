@@ -142,6 +142,10 @@ def lib():
         g("hip_rfft2_transform_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, ct, C.c_void_p]
         g("hip_rfft2_convolve_batch").restype = C.c_int
         g("hip_rfft2_convolve_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, ct, C.c_size_t, C.c_int, C.c_int, C.c_void_p]
+        g("hip_dct2d_new_setup").restype = C.c_void_p; g("hip_dct2d_new_setup").argtypes = [C.c_int] * 4
+        g("hip_dct2d_destroy_setup").restype = None; g("hip_dct2d_destroy_setup").argtypes = [C.c_void_p]
+        g("hip_dct2d_transform_batch").restype = C.c_int
+        g("hip_dct2d_transform_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         getattr(L, f"validate_{pfx}_simd").restype = C.c_int
         getattr(L, f"validate_{pfx}_simd_ex").restype = C.c_int
         getattr(L, f"validate_{pfx}_simd_ex").argtypes = [C.c_void_p]
@@ -192,6 +196,7 @@ def lib():
     L.pffft_hip_fft2_convolve_route.restype = C.c_char_p; L.pffft_hip_fft2_convolve_route.argtypes = [C.c_void_p, C.c_int]
     L.pffft_hip_rfft2_route.restype = C.c_char_p; L.pffft_hip_rfft2_route.argtypes = [C.c_void_p]
     L.pffft_hip_rfft2_convolve_route.restype = C.c_char_p; L.pffft_hip_rfft2_convolve_route.argtypes = [C.c_void_p, C.c_int]
+    L.pffft_hip_dct2d_route.restype = C.c_char_p; L.pffft_hip_dct2d_route.argtypes = [C.c_void_p]
     L.pffft_hip_kernel_name.restype = C.c_char_p; L.pffft_hip_kernel_name.argtypes = [C.c_void_p]
     L.pffft_hip_describe.restype = C.c_int; L.pffft_hip_describe.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.pffft_hip_route_occupancy.restype = C.c_int; L.pffft_hip_route_occupancy.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -1070,6 +1075,38 @@ class Rfft2Setup(_Handle):
         assert self._whole_rows(out, self.image_scalars) == batch, "x and out hold different numbers of images"
         _check(self._fn("hip_rfft2_convolve_batch")(self.handle, x.data_ptr(), H.data_ptr(), out.data_ptr(), float(scaling), batch,
                                                     int(bool(conj_h)), int(images == 1), self._stream()), "hip_rfft2_convolve_batch")
+        return out
+
+
+class Dct2dSetup(_Handle):
+    """PFFFT_HIP_Dct2dSetup / PFFFTD_HIP_Dct2dSetup: batched 2-D cosine / sine transforms of type II / III of dense row-major images of
+    rows x cols reals (include/pffft_hip.h; scipy.fft.dctn / dstn with type = 2 / 3 over the last two axes).  kind: "dct2" / "dct3" /
+    "dst2" / "dst3" (or the enum value), norm: None / "ortho", the same on both axes.  Raises ValueError where pffft_hip_dct2d_new_setup
+    returns NULL (a length no real setup of the precision takes, a kind or a norm out of range)."""
+
+    _new, _destroy = "hip_dct2d_new_setup", "hip_dct2d_destroy_setup"
+
+    def __init__(self, rows: int, cols: int, kind, norm=None, dtype=np.float32):
+        self.rows, self.cols, self.dtype = int(rows), int(cols), np.dtype(dtype)
+        self.kind = DCT_KINDS[kind] if kind in DCT_KINDS else int(kind)
+        self.norm = DCT_NORMS[norm] if norm in DCT_NORMS else int(norm)
+        self.image_scalars = self.rows * self.cols
+        self._open(_pfx(dtype), self.rows, self.cols, self.kind, self.norm, shown=f"pffft_hip_dct2d_new_setup({rows}, {cols}, {kind}, {norm})")
+
+    def route(self) -> str:
+        """pffft_hip_dct2d_route: "fused" / "composed" under the calling thread's selector.  Host arithmetic only."""
+        return self._L.pffft_hip_dct2d_route(self.handle).decode()
+
+    def transform_batch(self, x, out=None):
+        """x: contiguous CUDA tensor of the setup's dtype holding whole images (of any shape, such as [batch, rows, cols]).  out: None (a
+        new tensor shaped like x), another such tensor, or x itself (in place)."""
+        import torch
+        batch = self._whole_rows(x, self.image_scalars)
+        if out is None:
+            out = torch.empty_like(x)
+        assert self._whole_rows(out, self.image_scalars) == batch, "x and out hold different numbers of images"
+        _check(self._fn("hip_dct2d_transform_batch")(self.handle, x.data_ptr(), out.data_ptr(), batch, self._stream()),
+               "hip_dct2d_transform_batch")
         return out
 
 

@@ -5,6 +5,7 @@
 #include <memory>
 
 #include "pf_compose.h"
+#include "dct_host.h"
 #include "fft_dct.h"
 
 namespace pf {
@@ -150,6 +151,15 @@ static int dct_transform_batch(void* setup, const T* in, T* out, size_t batch, h
         if (dct_fused_now(z, ab()) && dct_fusable(z, &e)) return dct_fused(s, e, dct_route(z->inner, z->kind).oneshot, in, out, batch, tab, st);
     }
     return dct_composed<T>(z, s, in, out, batch, tab, st);
+}
+
+// (dct_host.h) for the fused 2-D kernel of dct2d_tu.hip
+int dct_device_table(void* setup, hipStream_t st, const cx<float>** tab) {
+    DctSetup* z = typed_handle<DctSetup, float>(setup);
+    if (!z) return (int)hipErrorInvalidHandle;
+    Setup* s = for_device(z->inner);
+    if (int rc = ensure_device_any(s)) return rc;
+    return dct_table<float>(z, s, st, tab);
 }
 
 }  // namespace pf

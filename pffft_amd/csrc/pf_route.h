@@ -99,6 +99,8 @@ enum AbValue : int {
     AB_RFFT2CONV_FUSED = 155,   // ... the fused LDS-resident 2-D real convolution kernel wherever it is legal (float, one broadcast H), whatever the measured default of the shape is
     AB_RESAMPLE_COMPOSED = 156, // pffft_hip_resample_batch: never the fused kernel (widening kernel + transform_batch at N + map kernel + transform_batch at M + narrowing kernel)
     AB_RESAMPLE_FUSED = 157,    // ... the fused two-length resampling kernel wherever it is legal (float, N != M from 512 ... 4096), whatever the measured default of the cell is
+    AB_DCT2D_COMPOSED = 158,    // pffft_hip_dct2d_transform_batch: never the fused kernel (dct_transform_batch + real transposing kernel + dct_transform_batch + its twin)
+    AB_DCT2D_FUSED = 159,       // ... the fused LDS-resident 2-D cosine kernel wherever it is legal (float, rows and cols 32 / 64), whatever the measured default of the (shape, kind) is
     AB_FAKE_DEVICE = 130,   // the calling thread counts as being on ANOTHER device than its current one (key + 64): exercises the per-device
                                 // replicas of a shared setup on a box with one GPU (tests/test_gpu_round6.py)
 };
