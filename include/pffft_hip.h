@@ -1035,6 +1035,66 @@ int pffftd_hip_dct2d_transform_batch(PFFFTD_HIP_Dct2dSetup *, const double *in, 
 /* Host arithmetic only, handles of both precisions: "fused" / "composed" under the calling thread's selector; "" for an invalid handle. */
 const char *pffft_hip_dct2d_route(const void *setup);
 
+/* ---- batched band energies of framed transforms: mel / Bark / ERB / octave bands, channel powers, rebinned spectrograms
+ *
+ * Row v of `out` is the |X|^2 row of frame v reduced along frequency by a sparse bank of weighted bands, without the nframes x P
+ * intermediate and without a dense matrix product.
+ *
+ * pffft[d]_hip_bands_new_setup(N, transform, nbands, first, count, weights).  The handle owns one inner setup of length N (real or complex)
+ * and a host copy of the bank; the arrays are HOST arrays and are copied.  P = N/2 + 1 bins for a real setup, N for a complex one
+ * (pffft_hip_bands_bins; pffft_hip_bands_count returns nbands).  `weights` holds sum(count[b]) values, band after band: entry j of band b
+ * multiplies bin first[b] + j.  Bands may overlap, repeat and come in any order; count[b] == 0 and negative weights are legal.  NULL, with
+ * a text in pffft_hip_last_error() (it opens with "pffft_hip: bands: ") and no device touched, for: an N that is no length of that
+ * transform, nbands == 0, a NULL array, first[b] + count[b] > P, a weight that is not finite.  A handle serves ONE device: the first call
+ * binds it to the current device and uploads the bank (not during a stream capture: run the call once before capturing).
+ *
+ * pffft[d]_hip_bands_batch.  Framing, `window` (NULL = no product), `hop`, `signal_stride`, the frame numbering v = i*nframes + f, the
+ * sample / scalar rules and the pointer rules are exactly those of pffft_hip_frames_transform_batch.  Row v holds nbands scalars at
+ * out + v*out_stride (0 = dense); out needs scalar alignment only and must not overlap signal.
+ * ARITHMETIC - THE ORDER IS PART OF THE CONTRACT.  p[k] is the value pffft_hip_frames_transform_batch(..., PFFFT_HIP_FRAMES_POWER) produces
+ * for that frame, bit for bit (DC and Nyquist as that output forms them).  Band b's entries are cut into segments of PFFFT_HIP_BANDS_SEG
+ * consecutive entries, counted from the band's first entry (the last segment may be shorter).  A segment's partial is the sum of
+ * fl(w_j * p[first + j]), j ascending, started from its first term; the band's value e_b is the sum of its segment partials, segment
+ * ascending, started from the first.  Every product and every addition is rounded once: no FMA, no atomics.  An empty band gives +0.
+ *     PFFFT_HIP_BANDS_ENERGY  stores fl(scaling * e_b); `floor` is not read
+ *     PFFFT_HIP_BANDS_LOG     stores log(max(fl(scaling * e_b), floor)), the natural logarithm of the device's math library (a NaN passes
+ *                             through the maximum); floor must be finite and > 0
+ * Up to 16 entries the order is the plain left-to-right sum.  The result is deterministic and equal on every route, LOG included.
+ * ROUTES (pffft_hip_bands_route names the one a call takes under the calling thread's selector, pffft_hip_set_variant: 160 = always
+ * composed, 161 = fused wherever it is legal; it assumes 16-byte aligned pointers; signal_stride = 0: one signal; "" for an invalid handle
+ * or hop == 0; host arithmetic only).  Real float setups of N = 1024 / 2048 / 4096 run FUSED when hop and signal_stride are multiples of 4
+ * and signal and window are 16-byte aligned: the framed kernel leaves the |X|^2 values of a frame in LDS, forms the band sums there and
+ * stores nbands scalars per frame - hop + nbands scalars of HBM traffic per frame.  Descriptors and weights are read through L2, so the
+ * fused route puts no cap on nbands or on sum(count); it keeps one partial per segment of the bank in LDS, so the bank may hold at most
+ * 658 / 1298 / 2578 segments, sum over b of ceil(count[b] / 16), at N = 1024 / 2048 / 4096 (an 80-band mel bank has 104 / 162 / 286).
+ * Banks beyond that run composed, and pffft_hip_bands_route says so.
+ * Everything else - double, complex, other sizes, hops and alignments - is COMPOSED: the |X|^2 rows of
+ * whole chunks of frames go into a scratch of the handle (one buffer per stream, at most 256 MiB), produced by the inner setup's own
+ * pffft_hip_frames_transform_batch, and a row kernel reduces them.  A chunk is whole signals; where one signal's rows exceed the cap, runs
+ * of frames of one signal.  The scratch grows outside HIP graph capture only: a call that would have to grow it while `stream` is
+ * capturing fails with hipErrorStreamCaptureUnsupported and launches nothing.
+ * Validation happens before any device is touched: a NULL or foreign handle or the other precision's handle, an unknown `what`, a floor
+ * that is not finite or not > 0 for LOG, what pffft_hip_frames_transform_batch refuses (hop == 0, a signal_stride smaller than one
+ * signal's scalars when nsignals > 1, a NULL signal / out), an out_stride smaller than nbands -> non-zero, nothing launched.
+ * nsignals == 0 or nframes == 0 -> 0, nothing launched. */
+enum { PFFFT_HIP_BANDS_ENERGY = 0, PFFFT_HIP_BANDS_LOG = 1 };
+#define PFFFT_HIP_BANDS_SEG 16
+typedef struct PFFFT_HIP_Bands_Setup PFFFT_HIP_Bands_Setup;
+typedef struct PFFFTD_HIP_Bands_Setup PFFFTD_HIP_Bands_Setup;
+PFFFT_HIP_Bands_Setup *pffft_hip_bands_new_setup(int N, pffft_transform_t transform, unsigned nbands, const unsigned *first,
+                                                 const unsigned *count, const float *weights);
+PFFFTD_HIP_Bands_Setup *pffftd_hip_bands_new_setup(int N, pffft_transform_t transform, unsigned nbands, const unsigned *first,
+                                                   const unsigned *count, const double *weights);
+void pffft_hip_bands_destroy_setup(PFFFT_HIP_Bands_Setup *);     /* NULL-safe */
+void pffftd_hip_bands_destroy_setup(PFFFTD_HIP_Bands_Setup *);
+int pffft_hip_bands_batch(PFFFT_HIP_Bands_Setup *, const float *signal, size_t signal_stride, size_t nsignals, size_t nframes, size_t hop,
+                          const float *window, float scaling, float floor, int what, float *out, size_t out_stride, void *stream);
+int pffftd_hip_bands_batch(PFFFTD_HIP_Bands_Setup *, const double *signal, size_t signal_stride, size_t nsignals, size_t nframes, size_t hop,
+                           const double *window, double scaling, double floor, int what, double *out, size_t out_stride, void *stream);
+const char *pffft_hip_bands_route(const void *setup, size_t hop, size_t signal_stride);
+unsigned pffft_hip_bands_count(const void *setup);   /* nbands; 0 for an invalid handle */
+unsigned pffft_hip_bands_bins(const void *setup);    /* P; 0 for an invalid handle */
+
 /* Overlap-save FIR on device-resident signal/output (same block schedule as pffastconv_apply,
  * src/pffastconv.c:204-261): returns the number of output samples written, or -1 on error. */
 int pffastconv_hip_apply_device(PFFASTCONV_Setup *, const float *d_input, int inputLen, float *d_output,

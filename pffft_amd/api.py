@@ -146,6 +146,12 @@ def lib():
         g("hip_dct2d_destroy_setup").restype = None; g("hip_dct2d_destroy_setup").argtypes = [C.c_void_p]
         g("hip_dct2d_transform_batch").restype = C.c_int
         g("hip_dct2d_transform_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        g("hip_bands_new_setup").restype = C.c_void_p
+        g("hip_bands_new_setup").argtypes = [C.c_int, C.c_int, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]
+        g("hip_bands_destroy_setup").restype = None; g("hip_bands_destroy_setup").argtypes = [C.c_void_p]
+        g("hip_bands_batch").restype = C.c_int
+        g("hip_bands_batch").argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, ct, ct, C.c_int,
+                                         C.c_void_p, C.c_size_t, C.c_void_p]
         getattr(L, f"validate_{pfx}_simd").restype = C.c_int
         getattr(L, f"validate_{pfx}_simd_ex").restype = C.c_int
         getattr(L, f"validate_{pfx}_simd_ex").argtypes = [C.c_void_p]
@@ -197,6 +203,9 @@ def lib():
     L.pffft_hip_rfft2_route.restype = C.c_char_p; L.pffft_hip_rfft2_route.argtypes = [C.c_void_p]
     L.pffft_hip_rfft2_convolve_route.restype = C.c_char_p; L.pffft_hip_rfft2_convolve_route.argtypes = [C.c_void_p, C.c_int]
     L.pffft_hip_dct2d_route.restype = C.c_char_p; L.pffft_hip_dct2d_route.argtypes = [C.c_void_p]
+    L.pffft_hip_bands_route.restype = C.c_char_p; L.pffft_hip_bands_route.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t]
+    L.pffft_hip_bands_count.restype = C.c_uint; L.pffft_hip_bands_count.argtypes = [C.c_void_p]
+    L.pffft_hip_bands_bins.restype = C.c_uint; L.pffft_hip_bands_bins.argtypes = [C.c_void_p]
     L.pffft_hip_kernel_name.restype = C.c_char_p; L.pffft_hip_kernel_name.argtypes = [C.c_void_p]
     L.pffft_hip_describe.restype = C.c_int; L.pffft_hip_describe.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.pffft_hip_route_occupancy.restype = C.c_int; L.pffft_hip_route_occupancy.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -1107,6 +1116,103 @@ class Dct2dSetup(_Handle):
         assert self._whole_rows(out, self.image_scalars) == batch, "x and out hold different numbers of images"
         _check(self._fn("hip_dct2d_transform_batch")(self.handle, x.data_ptr(), out.data_ptr(), batch, self._stream()),
                "hip_dct2d_transform_batch")
+        return out
+
+
+BANDS_WHAT = {"energy": 0, "log": 1}   # PFFFT_HIP_BANDS_* of include/pffft_hip.h
+BANDS_SEG = 16                          # PFFFT_HIP_BANDS_SEG
+
+
+def _hz_to_mel(f, scale):
+    f = np.asarray(f, dtype=np.float64)
+    if scale == "htk":
+        return 2595.0 * np.log10(1.0 + f / 700.0)
+    # Slaney's Auditory Toolbox: linear below 1 kHz (200/3 Hz per mel), logarithmic above (27 steps per factor 6.4)
+    lin = f / (200.0 / 3.0)
+    return np.where(f >= 1000.0, 15.0 + np.log(np.maximum(f, 1000.0) / 1000.0) / (np.log(6.4) / 27.0), lin)
+
+
+def _mel_to_hz(m, scale):
+    m = np.asarray(m, dtype=np.float64)
+    if scale == "htk":
+        return 700.0 * (10.0 ** (m / 2595.0) - 1.0)
+    return np.where(m >= 15.0, 1000.0 * np.exp((np.log(6.4) / 27.0) * (np.maximum(m, 15.0) - 15.0)), (200.0 / 3.0) * m)
+
+
+def mel_bank(N, nbands, fs, fmin=0.0, fmax=None, scale="htk", norm=None, dtype=np.float32):
+    """A triangular mel filter bank over the N/2 + 1 bins of a real transform of N samples at the rate `fs`, for BandsSetup: returns
+    (first, count, weights).  nbands + 2 edges are equally spaced on the mel scale ("htk": 2595 log10(1 + f / 700); "slaney": linear below
+    1 kHz, logarithmic above) between fmin and fmax (None: fs / 2); band b rises from edge b to 1 at edge b + 1 and falls to 0 at edge
+    b + 2, evaluated at the bin frequencies k fs / N.  norm = "slaney" divides band b by half its width in Hz (equal area).  The triangles
+    are computed in float64 and rounded to `dtype`; first[b], count[b] span the non-zero support of band b (count 0 where no bin falls
+    inside).  Host arithmetic only."""
+    assert scale in ("htk", "slaney") and norm in (None, "slaney") and nbands >= 1 and N >= 2
+    fmax = fs / 2.0 if fmax is None else float(fmax)
+    assert 0.0 <= fmin < fmax <= fs / 2.0
+    edges = _mel_to_hz(np.linspace(_hz_to_mel(fmin, scale), _hz_to_mel(fmax, scale), nbands + 2), scale)
+    edges[0], edges[-1] = fmin, fmax                      # (exactly: a bin at fmin or fmax lies on the edge, outside the support)
+    f = np.arange(N // 2 + 1, dtype=np.float64) * float(fs) / N
+    first, count, weights = np.zeros(nbands, np.uint32), np.zeros(nbands, np.uint32), []
+    for b in range(nbands):
+        lo, c, hi = edges[b], edges[b + 1], edges[b + 2]
+        tri = np.maximum(0.0, np.minimum((f - lo) / (c - lo), (hi - f) / (hi - c)))
+        if norm == "slaney":
+            tri = tri * (2.0 / (hi - lo))
+        nz = np.nonzero(tri)[0]
+        if nz.size:
+            first[b], count[b] = nz[0], nz[-1] - nz[0] + 1
+            weights.append(tri[nz[0]:nz[-1] + 1])
+    w = np.concatenate(weights) if weights else np.zeros(0)
+    return first, count, w.astype(dtype)
+
+
+def bands_route(setup: "BandsSetup", hop, signal_stride=0) -> str:
+    """pffft_hip_bands_route: "fused" / "composed" for a band-energy call with 16-byte aligned pointers, under the calling thread's
+    selector.  Host arithmetic only."""
+    return lib().pffft_hip_bands_route(setup.handle, int(hop), int(signal_stride)).decode()
+
+
+class BandsSetup(_Handle):
+    """PFFFT_HIP_Bands_Setup / PFFFTD_HIP_Bands_Setup: band energies (mel / Bark / octave bands, rebinned spectrograms) of the |X|^2 rows
+    of framed transforms (include/pffft_hip.h).  first, count: nbands unsigned values; weights: sum(count) values, band after band (entry j
+    of band b multiplies bin first[b] + j).  Raises ValueError where pffft_hip_bands_new_setup returns NULL (the text is in last_error())."""
+
+    _new, _destroy = "hip_bands_new_setup", "hip_bands_destroy_setup"
+
+    def __init__(self, N: int, first, count, weights, transform=REAL, dtype=np.float32):
+        self.N, self.transform_type, self.dtype = int(N), int(transform), np.dtype(dtype)
+        first = np.ascontiguousarray(first, dtype=np.uint32).ravel()
+        count = np.ascontiguousarray(count, dtype=np.uint32).ravel()
+        weights = np.ascontiguousarray(weights, dtype=self.dtype).ravel()
+        assert first.size == count.size and weights.size == int(count.astype(np.uint64).sum()), "weights holds sum(count) values"
+        self._open(_pfx(dtype), self.N, self.transform_type, first.size, first.ctypes.data, count.ctypes.data, weights.ctypes.data,
+                   shown=f"pffft_hip_bands_new_setup({N}, {transform}, {first.size} bands)")
+
+    @property
+    def nbands(self) -> int:
+        return int(self._L.pffft_hip_bands_count(self.handle))
+
+    @property
+    def bins(self) -> int:
+        return int(self._L.pffft_hip_bands_bins(self.handle))
+
+    # the framing arguments are those of Setup.frames_transform_batch
+    _frames_rows, _spp, _analysis_in, _window_ptr = Setup._frames_rows, Setup._spp, Setup._analysis_in, Setup._window_ptr
+    _rows_out = staticmethod(Setup._rows_out)
+
+    def bands_batch(self, signal, hop, nframes=None, window=None, scaling=1.0, what="energy", floor=None, out=None):
+        """pffft_hip_bands_batch: the band sums of the |X|^2 row of every frame of frames_transform_batch, in the documented order, times
+        `scaling`; what = "log": log(max(., floor)), floor > 0 required.  Returns [nsignals,] nframes, nbands]; `out` may have padded rows
+        (its stride(-2) is the row pitch)."""
+        nsig, sstride, nframes = self._analysis_in(signal, hop, nframes, self.N)
+        out, pitch = self._rows_out(out, signal, nsig, nframes, self.nbands, "row v = i nframes + f")
+        w = BANDS_WHAT[what] if what in BANDS_WHAT else int(what)
+        if floor is None:
+            if w == BANDS_WHAT["log"]:
+                raise ValueError("what = 'log' needs a floor > 0")
+            floor = 0.0
+        _check(self._fn("hip_bands_batch")(self.handle, signal.data_ptr(), sstride, nsig, nframes, hop, self._window_ptr(window, signal),
+                                           float(scaling), float(floor), w, out.data_ptr(), pitch, self._stream()), "hip_bands_batch")
         return out
 
 

@@ -101,6 +101,8 @@ enum AbValue : int {
     AB_RESAMPLE_FUSED = 157,    // ... the fused two-length resampling kernel wherever it is legal (float, N != M from 512 ... 4096), whatever the measured default of the cell is
     AB_DCT2D_COMPOSED = 158,    // pffft_hip_dct2d_transform_batch: never the fused kernel (dct_transform_batch + real transposing kernel + dct_transform_batch + its twin)
     AB_DCT2D_FUSED = 159,       // ... the fused LDS-resident 2-D cosine kernel wherever it is legal (float, rows and cols 32 / 64), whatever the measured default of the (shape, kind) is
+    AB_BANDS_COMPOSED = 160,    // pffft_hip_bands_batch: never the fused kernel (the inner setup's POWER rows into the handle's scratch + row kernel)
+    AB_BANDS_FUSED = 161,       // ... the fused framed band kernel wherever it is legal (real float N = 1024 / 2048 / 4096), whatever the measured default of the size is
     AB_FAKE_DEVICE = 130,   // the calling thread counts as being on ANOTHER device than its current one (key + 64): exercises the per-device
                                 // replicas of a shared setup on a box with one GPU (tests/test_gpu_round6.py)
 };
