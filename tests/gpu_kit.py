@@ -1,7 +1,12 @@
 """What the GPU test files (tests/test_gpu_*.py) share: the device fixture, the kineto tracers, bit comparison, sentinel-guarded outputs,
-the seeded CUDA generators, the selector scope, and the signal / window / prototype makers of the frame family.  Imported by name, like
-tests/accuracy_model.py; needs no device at import.  What differs by feature (row budgets, selectors, setups, run_* and the identity
-matrices, the allowances of the memory tests) stays in its file."""
+the seeded CUDA generators, the selector scope, the signal / window / prototype makers of the frame family, the small names (dev, PEAK,
+shape_id, dtype_id), and the scaffolding of the capture and timing tests: a call refused on a capturing stream (refused_in_capture,
+assert_refusal), graph replays against the eager bits (assert_replays), alternating round-bests (alternating) and the two lists of a
+default cell (cell_times).  Imported by name, like tests/accuracy_model.py; needs no device at import.  What differs by feature stays in
+its file: row budgets, selectors, setups, run_* and the identity matrices, the allowances of the memory tests, the needles a refusal
+must name, what is captured and in which order, and of a timing test the bytes moved, the printed line and the assertion on ratio and
+spread.  A test whose rounds do something else (a second stream during the replay, a host model as the wanted result, another timing
+protocol) keeps its own loop."""
 import json
 import math
 import os
@@ -18,6 +23,13 @@ import pffft_amd as pa  # noqa: E402
 
 SENTINEL = -77.0
 TDT = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64}      # torch dtype of a numpy dtype
+PEAK = 8e12                                                                            # bytes / s of HBM: the roofline of the printed shares
+shape_id = lambda s: f"{s[0]}x{s[1]}"  # noqa: E731                                    (ids of parametrized shapes and dtypes)
+dtype_id = lambda d: np.dtype(d).name  # noqa: E731
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -174,3 +186,72 @@ def best_of(fn, rounds=3, calls=20):
         e1.synchronize()
         best = min(best, e0.elapsed_time(e1) * 1e-3 / calls)
     return best
+
+
+def alternating(fns, rounds=5):
+    """Per function the round-bests of `rounds` alternating rounds (best_of: the best of three runs of 20 calls each); within a round the
+    functions run in the order of `fns`."""
+    ts = [[] for _ in fns]
+    for _ in range(rounds):
+        for t, f in zip(ts, fns):
+            t.append(best_of(f))
+    return ts
+
+
+def cell_times(at, sel_a, sel_b):
+    """The two lists of round-bests of at(sel_a) and at(sel_b), alternating, after one synchronized warm call of each; the selector is 0
+    again afterwards.  spread, ratio, the printed line and `ratio > spread` are the site's: bytes moved and text differ by feature."""
+    try:
+        for sel in (sel_a, sel_b):
+            at(sel)()
+            torch.cuda.synchronize()
+        return alternating((at(sel_a), at(sel_b)))
+    finally:
+        pa.set_variant(0)
+
+
+# ------------------------------------------------------------------ graph capture: the refusal, the replays
+def refused_in_capture(stream, fn, untouched=()):
+    """The message of the RuntimeError that fn() raises inside a graph capture on `stream` ("" when it raises none - assert_refusal fails
+    on that).  The selector is 0 again, the graph dropped and the stream synchronized; every tensor of `untouched` must still hold
+    SENTINEL everywhere: a refused call launches nothing."""
+    g, msg = torch.cuda.CUDAGraph(), ""
+    try:
+        with torch.cuda.graph(g, stream=stream):
+            try:
+                fn()
+            except RuntimeError as ex:
+                msg = str(ex)
+    finally:
+        pa.set_variant(0)
+    del g
+    stream.synchronize()
+    for t in untouched:
+        assert bool((t == SENTINEL).all()), "a refused call launched something"
+    return msg
+
+
+def assert_refusal(msg, *needles):
+    """`msg` is a refusal during graph capture that names every needle, e.g. "(900)" or "tables of this setup"."""
+    for needle in ("graph capture",) + needles:
+        assert needle in msg, (needle, msg)
+
+
+def assert_replays(stream, graphs, refresh, eager, outs, rounds, each=None):
+    """`rounds` times: refresh() the input, eager() for the wanted tensors, the outputs zeroed, every graph replayed - a synchronize of
+    `stream` after refresh, after eager and after the replays - then each output has the bits of its wanted tensor.  each(rep, wants),
+    if given, is the site's own look at the eager result, before the replays."""
+    for rep in range(rounds):
+        refresh()
+        stream.synchronize()
+        wants = eager()
+        stream.synchronize()
+        if each is not None:
+            each(rep, wants)
+        for o in outs:
+            o.zero_()
+        for g in graphs:
+            g.replay()
+        stream.synchronize()
+        for o, w in zip(outs, wants):
+            assert same_bits(o, w), rep

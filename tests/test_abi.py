@@ -10,16 +10,10 @@ import subprocess
 import numpy as np
 import pytest
 
+from abi_kit import L  # noqa: F401
 import pffft_amd as pa
 from conftest import ROOT
 from oracle import pffft_oracle as po
-
-
-@pytest.fixture(scope="module")
-def L():
-    from pffft_amd import build
-    build.build()
-    return pa.lib()
 
 
 def declared_symbols():

@@ -5,19 +5,13 @@ import numpy as np
 import pytest
 import scipy.signal
 
+from abi_kit import L  # noqa: F401
 import accuracy_model as am
 import analytic_model as an
 import pffft_amd as pa
 
 DTYPES = [np.float32, np.float64]
 SIZES = (32, 96, 512, 1024, 4096, 8192, 20480)
-
-
-@pytest.fixture(scope="module")
-def L():
-    from pffft_amd import build
-    build.build()
-    return pa.lib()
 
 
 @pytest.mark.parametrize("N", (16, 96, 1024, 20480))

@@ -9,10 +9,10 @@ import re
 import numpy as np
 import pytest
 
+from abi_kit import INVALID_HANDLE, INVALID_VALUE, L, prefix, refused  # noqa: F401
 import analytic_model as an
 import pffft_amd as pa
 
-INVALID_VALUE, INVALID_HANDLE = 1, 400      # hipErrorInvalidValue, hipErrorInvalidHandle
 P = 0x10000                                 # a non-NULL "device pointer", 16-byte aligned: validation answers before anything reads it
 N = 1024
 HANDLE = "pffft_hip: bad analytic setup handle"
@@ -21,19 +21,8 @@ ALIGN = PRE + "in / out not aligned to 8 bytes (real rows) / 16 bytes (complex r
 A, H, E = 0, 1, 2
 
 
-@pytest.fixture(scope="module")
-def L():
-    from pffft_amd import build
-    build.build()
-    return pa.lib()
-
-
 def call(L, pfx, h, src=P, dst=16 * P, batch=1, what=A):
     return getattr(L, f"{pfx}_hip_analytic_transform_batch")(h, src, dst, batch, what, None)
-
-
-def refused(rc, code, text):
-    assert rc == code and pa.last_error() == text, (rc, pa.last_error(), text)
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
@@ -56,7 +45,7 @@ def test_refusals(L, dtype):
     other = pa.AnalyticSetup(N, dtype=np.float64 if dtype == np.float32 else np.float32)
     plain = pa.Setup(N, pa.COMPLEX, dtype)                      # a transform setup is no analytic handle
     junk = C.create_string_buffer(4096)
-    pfx = "pffftd" if dtype == np.float64 else "pffft"
+    pfx = prefix(dtype)
     h = s.handle
     size = np.dtype(dtype).itemsize
 

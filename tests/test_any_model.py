@@ -5,6 +5,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from abi_kit import L, prefix  # noqa: F401
 import accuracy_model as am
 import any_model as ym
 import pffft_amd as pa
@@ -12,13 +13,6 @@ import pffft_amd as pa
 AB_ANY_COMPOSED, AB_ANY_FUSED = 132, 133
 DTYPES = [np.float32, np.float64]
 SIZES = [1, 2, 3, 17, 100, 127, 129, 255, 257, 500, 509, 1000, 1021, 1023, 1025, 2047, 2049, 4093, 10007, 65537, 100003, 1000003]
-
-
-@pytest.fixture(scope="module")
-def L():
-    from pffft_amd import build
-    build.build()
-    return pa.lib()
 
 
 # ------------------------------------------------------------------ the model is a DFT
@@ -52,7 +46,7 @@ def test_model_roundtrip_and_known_vectors():
 
 # ------------------------------------------------------------------ host-only entries
 def _new(L, N, tr, dtype):
-    pfx = "pffftd" if np.dtype(dtype) == np.float64 else "pffft"
+    pfx = prefix(dtype)
     return getattr(L, f"{pfx}_hip_any_new_setup")(N, tr), getattr(L, f"{pfx}_hip_any_destroy_setup")
 
 

@@ -4,6 +4,7 @@ pffft_hip_any_is_real / _any_bins, route and convolution length, validation befo
 import numpy as np
 import pytest
 
+from abi_kit import L, prefix  # noqa: F401
 import accuracy_model as am
 import any_model as ym
 import anyr_model as rm
@@ -13,13 +14,6 @@ AB_ANY_COMPOSED, AB_ANY_FUSED = 132, 133
 DTYPES = [np.float32, np.float64]
 SIZES = [1, 2, 3, 4, 5, 17, 100, 171, 172, 341, 342, 683, 684, 1000, 1021, 1365, 1366, 2731, 2732, 4093, 10007, 65537, 100003]
 LEGAL_REAL = [32, 96, 1024, 20480]
-
-
-@pytest.fixture(scope="module")
-def L():
-    from pffft_amd import build
-    build.build()
-    return pa.lib()
 
 
 # ------------------------------------------------------------------ the model is rfft / irfft
@@ -65,7 +59,7 @@ def test_model_ignores_the_imaginary_parts_that_are_no_input():
 
 # ------------------------------------------------------------------ host-only entries
 def _ctor(L, dtype):
-    pfx = "pffftd" if np.dtype(dtype) == np.float64 else "pffft"
+    pfx = prefix(dtype)
     return getattr(L, f"{pfx}_hip_any_new_real_setup"), getattr(L, f"{pfx}_hip_any_destroy_setup")
 
 

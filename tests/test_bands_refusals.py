@@ -7,22 +7,15 @@ import os
 import numpy as np
 import pytest
 
+from abi_kit import INVALID_HANDLE, INVALID_VALUE, L, prefix, refused  # noqa: F401
 import pffft_amd as pa
 
-INVALID_VALUE, INVALID_HANDLE = 1, 400      # hipErrorInvalidValue, hipErrorInvalidHandle
 SIG = 0x100000                              # non-NULL "device pointers", 16-byte aligned: validation answers before anything reads them
 OUT = 0x4000000
 HANDLE = "pffft_hip: bad bands setup handle"
 PRE = "pffft_hip: bands: "
 AB_BANDS_COMPOSED, AB_BANDS_FUSED = 160, 161
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def L():
-    from pffft_amd import build
-    build.build()
-    return pa.lib()
 
 
 def new(L, pfx, N, transform, nbands, first, count, weights):
@@ -39,10 +32,6 @@ def call(L, pfx, h, signal=SIG, signal_stride=0, nsignals=1, nframes=4, hop=256,
          out_stride=0):
     return getattr(L, f"{pfx}_hip_bands_batch")(h, signal, signal_stride, nsignals, nframes, hop, window, scaling, floor, what, out, out_stride,
                                                None)
-
-
-def refused(rc, code, text):
-    assert rc == code and pa.last_error() == text, (rc, pa.last_error(), text)
 
 
 @pytest.mark.parametrize("pfx", ["pffft", "pffftd"])
@@ -108,7 +97,7 @@ def test_refusals(L, dtype, transform):
     plain = pa.Setup(N, transform, dtype)                       # a transform setup is no bands handle
     dct = pa.DctSetup(64, "dct2", dtype=dtype)                  # nor is another derived handle
     junk = C.create_string_buffer(4096)
-    pfx = "pffftd" if dtype == np.float64 else "pffft"
+    pfx = prefix(dtype)
     h = s.handle
     spp = 2 if transform == pa.COMPLEX else 1
 

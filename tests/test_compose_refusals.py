@@ -8,19 +8,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from abi_kit import INVALID_HANDLE, INVALID_VALUE, L, prefix, refused  # noqa: F401
 import pffft_amd as pa
 
-INVALID_VALUE, INVALID_HANDLE = 1, 400      # hipErrorInvalidValue, hipErrorInvalidHandle
 P = 0x1000                                  # a non-NULL "device pointer", 16-byte aligned: validation answers before anything reads it
 N, NFRAMES, HOP = 1024, 4, 256
 HANDLE = "pffft_hip: bad setup handle"
-
-
-@pytest.fixture(scope="module")
-def L():
-    from pffft_amd import build
-    build.build()
-    return pa.lib()
 
 
 def frames(L, pfx, h, signal=P, signal_stride=0, nsignals=1, nframes=NFRAMES, hop=HOP, out=P, out_stride=0, output=1):
@@ -46,17 +39,13 @@ def syn(L, pfx, h, spectra=P, spectra_stride=0, nsignals=1, nframes=NFRAMES, hop
                                                         signal_stride, 1, None)
 
 
-def refused(rc, code, text):
-    assert rc == code and pa.last_error() == text, (rc, pa.last_error(), text)
-
-
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 @pytest.mark.parametrize("transform", [pa.REAL, pa.COMPLEX])
 def test_frame_matrix_entries(L, dtype, transform):
     s = pa.Setup(N, transform, dtype)
     other = pa.Setup(N, transform, np.float64 if dtype == np.float32 else np.float32)
     junk = C.create_string_buffer(4096)
-    pfx = "pffftd" if dtype == np.float64 else "pffft"
+    pfx = prefix(dtype)
     h = s.handle
     spp = 2 if transform == pa.COMPLEX else 1
     row, prow = N * spp, (N // 2 + 1 if transform == pa.REAL else N)

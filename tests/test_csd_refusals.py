@@ -8,22 +8,15 @@ import re
 import numpy as np
 import pytest
 
+from abi_kit import INVALID_HANDLE, INVALID_VALUE, L, prefix, refused  # noqa: F401
 import pffft_amd as pa
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INVALID_VALUE, INVALID_HANDLE = 1, 400      # hipErrorInvalidValue, hipErrorInvalidHandle
 PTR = 0x1000                                # a non-NULL "device pointer", 16-byte aligned: validation answers before anything reads it
 N, HOP, NFRAMES = 1024, 256, 4
 HANDLE = "pffft_hip: bad setup handle"
 PRE = "pffft_hip: csd: "
 CROSS, ALL, COHERENCE = 0, 1, 2
-
-
-@pytest.fixture(scope="module")
-def L():
-    from pffft_amd import build
-    build.build()
-    return pa.lib()
 
 
 def csd(L, pfx, h, x=PTR, x_stride=0, y=2 * PTR, y_stride=0, nsignals=1, nframes=NFRAMES, hop=HOP, navg=0, what=CROSS, out=3 * PTR,
@@ -32,17 +25,13 @@ def csd(L, pfx, h, x=PTR, x_stride=0, y=2 * PTR, y_stride=0, nsignals=1, nframes
                                                      out_stride, None)
 
 
-def refused(rc, code, text):
-    assert rc == code and pa.last_error() == text, (rc, pa.last_error(), text)
-
-
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 @pytest.mark.parametrize("transform", [pa.REAL, pa.COMPLEX])
 def test_refusals(L, dtype, transform):
     s = pa.Setup(N, transform, dtype)
     other = pa.Setup(N, transform, np.float64 if dtype == np.float32 else np.float32)
     junk = C.create_string_buffer(4096)
-    pfx = "pffftd" if dtype == np.float64 else "pffft"
+    pfx = prefix(dtype)
     h = s.handle
     spp = 2 if transform == pa.COMPLEX else 1
     P = N // 2 + 1 if transform == pa.REAL else N

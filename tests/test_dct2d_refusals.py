@@ -6,10 +6,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from abi_kit import INVALID_HANDLE, INVALID_VALUE, L, prefix, refused  # noqa: F401
 import dct2d_model as d2
 import pffft_amd as pa
 
-INVALID_VALUE, INVALID_HANDLE = 1, 400      # hipErrorInvalidValue, hipErrorInvalidHandle
 P = 0x100000                                # a non-NULL "device pointer", 16-byte aligned: validation answers before anything reads it
 O = 0x4000000
 HANDLE = "pffft_hip: bad dct2d setup handle"
@@ -18,19 +18,8 @@ ALIGN = PRE + "in / out not aligned to 16 bytes"
 OVERLAP = PRE + "out overlaps in (in == out, in place, is the one legal overlap)"
 
 
-@pytest.fixture(scope="module")
-def L():
-    from pffft_amd import build
-    build.build()
-    return pa.lib()
-
-
 def call(L, pfx, h, x=P, out=O, batch=1):
     return getattr(L, f"{pfx}_hip_dct2d_transform_batch")(h, x, out, batch, None)
-
-
-def refused(rc, code, text):
-    assert rc == code and pa.last_error() == text, (rc, pa.last_error(), text)
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=lambda d: np.dtype(d).name)
@@ -73,7 +62,7 @@ def test_refusals(L, dtype):
     plain = pa.Setup(64, pa.REAL, dtype)                        # nor is a transform setup
     r2 = pa.Rfft2Setup(rows, cols, dtype=dtype)                 # nor another 2-D handle
     junk = C.create_string_buffer(4096)
-    pfx = "pffftd" if dtype == np.float64 else "pffft"
+    pfx = prefix(dtype)
     h = s.handle
 
     for bad in (None, other.handle, one_d.handle, plain.handle, r2.handle, C.addressof(junk)):

@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+from abi_kit import L  # noqa: F401
 import accuracy_model as am
 import dct_model as dm
 import pffft_amd as pa
@@ -17,13 +18,6 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "dct_golden.npz")
 MODEL_SIZES = (32, 96, 1024, 2048, 4096, 8192, 20480, 65536)
 SCIPY = {dm.DCT2: ("dct", 2), dm.DCT3: ("dct", 3), dm.DST2: ("dst", 2), dm.DST3: ("dst", 3)}
-
-
-@pytest.fixture(scope="module")
-def L():
-    from pffft_amd import build
-    build.build()
-    return pa.lib()
 
 
 def white(N, rows, dtype, seed):

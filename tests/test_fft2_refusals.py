@@ -8,10 +8,10 @@ import re
 import numpy as np
 import pytest
 
+from abi_kit import INVALID_HANDLE, INVALID_VALUE, L, prefix, refused  # noqa: F401
 import fft2_model as f2
 import pffft_amd as pa
 
-INVALID_VALUE, INVALID_HANDLE = 1, 400      # hipErrorInvalidValue, hipErrorInvalidHandle
 P = 0x100000                                # a non-NULL "device pointer", 16-byte aligned: validation answers before anything reads it
 O = 0x4000000
 HANDLE = "pffft_hip: bad fft2 setup handle"
@@ -21,19 +21,8 @@ OVERLAP = PRE + "out overlaps in (in == out, in place, is the one legal overlap)
 FWD, BWD = 0, 1
 
 
-@pytest.fixture(scope="module")
-def L():
-    from pffft_amd import build
-    build.build()
-    return pa.lib()
-
-
 def call(L, pfx, h, x=P, out=O, batch=1, d=FWD):
     return getattr(L, f"{pfx}_hip_fft2_transform_batch")(h, x, out, batch, d, 1.0, None)
-
-
-def refused(rc, code, text):
-    assert rc == code and pa.last_error() == text, (rc, pa.last_error(), text)
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
@@ -67,7 +56,7 @@ def test_refusals(L, dtype):
     plain = pa.Setup(64, pa.COMPLEX, dtype)                     # a transform setup is no fft2 handle
     xc = pa.XcorrSetup(64, dtype=dtype)                         # nor is another derived handle
     junk = C.create_string_buffer(4096)
-    pfx = "pffftd" if dtype == np.float64 else "pffft"
+    pfx = prefix(dtype)
     h = s.handle
 
     for bad in (None, other.handle, plain.handle, xc.handle, C.addressof(junk)):

@@ -11,11 +11,11 @@ import pytest
 import accuracy_model as am
 import fft2_model as f2
 import fft2conv_model as fc
+from gpu_kit import shape_id
 
 ROOT = os.path.join(os.path.dirname(__file__), "..")
 SHAPES = list(fc.FUSED_SHAPES) + [(48, 80), (16, 1024)]
 BATCH = 5
-shape_id = lambda s: f"{s[0]}x{s[1]}"  # noqa: E731
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=lambda d: np.dtype(d).name)

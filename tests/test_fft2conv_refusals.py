@@ -6,10 +6,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from abi_kit import Fake, INVALID_HANDLE, INVALID_VALUE, L, prefix, refused  # noqa: F401
 import fft2conv_model as fc
 import pffft_amd as pa
 
-INVALID_VALUE, INVALID_HANDLE = 1, 400      # hipErrorInvalidValue, hipErrorInvalidHandle
 P = 0x100000                                # non-NULL "device pointers", 16-byte aligned: validation answers before anything reads them
 O = 0x4000000
 G = 0x8000000
@@ -21,19 +21,8 @@ OVERLAP = PRE + "out overlaps in (in == out, in place, is the one legal overlap)
 H_OVERLAP = PRE + "H overlaps out"
 
 
-@pytest.fixture(scope="module")
-def L():
-    from pffft_amd import build
-    build.build()
-    return pa.lib()
-
-
 def call(L, pfx, h, x=P, H=G, out=O, batch=1, conj_h=0, bc=1):
     return getattr(L, f"{pfx}_hip_fft2_convolve_batch")(h, x, H, out, 1.0, batch, conj_h, bc, None)
-
-
-def refused(rc, code, text):
-    assert rc == code and pa.last_error() == text, (rc, pa.last_error(), text)
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=lambda d: np.dtype(d).name)
@@ -44,7 +33,7 @@ def test_refusals(L, dtype):
     plain = pa.Setup(64, pa.COMPLEX, dtype)                     # a transform setup is no fft2 handle
     r2 = pa.Rfft2Setup(32, 64, dtype=dtype)               # nor is another derived handle
     junk = C.create_string_buffer(4096)
-    pfx = "pffftd" if dtype == np.float64 else "pffft"
+    pfx = prefix(dtype)
     h = s.handle
 
     for bad in (None, other.handle, plain.handle, r2.handle, C.addressof(junk)):
@@ -116,23 +105,8 @@ def test_routes_and_selectors(L):
 def test_python_refuses_other_spectrum_sizes():
     """convolve_batch takes H of one image or of as many as x: the count is checked before anything else is looked at."""
     s = pa.Fft2Setup(16, 16)
-
-    class Fake:                                    # what _whole_rows reads of a tensor
-        is_cuda, dtype = True, None
-
-        def __init__(self, n):
-            self.n = n
-
-        def is_contiguous(self):
-            return True
-
-        def numel(self):
-            return self.n
-
-        def data_ptr(self):
-            raise AssertionError("a refused call reads no pointer")
-    Fake.dtype = s._torch_dtype()
+    tdt = s._torch_dtype()
     for images in (0, 2, 4):
         with pytest.raises(ValueError, match="1 .broadcast. or as many as x"):
-            s.convolve_batch(Fake(3 * 512), Fake(images * 512))
+            s.convolve_batch(Fake(3 * 512, tdt), Fake(images * 512, tdt))    # Fake: what _whole_rows reads of a tensor
     s.close()

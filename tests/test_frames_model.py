@@ -5,6 +5,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from abi_kit import L, prefix  # noqa: F401
 import accuracy_model as am
 import frames_model as fm
 import pffft_amd as pa
@@ -95,11 +96,6 @@ def test_hann_quarter_hop_round_trip_float64():
 
 
 # ------------------------------------------------------------------ validation rules, no device
-@pytest.fixture(scope="module")
-def L():
-    return pa.lib()
-
-
 PTR = 0x1000   # a non-NULL "device pointer": validation must answer before anything dereferences or launches
 
 
@@ -118,7 +114,7 @@ def _sy(L, pfx, h, spectra_stride=0, nsignals=1, nframes=4, hop=256, signal_stri
 def test_validation_before_any_device(L, dtype, transform):
     s = pa.Setup(1024, transform, dtype)
     other = pa.Setup(1024, transform, np.float64 if dtype == np.float32 else np.float32)
-    pfx = "pffftd" if dtype == np.float64 else "pffft"
+    pfx = prefix(dtype)
     N, spp = 1024, (2 if transform == pa.COMPLEX else 1)
     row = N * spp
     prow = N // 2 + 1 if transform == pa.REAL else N

@@ -18,13 +18,13 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pffft_amd as pa  # noqa: E402
-from gpu_kit import best_of, bits, mem_free, need_gpu, same_bits, SENTINEL, TDT, traced, under, uniform_t  # noqa: E402,F401
+from gpu_kit import (alternating, assert_refusal, assert_replays, bits, cell_times, mem_free, need_gpu, PEAK, refused_in_capture, same_bits,  # noqa: E402,F401
+                     SENTINEL, TDT, traced, under, uniform_t)
 
 SEL_COMPOSED, SEL_FUSED = an.AB_ANALYTIC_COMPOSED, an.AB_ANALYTIC_FUSED
 DTYPES = [np.float32, np.float64]
 SIZES = (16, 32, 96, 512, 1024, 2048, 4096, 8192, 20480)
 BATCHES = (1, 7, 1000)
-PEAK = 8e12
 BYTES = {"analytic": 12, "hilbert": 8, "envelope": 8}      # per sample of a float row: read + written by the fused kernel
 # the default route per (N, what), analytic_fused_default of analytic_tu.hip (DESIGN.md §3.24 has the measured table)
 FUSED_DEFAULT = {(N, what): True for N in an.FUSED_SIZES for what in an.WHATS}
@@ -166,20 +166,6 @@ def test_graph_replay_and_capture_rules():
     fresh = pa.AnalyticSetup(N)
     st = torch.cuda.Stream()
 
-    def refused_in_capture(call):
-        g = torch.cuda.CUDAGraph()
-        msg = ""
-        with torch.cuda.graph(g, stream=st):
-            try:
-                call()
-            except RuntimeError as ex:
-                msg = str(ex)
-            finally:
-                pa.set_variant(0)
-        assert "graph capture" in msg and "(900)" in msg, msg
-        del g
-        st.synchronize()
-
     try:
         with torch.cuda.stream(st):
             x_t = torch.empty((batch, N), device="cuda", dtype=torch.float32).uniform_(-1, 1)
@@ -187,16 +173,14 @@ def test_graph_replay_and_capture_rules():
             out_c = torch.full_like(out_f, SENTINEL)
             out_e = torch.full((batch, N), SENTINEL, device="cuda", dtype=torch.float32)
             st.synchronize()
-            refused_in_capture(lambda: fresh.transform_batch(x_t, out_f, "analytic"))                  # the tables
-            assert bool((out_f == SENTINEL).all()), "a refused call launched something"
+            assert_refusal(refused_in_capture(st, lambda: fresh.transform_batch(x_t, out_f, "analytic"), (out_f,)), "(900)")   # the tables
             s.transform_batch(x_t[:8].contiguous(), None, "analytic")     # the tables exist; the scratch image of this stream does not
             st.synchronize()
 
             def grow():
                 pa.set_variant(SEL_COMPOSED)
                 s.transform_batch(x_t, out_e, "envelope")
-            refused_in_capture(grow)
-            assert bool((out_e == SENTINEL).all()), "a refused call launched something"
+            assert_refusal(refused_in_capture(st, grow, (out_e,)), "(900)")
             gf, gc = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
             with torch.cuda.graph(gf, stream=st):
                 pa.set_variant(SEL_FUSED)
@@ -206,21 +190,19 @@ def test_graph_replay_and_capture_rules():
                 pa.set_variant(SEL_COMPOSED)
                 s.transform_batch(x_t, out_c, "analytic")
                 pa.set_variant(0)
-            for rep in range(3):
-                x_t.uniform_(-1, 1)
-                st.synchronize()
+
+            def eager():
                 pa.set_variant(SEL_FUSED)
                 want_f = s.transform_batch(x_t, None, "analytic")
                 pa.set_variant(SEL_COMPOSED)
                 want_c = s.transform_batch(x_t, None, "analytic")
                 pa.set_variant(0)
-                st.synchronize()
+                return want_f, want_c
+
+            def at_the_truth(rep, wants):
                 x8 = x_t[:8].cpu().numpy()
-                check(want_c[:8].cpu().numpy(), an.truth(x8, N, "analytic"), N, np.float32, rep)
-                out_f.zero_(); out_c.zero_()
-                gf.replay(); gc.replay()
-                st.synchronize()
-                assert same_bits(out_f, want_f) and same_bits(out_c, want_c), rep
+                check(wants[1][:8].cpu().numpy(), an.truth(x8, N, "analytic"), N, np.float32, rep)
+            assert_replays(st, (gf, gc), lambda: x_t.uniform_(-1, 1), eager, (out_f, out_c), 3, at_the_truth)
     finally:
         pa.set_variant(0)
     s.close()
@@ -257,15 +239,6 @@ def test_memory_is_back_after_close():
 
 
 # ------------------------------------------------------------------ 6. time
-def alternating(fa, fb, rounds=5):
-    """Per function the round-bests of `rounds` alternating rounds (gpu_kit.best_of: the best of three runs of 20 calls each)."""
-    ta, tb = [], []
-    for _ in range(rounds):
-        ta.append(best_of(fa))
-        tb.append(best_of(fb))
-    return ta, tb
-
-
 @pytest.mark.parametrize("what", an.WHATS)
 @pytest.mark.parametrize("N", (1024, 4096))
 def test_fused_beats_what_the_library_offered_before(N, what):
@@ -298,7 +271,7 @@ def test_fused_beats_what_the_library_offered_before(N, what):
         torch.cuda.synchronize()
         if what != "envelope":                      # (torch's abs is its own arithmetic)
             assert same_bits(got, want.view(got.shape)), "the baseline computes something else"
-        tf, tb = alternating(fused, baseline)
+        tf, tb = alternating((fused, baseline))
     finally:
         pa.set_variant(0)
     spread, ratio = max(tb) / min(tb), min(tb) / min(tf)
@@ -327,13 +300,7 @@ def test_default_cells():
                     pa.set_variant(sel)
                     s.transform_batch(x, y, what)
                 return f
-            try:
-                for sel in (SEL_FUSED, SEL_COMPOSED):
-                    at(sel)()
-                    torch.cuda.synchronize()
-                tf, tc = alternating(at(SEL_FUSED), at(SEL_COMPOSED))
-            finally:
-                pa.set_variant(0)
+            tf, tc = cell_times(at, SEL_FUSED, SEL_COMPOSED)
             spread, ratio = max(tc) / min(tc), min(tc) / min(tf)
             print(f"ANALYTIC CELL N={N} {what} batch={batch}: fused {min(tf) * 1e6:.1f} us, composed {min(tc) * 1e6:.1f} us, ratio {ratio:.2f} "
                   f"(composed spread {spread:.3f}), {BYTES[what] * N * batch / PEAK / min(tf):.3f} of the 8 TB/s roofline")

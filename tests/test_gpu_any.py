@@ -15,7 +15,8 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pffft_amd as pa  # noqa: E402
-from gpu_kit import kernels_run, kinds_by, mem_free, need_gpu, same_bits, TDT, under  # noqa: E402,F401
+from gpu_kit import (assert_refusal, kernels_run, kinds_by, mem_free, need_gpu, PEAK, refused_in_capture, same_bits, SENTINEL,  # noqa: E402,F401
+                     TDT, under)
 
 AB_ANY_COMPOSED, AB_ANY_FUSED = 132, 133
 DTYPES = [np.float32, np.float64]
@@ -23,7 +24,6 @@ DT = TDT
 SIZES = [1, 2, 3, 17, 100, 127, 129, 255, 257, 500, 509, 1000, 1021, 1023, 1025, 2047, 2049, 4093, 10007, 65537, 100003, 1000003]
 FUSED_SIZES = [N for N in SIZES if ym.expected_route(N, np.float32) == "fused"]
 BATCHES = (1, 7, 1000)
-PEAK = 8e12
 
 
 def kinds(names):
@@ -208,40 +208,24 @@ def test_graph_replay_capture_rule_and_two_streams():
     N, batch = 1021, 5000         # at most 4 groups per resident workgroup: one group per workgroup in dispatch order, no counter (the loop: test_gpu_launch_shapes.py)
     s = pa.AnySetup(N, pa.COMPLEX, np.float32)
     st = torch.cuda.Stream()
+
+    def grows():
+        pa.set_variant(AB_ANY_COMPOSED)
+        s.transform_batch(x_t, out_c, pa.FORWARD)
+
     try:
         with torch.cuda.stream(st):
             x_t = torch.empty((batch, 2 * N), device="cuda", dtype=torch.float32).uniform_(-1, 1)
-            out_f = torch.full_like(x_t, -77.0)
-            out_c = torch.full_like(x_t, -77.0)
+            out_f = torch.full_like(x_t, SENTINEL)
+            out_c = torch.full_like(x_t, SENTINEL)
             st.synchronize()
-            g0 = torch.cuda.CUDAGraph()
-            msg = ""
-            with torch.cuda.graph(g0, stream=st):
-                try:
-                    s.transform_batch(x_t, out_f, pa.FORWARD)
-                except RuntimeError as ex:
-                    msg = str(ex)
-            assert "graph capture" in msg and "(900)" in msg, msg          # the tables: hipErrorStreamCaptureUnsupported
-            del g0
-            st.synchronize()
+            # the tables: hipErrorStreamCaptureUnsupported
+            assert_refusal(refused_in_capture(st, lambda: s.transform_batch(x_t, out_f, pa.FORWARD)), "(900)")
             pa.set_variant(AB_ANY_FUSED)
             s.transform_batch(x_t[:8].contiguous(), None, pa.FORWARD)      # the tables exist; the scratch image of this stream does not
             pa.set_variant(0)
             st.synchronize()
-            g1 = torch.cuda.CUDAGraph()
-            msg = ""
-            with torch.cuda.graph(g1, stream=st):
-                pa.set_variant(AB_ANY_COMPOSED)
-                try:
-                    s.transform_batch(x_t, out_c, pa.FORWARD)
-                except RuntimeError as ex:
-                    msg = str(ex)
-                finally:
-                    pa.set_variant(0)
-            assert "graph capture" in msg and "(900)" in msg, msg
-            del g1
-            st.synchronize()
-            assert bool((out_c == -77.0).all()) and bool((out_f == -77.0).all()), "a refused call launched something"
+            assert_refusal(refused_in_capture(st, grows, (out_c, out_f)), "(900)")
 
             def calls():
                 pa.set_variant(AB_ANY_FUSED)

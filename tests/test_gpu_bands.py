@@ -20,7 +20,8 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pffft_amd as pa  # noqa: E402
-from gpu_kit import assert_guards, assert_same_bits, best_of, guarded, kernels_run, make_signal, need_gpu, same_bits, SENTINEL, TDT, traced, windows  # noqa: E402,F401
+from gpu_kit import (alternating, assert_guards, assert_refusal, assert_same_bits, guarded, kernels_run, make_signal, need_gpu,  # noqa: E402,F401
+                     PEAK, refused_in_capture, same_bits, SENTINEL, TDT, traced, windows)
 
 AB_BANDS_COMPOSED, AB_BANDS_FUSED = 160, 161
 SELECTORS = {"default": 0, "composed": AB_BANDS_COMPOSED, "fused": AB_BANDS_FUSED}
@@ -28,7 +29,6 @@ FUSED_N = (1024, 2048, 4096)
 TPT = {1024: 32, 2048: 64, 4096: 128}       # threads per transform of the stored configuration (TiledPick C512 / C1024 / C2048)
 SCALING = 1.0 / 37.0                        # no power of two: the one product rounds
 FS = 16000.0
-PEAK = 8e12
 # bands_fused_default of bands_tu.hip, as measured by tools/bands_bench.py
 FUSED_DEFAULT = {1024: True, 2048: True, 4096: True}
 # The installed ROCm states no ulp bound for logf / log.  Measured on the device over the inputs of test_log: the worst
@@ -394,19 +394,6 @@ def test_graph_replay_and_the_capture_rules():
     w_t = torch.from_numpy(fm.hann(N, np.float32)).cuda()
     st = torch.cuda.Stream()
 
-    def refused_in_capture(fn):
-        g0 = torch.cuda.CUDAGraph()
-        msg = ""
-        with torch.cuda.graph(g0, stream=st):
-            try:
-                fn()
-            except RuntimeError as ex:
-                msg = str(ex)
-            finally:
-                pa.set_variant(0)
-        del g0
-        return msg
-
     try:
         with torch.cuda.stream(st):
             sig = torch.empty((nframes - 1) * hop + N, device="cuda", dtype=torch.float32).uniform_(-1, 1)
@@ -417,8 +404,7 @@ def test_graph_replay_and_the_capture_rules():
             def first_call():
                 pa.set_variant(AB_BANDS_FUSED)
                 b.bands_batch(sig, hop, nframes, w_t, SCALING, out=out["fused"])
-            msg = refused_in_capture(first_call)
-            assert "graph capture" in msg and "tables of this setup" in msg, msg
+            assert_refusal(refused_in_capture(st, first_call), "tables of this setup")
             pa.set_variant(AB_BANDS_FUSED)
             b.bands_batch(sig, hop, nframes, w_t, SCALING, out=out["fused"])         # binds the handle; the fused route takes no scratch
             pa.set_variant(0)
@@ -427,8 +413,7 @@ def test_graph_replay_and_the_capture_rules():
             def grows():
                 pa.set_variant(AB_BANDS_COMPOSED)
                 b.bands_batch(sig, hop, nframes, w_t, SCALING, out=out["composed"])
-            msg = refused_in_capture(grows)
-            assert "graph capture" in msg and "band scratch" in msg, msg
+            assert_refusal(refused_in_capture(st, grows), "band scratch")
 
             def calls():
                 pa.set_variant(AB_BANDS_FUSED)
@@ -502,15 +487,6 @@ def test_frames_beyond_the_scratch_cap_go_through_in_chunks():
 
 
 # ------------------------------------------------------------------ time
-def alternating(fns, rounds=5):
-    """Per function the round-bests of `rounds` alternating rounds (gpu_kit.best_of: the best of three runs of 20 calls each)."""
-    ts = [[] for _ in fns]
-    for _ in range(rounds):
-        for t, f in zip(ts, fns):
-            t.append(best_of(f))
-    return ts
-
-
 @pytest.mark.parametrize("N", FUSED_N)
 def test_default_cells(N):
     """The default route of every fused size is the recorded one, and it is not the slower one: one real float signal of 64 MiB, periodic

@@ -23,7 +23,7 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pffft_amd as pa  # noqa: E402
-from gpu_kit import assert_guards, assert_same_bits, guarded, kernels_run, make_signal, need_gpu, same_bits, SENTINEL, traced, windows  # noqa: E402,F401
+from gpu_kit import assert_guards, assert_same_bits, guarded, kernels_run, make_signal, need_gpu, PEAK, same_bits, SENTINEL, traced, windows  # noqa: E402,F401
 
 AB_CSD_COMPOSED, AB_CSD_FUSED = 142, 143
 SELECTORS = {"default": 0, "composed": AB_CSD_COMPOSED, "fused": AB_CSD_FUSED}
@@ -31,7 +31,6 @@ FUSED_N = (1024, 2048, 4096)
 NAVG = (1, 2, 32, 33, 65, 0)
 NFRAMES_ALL = 70                    # frames per signal of the navg = 0 cases: runs of 32, 32 and 6
 SCALING = 1.0 / 37.0                # no power of two: the one product rounds
-PEAK = 8e12
 GATHER2 = ["frames_gather_kernel", "frames_gather_kernel"]
 
 

@@ -20,7 +20,8 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pffft_amd as pa  # noqa: E402
-from gpu_kit import best_of, bits, guarded, kinds_by, mem_free, need_gpu, same_bits, SENTINEL, TDT, traced, under, uniform_t  # noqa: E402,F401
+from gpu_kit import (assert_refusal, assert_replays, best_of, bits, guarded, kinds_by, mem_free, need_gpu, PEAK, refused_in_capture,  # noqa: E402,F401
+                     same_bits, SENTINEL, TDT, traced, under, uniform_t)
 
 SEL_COMPOSED, SEL_FUSED = dm.AB_DCT_COMPOSED, dm.AB_DCT_FUSED
 DTYPES = [np.float32, np.float64]
@@ -28,7 +29,6 @@ DT = TDT
 SIZES = (32, 96, 1024, 2048, 4096, 8192, 20480, 65536)
 BATCHES = (1, 7, 1000)
 NORM_ARG = {dm.NORM_NONE: None, dm.NORM_ORTHO: "ortho"}
-PEAK = 8e12
 SHORT = 256
 # the default route per (N, kind), dct_fused_default of dct_tu.hip (DESIGN.md §3.16 has the measured table): test_default_cells asserts it
 FUSED_DEFAULT = {(N, kind): True for N in dm.FUSED_SIZES for kind in dm.KINDS}
@@ -225,6 +225,23 @@ def test_graph_replay_and_capture_rule():
     N, batch = 1024, 3000
     s = setup(N, dm.DCT2)
     st = torch.cuda.Stream()
+
+    def grows():
+        pa.set_variant(SEL_COMPOSED)
+        s.transform_batch(x_t, out_c)
+
+    def eager():
+        pa.set_variant(SEL_FUSED)
+        want_f = s.transform_batch(x_t)
+        pa.set_variant(SEL_COMPOSED)
+        want_c = s.transform_batch(x_t)
+        pa.set_variant(0)
+        return want_f, want_c
+
+    def at_the_truth(rep, wants):
+        x8 = x_t[:8].cpu().numpy()
+        am.check(wants[1][:8].cpu().numpy(), dm.truth(x8, N, dm.DCT2, dm.NORM_NONE), N, np.float32, rep)
+
     try:
         with torch.cuda.stream(st):
             x_t = torch.empty((batch, N), device="cuda", dtype=torch.float32).uniform_(-1, 1)
@@ -234,20 +251,7 @@ def test_graph_replay_and_capture_rule():
             s.transform_batch(x_t[:8].contiguous())        # the table exists; the scratch image of this stream does not
             pa.set_variant(0)
             st.synchronize()
-            g1 = torch.cuda.CUDAGraph()
-            msg = ""
-            with torch.cuda.graph(g1, stream=st):
-                pa.set_variant(SEL_COMPOSED)
-                try:
-                    s.transform_batch(x_t, out_c)
-                except RuntimeError as ex:
-                    msg = str(ex)
-                finally:
-                    pa.set_variant(0)
-            assert "graph capture" in msg and "(900)" in msg, msg
-            del g1
-            st.synchronize()
-            assert bool((out_c == SENTINEL).all()), "a refused call launched something"
+            assert_refusal(refused_in_capture(st, grows, (out_c,)), "(900)")
             gf = torch.cuda.CUDAGraph()                    # fused: no warm-up scratch
             with torch.cuda.graph(gf, stream=st):
                 pa.set_variant(SEL_FUSED)
@@ -262,21 +266,7 @@ def test_graph_replay_and_capture_rule():
                 pa.set_variant(SEL_COMPOSED)
                 s.transform_batch(x_t, out_c)
                 pa.set_variant(0)
-            for rep in range(3):
-                x_t.uniform_(-1, 1)
-                st.synchronize()
-                pa.set_variant(SEL_FUSED)
-                want_f = s.transform_batch(x_t)
-                pa.set_variant(SEL_COMPOSED)
-                want_c = s.transform_batch(x_t)
-                pa.set_variant(0)
-                st.synchronize()
-                x8 = x_t[:8].cpu().numpy()
-                am.check(want_c[:8].cpu().numpy(), dm.truth(x8, N, dm.DCT2, dm.NORM_NONE), N, np.float32, rep)
-                out_f.zero_(); out_c.zero_()
-                gf.replay(); gc.replay()
-                st.synchronize()
-                assert same_bits(out_f, want_f) and same_bits(out_c, want_c), rep
+            assert_replays(st, (gf, gc), lambda: x_t.uniform_(-1, 1), eager, (out_f, out_c), 3, at_the_truth)
     finally:
         pa.set_variant(0)
     s.close()

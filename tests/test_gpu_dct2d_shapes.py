@@ -13,12 +13,11 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pffft_amd as pa  # noqa: E402
-from gpu_kit import assert_guards, assert_same_bits, guarded, need_gpu, traced, under, uniform_t  # noqa: E402,F401
+from gpu_kit import assert_guards, assert_same_bits, guarded, need_gpu, shape_id, traced, under, uniform_t  # noqa: E402,F401
 
 SEL_COMPOSED, SEL_FUSED = d2.AB_DCT2D_COMPOSED, d2.AB_DCT2D_FUSED
 SHORT = 256
 KINDS = (dm.DCT2, dm.DCT3, dm.DST2)
-shape_id = lambda s: f"{s[0]}x{s[1]}"  # noqa: E731
 kind_id = lambda k: dm.KIND_NAMES[k]  # noqa: E731
 
 

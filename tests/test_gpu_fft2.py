@@ -15,22 +15,16 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pffft_amd as pa  # noqa: E402
-from gpu_kit import (assert_guards, assert_same_bits, best_of, guarded, kernels_run, need_gpu, same_bits, SENTINEL, TDT,  # noqa: E402,F401
-                     under)
+from gpu_kit import (assert_guards, assert_refusal, assert_replays, assert_same_bits, cell_times, dev, guarded,  # noqa: E402,F401
+                     kernels_run, need_gpu, PEAK, refused_in_capture, SENTINEL, shape_id, TDT, under)
 
 SEL_COMPOSED, SEL_FUSED = f2.AB_FFT2_COMPOSED, f2.AB_FFT2_FUSED
 DTYPES = [np.float32, np.float64]
 DIRECTIONS = (("forward", f2.FORWARD), ("backward", f2.BACKWARD))
 COMPOSED_SHAPES = [(16, 16), (48, 80), (80, 48), (16, 1024), (1024, 16), (96, 256)]
 BATCHES = (1, 3, 37)
-PEAK = 8e12
 # the default route per fused shape, fft2_fused_default of fft2_tu.hip (DESIGN.md §3.26 has the measured table)
 FUSED_DEFAULT = {shape: True for shape in f2.FUSED_SHAPES}
-shape_id = lambda s: f"{s[0]}x{s[1]}"  # noqa: E731
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def run(s, x_t, sel=0, out=None, direction="forward", scaling=1.0):
@@ -250,17 +244,13 @@ def test_graph_replay_and_capture_rules():
         finally:
             pa.set_variant(0)
 
-    def refused_in_capture(sel, out, setup=None):
-        g, msg = torch.cuda.CUDAGraph(), ""
-        with torch.cuda.graph(g, stream=st):
-            try:
-                call(sel, out, setup)
-            except RuntimeError as ex:
-                msg = str(ex)
-        assert "graph capture" in msg and "(900)" in msg, msg
-        del g
-        st.synchronize()
-        assert bool((out == SENTINEL).all()), "a refused call launched something"
+    def refused(sel, out, setup=None):
+        assert_refusal(refused_in_capture(st, lambda: call(sel, out, setup), (out,)), "(900)")
+
+    def eager():
+        want_f, want_c = torch.empty_like(out_f), torch.empty_like(out_c)
+        call(SEL_FUSED, want_f); call(SEL_COMPOSED, want_c)
+        return want_f, want_c
 
     try:
         with torch.cuda.stream(st):
@@ -268,11 +258,11 @@ def test_graph_replay_and_capture_rules():
             out_f = torch.full((batch, row), SENTINEL, device="cuda", dtype=torch.float32)
             out_c = torch.full_like(out_f, SENTINEL)
             st.synchronize()
-            refused_in_capture(SEL_FUSED, out_f, fresh)                  # the binding
-            refused_in_capture(SEL_COMPOSED, out_c, fresh)
+            refused(SEL_FUSED, out_f, fresh)                             # the binding
+            refused(SEL_COMPOSED, out_c, fresh)
             under(SEL_FUSED, lambda: s.transform_batch(x_t[:8].contiguous(), None, "backward"))   # binds the device (fused: no image yet)
             st.synchronize()
-            refused_in_capture(SEL_COMPOSED, out_c)                      # the image of this stream would have to grow
+            refused(SEL_COMPOSED, out_c)                                 # the image of this stream would have to grow
             call(SEL_COMPOSED, out_c)                                    # the warm call
             st.synchronize()
             gf, gc = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
@@ -280,16 +270,7 @@ def test_graph_replay_and_capture_rules():
                 call(SEL_FUSED, out_f)
             with torch.cuda.graph(gc, stream=st):
                 call(SEL_COMPOSED, out_c)
-            for rep in range(2):
-                x_t.uniform_(-1, 1)
-                st.synchronize()
-                want_f, want_c = torch.empty_like(out_f), torch.empty_like(out_c)
-                call(SEL_FUSED, want_f); call(SEL_COMPOSED, want_c)
-                st.synchronize()
-                out_f.zero_(); out_c.zero_()
-                gf.replay(); gc.replay()
-                st.synchronize()
-                assert same_bits(out_f, want_f) and same_bits(out_c, want_c), rep
+            assert_replays(st, (gf, gc), lambda: x_t.uniform_(-1, 1), eager, (out_f, out_c), 2)
     finally:
         pa.set_variant(0)
     s.close()
@@ -297,15 +278,6 @@ def test_graph_replay_and_capture_rules():
 
 
 # ------------------------------------------------------------------ 5. time
-def alternating(fns, rounds=5):
-    """Per function the round-bests of `rounds` alternating rounds (gpu_kit.best_of: the best of three runs of 20 calls each)."""
-    ts = [[] for _ in fns]
-    for _ in range(rounds):
-        for t, f in zip(ts, fns):
-            t.append(best_of(f))
-    return ts
-
-
 @pytest.mark.parametrize("shape", f2.FUSED_SHAPES, ids=shape_id)
 def test_default_cells(shape):
     """The default route of every fused shape is the recorded one; where it is fused, selector 149 beats selector 148 by more than the
@@ -325,13 +297,7 @@ def test_default_cells(shape):
             pa.set_variant(sel)
             s.transform_batch(x, out)
         return f
-    try:
-        for sel in (SEL_FUSED, SEL_COMPOSED):
-            at(sel)()
-            torch.cuda.synchronize()
-        tf, tc = alternating((at(SEL_FUSED), at(SEL_COMPOSED)))
-    finally:
-        pa.set_variant(0)
+    tf, tc = cell_times(at, SEL_FUSED, SEL_COMPOSED)
     spread, ratio = max(tc) / min(tc), min(tc) / min(tf)
     moved = 2 * rows * cols * 8 * batch
     print(f"FFT2 CELL {rows}x{cols} batch={batch} default={'fused' if fused else 'composed'}: fused {min(tf) * 1e6:.1f} us, composed "

@@ -16,23 +16,16 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pffft_amd as pa  # noqa: E402
-from gpu_kit import (assert_guards, assert_same_bits, best_of, guarded, kernels_run, need_gpu, same_bits, TDT,  # noqa: E402,F401
-                     under)
+from gpu_kit import (assert_guards, assert_replays, assert_same_bits, cell_times, dev, dtype_id, guarded, kernels_run,  # noqa: E402,F401
+                     need_gpu, PEAK, shape_id, TDT, under)
 
 SEL_COMPOSED, SEL_FUSED = fc.AB_FFT2CONV_COMPOSED, fc.AB_FFT2CONV_FUSED
 DTYPES = [np.float32, np.float64]
 COMPOSED_SHAPES = [(16, 16), (64, 32), (48, 80), (80, 48), (16, 1024), (96, 256)]
 BATCHES = (1, 3, 37)
-PEAK = 8e12
 # the default route per fused shape for one broadcast H, fft2conv_fused_default of fft2_tu.hip (DESIGN.md §3.29 has the measured table)
 FUSED_DEFAULT = {shape: True for shape in fc.FUSED_SHAPES}
-shape_id = lambda s: f"{s[0]}x{s[1]}"  # noqa: E731
-dtype_id = lambda d: np.dtype(d).name  # noqa: E731
 CONJ = pytest.mark.parametrize("conj_h", [False, True], ids=["plain", "conj"])
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def run(s, x_t, H_t, sel=0, out=None, scaling=1.0, conj_h=False):
@@ -242,6 +235,11 @@ def test_graph_replay():
         finally:
             pa.set_variant(0)
 
+    def eager():
+        want_f, want_c = torch.empty_like(out_f), torch.empty_like(out_c)
+        call(SEL_FUSED, want_f); call(SEL_COMPOSED, want_c)
+        return want_f, want_c
+
     try:
         with torch.cuda.stream(st):
             x_t = torch.empty((batch, row), device="cuda", dtype=torch.float32).uniform_(-1, 1)
@@ -254,31 +252,13 @@ def test_graph_replay():
                 call(SEL_FUSED, out_f)
             with torch.cuda.graph(gc, stream=st):
                 call(SEL_COMPOSED, out_c)
-            for rep in range(2):
-                x_t.uniform_(-1, 1)
-                st.synchronize()
-                want_f, want_c = torch.empty_like(out_f), torch.empty_like(out_c)
-                call(SEL_FUSED, want_f); call(SEL_COMPOSED, want_c)
-                st.synchronize()
-                out_f.zero_(); out_c.zero_()
-                gf.replay(); gc.replay()
-                st.synchronize()
-                assert same_bits(out_f, want_f) and same_bits(out_c, want_c), rep
+            assert_replays(st, (gf, gc), lambda: x_t.uniform_(-1, 1), eager, (out_f, out_c), 2)
     finally:
         pa.set_variant(0)
     s.close()
 
 
 # ------------------------------------------------------------------ 5. time
-def alternating(fns, rounds=5):
-    """Per function the round-bests of `rounds` alternating rounds (gpu_kit.best_of: the best of three runs of 20 calls each)."""
-    ts = [[] for _ in fns]
-    for _ in range(rounds):
-        for t, f in zip(ts, fns):
-            t.append(best_of(f))
-    return ts
-
-
 @pytest.mark.parametrize("shape", fc.FUSED_SHAPES, ids=shape_id)
 def test_default_cells(shape):
     """The default route of every fused shape (one broadcast H) is the recorded one; where it is fused, selector 153 beats selector 152 by
@@ -300,13 +280,7 @@ def test_default_cells(shape):
             pa.set_variant(sel)
             s.convolve_batch(x, H_t, out)
         return f
-    try:
-        for sel in (SEL_FUSED, SEL_COMPOSED):
-            at(sel)()
-            torch.cuda.synchronize()
-        tf, tc = alternating((at(SEL_FUSED), at(SEL_COMPOSED)))
-    finally:
-        pa.set_variant(0)
+    tf, tc = cell_times(at, SEL_FUSED, SEL_COMPOSED)
     spread, ratio = max(tc) / min(tc), min(tc) / min(tf)
     moved = 2 * rows * cols * 8 * batch
     print(f"FFT2CONV CELL {rows}x{cols} batch={batch} default={'fused' if fused else 'composed'}: fused {min(tf) * 1e6:.1f} us, composed "

@@ -21,14 +21,14 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pffft_amd as pa  # noqa: E402
-from gpu_kit import best_of, bits, kinds_by, mem_free, need_gpu, same_bits, SENTINEL, TDT, traced, under, uniform_t  # noqa: E402,F401
+from gpu_kit import (assert_refusal, assert_replays, best_of, bits, kinds_by, mem_free, need_gpu, PEAK, refused_in_capture,  # noqa: E402,F401
+                     same_bits, SENTINEL, TDT, traced, under, uniform_t)
 
 SEL_COMPOSED, SEL_FUSED = mm.AB_MDCT_COMPOSED, mm.AB_MDCT_FUSED
 DTYPES = [np.float32, np.float64]
 DT = TDT
 SIZES = (32, 96, 512, 1024, 2048, 40960)
 SHAPES = ((1, 1), (3, 7), (2, 500))          # nsignals x nframes
-PEAK = 8e12
 SHORT = 256
 # the default route per (M, what), mdct_fused_default of mdct_tu.hip (DESIGN.md §3.19 has the measured table): test_default_cells asserts it
 FUSED_DEFAULT = {(M, what): True for M in mm.FUSED_SIZES for what in mm.WHATS}
@@ -388,6 +388,22 @@ def test_graph_replay_and_capture_rule():
     s = pa.MdctSetup(M)
     st = torch.cuda.Stream()
     w = torch.from_numpy(mm.sine_window(M, np.float32)).cuda()
+
+    def grows():
+        pa.set_variant(SEL_COMPOSED)
+        s.mdct(x_t, w, out=out_c)
+
+    def eager():
+        pa.set_variant(SEL_FUSED)
+        want_f = s.mdct(x_t, w)
+        pa.set_variant(SEL_COMPOSED)
+        want_c = s.mdct(x_t, w)
+        pa.set_variant(0)
+        return want_f, want_c
+
+    def at_the_truth(rep, wants):
+        am.check(wants[1][:8].cpu().numpy(), mm.truth_mdct(x_t[:9 * M].cpu().numpy(), M, 8, w.cpu().numpy())[0], M, np.float32, rep)
+
     try:
         with torch.cuda.stream(st):
             x_t = torch.empty(((nframes + 1) * M,), device="cuda", dtype=torch.float32).uniform_(-1, 1)
@@ -397,20 +413,7 @@ def test_graph_replay_and_capture_rule():
             s.mdct(x_t[:9 * M].contiguous(), w)             # the tables exist; the scratch image of this stream does not
             pa.set_variant(0)
             st.synchronize()
-            g1 = torch.cuda.CUDAGraph()
-            msg = ""
-            with torch.cuda.graph(g1, stream=st):
-                pa.set_variant(SEL_COMPOSED)
-                try:
-                    s.mdct(x_t, w, out=out_c)
-                except RuntimeError as ex:
-                    msg = str(ex)
-                finally:
-                    pa.set_variant(0)
-            assert "graph capture" in msg and "(900)" in msg, msg
-            del g1
-            st.synchronize()
-            assert bool((out_c == SENTINEL).all()), "a refused call launched something"
+            assert_refusal(refused_in_capture(st, grows, (out_c,)), "(900)")
             gf = torch.cuda.CUDAGraph()                    # fused: no warm-up scratch
             with torch.cuda.graph(gf, stream=st):
                 pa.set_variant(SEL_FUSED)
@@ -425,20 +428,7 @@ def test_graph_replay_and_capture_rule():
                 pa.set_variant(SEL_COMPOSED)
                 s.mdct(x_t, w, out=out_c)
                 pa.set_variant(0)
-            for rep in range(3):
-                x_t.uniform_(-1, 1)
-                st.synchronize()
-                pa.set_variant(SEL_FUSED)
-                want_f = s.mdct(x_t, w)
-                pa.set_variant(SEL_COMPOSED)
-                want_c = s.mdct(x_t, w)
-                pa.set_variant(0)
-                st.synchronize()
-                am.check(want_c[:8].cpu().numpy(), mm.truth_mdct(x_t[:9 * M].cpu().numpy(), M, 8, w.cpu().numpy())[0], M, np.float32, rep)
-                out_f.zero_(); out_c.zero_()
-                gf.replay(); gc.replay()
-                st.synchronize()
-                assert same_bits(out_f[0], want_f) and same_bits(out_c[0], want_c), rep
+            assert_replays(st, (gf, gc), lambda: x_t.uniform_(-1, 1), eager, (out_f[0], out_c[0]), 3, at_the_truth)
     finally:
         pa.set_variant(0)
     s.close()

@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pffft_amd as pa  # noqa: E402
-from gpu_kit import kernels_run, need_gpu, prototypes, short_name, TDT  # noqa: E402,F401
+from gpu_kit import assert_refusal, kernels_run, need_gpu, prototypes, refused_in_capture, SENTINEL, short_name, TDT  # noqa: E402,F401
 
 AB_PFB_COMPOSED, AB_PFB_FUSED = 126, 127
 AB_PFB_SYN_SCALAR, AB_PFB_SYN_PLAIN, AB_PFB_SYN_XCD = 128, 129, 131
@@ -366,18 +366,9 @@ def test_graph_replay_scratch_rule_and_two_streams():
             spec = torch.empty((nframes, 2 * N), device="cuda", dtype=torch.float32).uniform_(-1, 1)
             s.transform_batch(spec[:8].contiguous(), None, pa.BACKWARD, True)      # the setup's tables exist; its frame matrix does not
             st.synchronize()
-            back = torch.full((L,), -77.0, device="cuda", dtype=torch.float32)
-            g0 = torch.cuda.CUDAGraph()
-            msg = ""
-            with torch.cuda.graph(g0, stream=st):
-                try:
-                    s.pfb_synthesis_batch(spec, hop, g_t, 1.0 / N, back, True)
-                except RuntimeError as ex:
-                    msg = str(ex)
-            assert "graph capture" in msg and "(900)" in msg, msg      # hipErrorStreamCaptureUnsupported
-            del g0
-            st.synchronize()
-            assert bool((back == -77.0).all()), "the refused call launched something"
+            back = torch.full((L,), SENTINEL, device="cuda", dtype=torch.float32)
+            # hipErrorStreamCaptureUnsupported
+            assert_refusal(refused_in_capture(st, lambda: s.pfb_synthesis_batch(spec, hop, g_t, 1.0 / N, back, True), (back,)), "(900)")
 
             s.pfb_synthesis_batch(spec, hop, g_t, 1.0 / N, back, True)   # warm-up: the frame matrix of this stream
             st.synchronize()

@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pffft_amd as pa  # noqa: E402
-from gpu_kit import assert_guards, assert_same_bits, guarded, kernels_run, make_signal, need_gpu, same_bits, SENTINEL, TDT, traced, windows  # noqa: E402,F401
+from gpu_kit import assert_guards, assert_same_bits, guarded, kernels_run, make_signal, need_gpu, PEAK, same_bits, SENTINEL, TDT, traced, windows  # noqa: E402,F401
 
 AB_PSD_COMPOSED, AB_PSD_FUSED = 134, 135
 SELECTORS = {"default": 0, "composed": AB_PSD_COMPOSED, "fused": AB_PSD_FUSED}
@@ -29,7 +29,6 @@ NAVG = (1, 2, 31, 32, 33, 64, 65, 100, 0)
 NFRAMES_ALL = 70                    # frames per signal of the navg = 0 cases: runs of 32, 32 and 6
 SCALING = 1.0 / 37.0                # no power of two: the one product rounds
 DT = TDT
-PEAK = 8e12
 
 
 def power_rows(s, sig, hop, nframes, w_t):

@@ -14,22 +14,17 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pffft_amd as pa  # noqa: E402
-from gpu_kit import (assert_guards, assert_same_bits, best_of, guarded, kernels_run, mem_free, need_gpu, same_bits, SENTINEL, TDT,  # noqa: E402,F401
-                     under)
+from gpu_kit import (alternating, assert_guards, assert_refusal, assert_replays, assert_same_bits, cell_times, dev,  # noqa: E402,F401
+                     guarded, kernels_run, mem_free, need_gpu, PEAK, refused_in_capture, SENTINEL, TDT, under)
 
 SEL_COMPOSED, SEL_FUSED = rm.AB_RESAMPLE_COMPOSED, rm.AB_RESAMPLE_FUSED
 KINDS = [True, False]
 COMPOSED_PAIRS = [(16, 32), (32, 16), (16, 16), (96, 80), (80, 96), (512, 2048), (4096, 1024), (8192, 4096)]
 BATCHES = (1, 7, 300)
 SCALINGS = (1.0, 0.37)
-PEAK = 8e12
 pair_id = lambda p: f"{p[0]}to{p[1]}"
 # the default route per (N, M, real), resample_fused_default of resample_tu.hip (DESIGN.md §3.32 has the measured table)
 FUSED_DEFAULT = {(N, M, real): True for N, M in rm.FUSED_CELLS for real in KINDS}
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def run(s, x_t, sel=0, out=None, scaling=1.0):
@@ -234,17 +229,13 @@ def test_graph_replay_and_capture_rules():
         finally:
             pa.set_variant(0)
 
-    def refused_in_capture(sel, out, setup=None):
-        g, msg = torch.cuda.CUDAGraph(), ""
-        with torch.cuda.graph(g, stream=st):
-            try:
-                call(sel, out, setup)
-            except RuntimeError as ex:
-                msg = str(ex)
-        assert "graph capture" in msg and "(900)" in msg, msg
-        del g
-        st.synchronize()
-        assert bool((out == SENTINEL).all()), "a refused call launched something"
+    def refused(sel, out, setup=None):
+        assert_refusal(refused_in_capture(st, lambda: call(sel, out, setup), (out,)), "(900)")
+
+    def eager():
+        want_f, want_c = torch.empty_like(out_f), torch.empty_like(out_c)
+        call(SEL_FUSED, want_f); call(SEL_COMPOSED, want_c)
+        return want_f, want_c
 
     try:
         with torch.cuda.stream(st):
@@ -252,12 +243,12 @@ def test_graph_replay_and_capture_rules():
             out_f = torch.full((batch, 2 * M), SENTINEL, device="cuda", dtype=torch.float32)
             out_c = torch.full_like(out_f, SENTINEL)
             st.synchronize()
-            refused_in_capture(SEL_FUSED, out_f, fresh)                     # the binding
+            refused(SEL_FUSED, out_f, fresh)                                # the binding
             pa.set_variant(SEL_FUSED)
             s.resample_batch(x_t[:8].contiguous())                          # binds the device (fused: no scratch yet)
             pa.set_variant(0)
             st.synchronize()
-            refused_in_capture(SEL_COMPOSED, out_c)                         # the scratch of this stream would have to grow
+            refused(SEL_COMPOSED, out_c)                                    # the scratch of this stream would have to grow
             call(SEL_COMPOSED, out_c)                                       # the warm call
             st.synchronize()
             gf, gc = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
@@ -265,16 +256,7 @@ def test_graph_replay_and_capture_rules():
                 call(SEL_FUSED, out_f)
             with torch.cuda.graph(gc, stream=st):
                 call(SEL_COMPOSED, out_c)
-            for rep in range(3):
-                x_t.uniform_(-1, 1)
-                st.synchronize()
-                want_f, want_c = torch.empty_like(out_f), torch.empty_like(out_c)
-                call(SEL_FUSED, want_f); call(SEL_COMPOSED, want_c)
-                st.synchronize()
-                out_f.zero_(); out_c.zero_()
-                gf.replay(); gc.replay()
-                st.synchronize()
-                assert same_bits(out_f, want_f) and same_bits(out_c, want_c), rep
+            assert_replays(st, (gf, gc), lambda: x_t.uniform_(-1, 1), eager, (out_f, out_c), 3)
     finally:
         pa.set_variant(0)
     s.close()
@@ -311,15 +293,6 @@ def test_memory_is_back_after_close():
 
 
 # ------------------------------------------------------------------ 6. time
-def alternating(fns, rounds=5):
-    """Per function the round-bests of `rounds` alternating rounds (gpu_kit.best_of: the best of three runs of 20 calls each)."""
-    ts = [[] for _ in fns]
-    for _ in range(rounds):
-        for t, f in zip(ts, fns):
-            t.append(best_of(f))
-    return ts
-
-
 @pytest.mark.parametrize("real", KINDS, ids=["real", "complex"])
 @pytest.mark.parametrize("pair", [(1024, 2048), (4096, 1024)], ids=pair_id)
 def test_default_beats_the_callers_path(pair, real):
@@ -405,13 +378,7 @@ def test_default_cells(pair):
                 pa.set_variant(sel)
                 s.resample_batch(x, out)
             return f
-        try:
-            for sel in (SEL_FUSED, SEL_COMPOSED):
-                at(sel)()
-                torch.cuda.synchronize()
-            tf, tc = alternating((at(SEL_FUSED), at(SEL_COMPOSED)))
-        finally:
-            pa.set_variant(0)
+        tf, tc = cell_times(at, SEL_FUSED, SEL_COMPOSED)
         spread, ratio = max(tc) / min(tc), min(tc) / min(tf)
         moved = (N + M) * spp * 4 * batch
         print(f"RESAMPLE CELL {N}->{M} {'real' if real else 'complex'} batch={batch}: fused {min(tf) * 1e6:.1f} us, composed "

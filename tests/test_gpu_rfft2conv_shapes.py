@@ -12,11 +12,10 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pffft_amd as pa  # noqa: E402
-from gpu_kit import assert_guards, assert_same_bits, guarded, need_gpu, traced, under, uniform_t  # noqa: E402,F401
+from gpu_kit import assert_guards, assert_same_bits, guarded, need_gpu, shape_id, traced, under, uniform_t  # noqa: E402,F401
 
 SEL_COMPOSED, SEL_FUSED = rc.AB_RFFT2CONV_COMPOSED, rc.AB_RFFT2CONV_FUSED
 SHORT = 256
-shape_id = lambda s: f"{s[0]}x{s[1]}"  # noqa: E731
 
 
 @pytest.mark.parametrize("shape", rc.FUSED_SHAPES, ids=shape_id)

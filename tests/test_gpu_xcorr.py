@@ -17,25 +17,20 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pffft_amd as pa  # noqa: E402
-from gpu_kit import (assert_guards, assert_same_bits, best_of, bits, guarded, kernels_run, mem_free, need_gpu, same_bits, SENTINEL, TDT,  # noqa: E402,F401
-                     under)
+from gpu_kit import (alternating, assert_guards, assert_refusal, assert_replays, assert_same_bits, bits, cell_times, dev,  # noqa: E402,F401
+                     guarded, kernels_run, mem_free, need_gpu, PEAK, refused_in_capture, SENTINEL, TDT, under)
 
 SEL_COMPOSED, SEL_FUSED = xm.AB_XCORR_COMPOSED, xm.AB_XCORR_FUSED
 DTYPES = [np.float32, np.float64]
 KINDS = [True, False]
 SIZES = (16, 96, 512, 1024, 2048, 4096, 8192)
 BATCHES = (1, 7, 300)
-PEAK = 8e12
 # the default route per (N, real, weighting, auto), xcorr_fused_default of xcorr_tu.hip (DESIGN.md §3.25 has the measured table)
 FUSED_DEFAULT = {(N, real, w, auto): True for N in xm.FUSED_SIZES for real in KINDS for w in xm.WEIGHTS for auto in (False, True)}
 
 
 def sels_of(N, dtype):
     return (SEL_FUSED, SEL_COMPOSED) if xm.can_fuse(N, dtype) else (0,)
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def run(s, x_t, y_t, weighting, sel=0, out=None, scaling=1.0):
@@ -288,17 +283,16 @@ def test_graph_replay_and_capture_rules():
         finally:
             pa.set_variant(0)
 
-    def refused_in_capture(sel, out, setup=None):
-        g, msg = torch.cuda.CUDAGraph(), ""
-        with torch.cuda.graph(g, stream=st):
-            try:
-                call(sel, out, setup)
-            except RuntimeError as ex:
-                msg = str(ex)
-        assert "graph capture" in msg and "(900)" in msg, msg
-        del g
-        st.synchronize()
-        assert bool((out == SENTINEL).all()), "a refused call launched something"
+    def refused(sel, out, setup=None):
+        assert_refusal(refused_in_capture(st, lambda: call(sel, out, setup), (out,)), "(900)")
+
+    def refresh():
+        x_t.uniform_(-1, 1); y_t.uniform_(-1, 1)
+
+    def eager():
+        want_f, want_c = torch.empty_like(out_f), torch.empty_like(out_c)
+        call(SEL_FUSED, want_f); call(SEL_COMPOSED, want_c)
+        return want_f, want_c
 
     try:
         with torch.cuda.stream(st):
@@ -307,10 +301,10 @@ def test_graph_replay_and_capture_rules():
             out_f = torch.full((batch, row), SENTINEL, device="cuda", dtype=torch.float32)
             out_c = torch.full_like(out_f, SENTINEL)
             st.synchronize()
-            refused_in_capture(SEL_FUSED, out_f, fresh)                                      # the binding
+            refused(SEL_FUSED, out_f, fresh)                                                 # the binding
             s.correlate_batch(x_t[:8].contiguous(), y_t[:8].contiguous(), None, "plain")     # binds the device (fused: no image yet)
             st.synchronize()
-            refused_in_capture(SEL_COMPOSED, out_c)                                          # the image of this stream would have to grow
+            refused(SEL_COMPOSED, out_c)                                                     # the image of this stream would have to grow
             call(SEL_COMPOSED, out_c)                                                        # the warm call
             st.synchronize()
             gf, gc = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
@@ -318,16 +312,7 @@ def test_graph_replay_and_capture_rules():
                 call(SEL_FUSED, out_f)
             with torch.cuda.graph(gc, stream=st):
                 call(SEL_COMPOSED, out_c)
-            for rep in range(3):
-                x_t.uniform_(-1, 1); y_t.uniform_(-1, 1)
-                st.synchronize()
-                want_f, want_c = torch.empty_like(out_f), torch.empty_like(out_c)
-                call(SEL_FUSED, want_f); call(SEL_COMPOSED, want_c)
-                st.synchronize()
-                out_f.zero_(); out_c.zero_()
-                gf.replay(); gc.replay()
-                st.synchronize()
-                assert same_bits(out_f, want_f) and same_bits(out_c, want_c), rep
+            assert_replays(st, (gf, gc), refresh, eager, (out_f, out_c), 3)
     finally:
         pa.set_variant(0)
     s.close()
@@ -365,15 +350,6 @@ def test_memory_is_back_after_close():
 
 
 # ------------------------------------------------------------------ 7. time
-def alternating(fns, rounds=5):
-    """Per function the round-bests of `rounds` alternating rounds (gpu_kit.best_of: the best of three runs of 20 calls each)."""
-    ts = [[] for _ in fns]
-    for _ in range(rounds):
-        for t, f in zip(ts, fns):
-            t.append(best_of(f))
-    return ts
-
-
 @pytest.mark.parametrize("real", KINDS, ids=["real", "complex"])
 @pytest.mark.parametrize("N", (1024, 4096))
 def test_default_beats_the_callers_path(N, real):
@@ -460,13 +436,7 @@ def test_default_cells(N):
                         pa.set_variant(sel)
                         s.correlate_batch(x, None if auto else y, out, weighting)
                     return f
-                try:
-                    for sel in (SEL_FUSED, SEL_COMPOSED):
-                        at(sel)()
-                        torch.cuda.synchronize()
-                    tf, tc = alternating((at(SEL_FUSED), at(SEL_COMPOSED)))
-                finally:
-                    pa.set_variant(0)
+                tf, tc = cell_times(at, SEL_FUSED, SEL_COMPOSED)
                 spread, ratio = max(tc) / min(tc), min(tc) / min(tf)
                 moved = ((1 if auto else 2) * lx + 2 * lx - 1) * spp * 4 * batch
                 print(f"XCORR CELL N={N} {'real' if real else 'complex'} {weighting} {'auto' if auto else 'cross'} batch={batch}: fused "

@@ -13,15 +13,11 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pffft_amd as pa  # noqa: E402
-from gpu_kit import assert_guards, assert_same_bits, guarded, need_gpu, traced, under  # noqa: E402,F401
+from gpu_kit import assert_guards, assert_same_bits, dev, guarded, need_gpu, traced, under  # noqa: E402,F401
 
 SEL_FUSED = xm.AB_XCORR_FUSED
 SHORT = 256
 KINDS = [True, False]
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 @pytest.mark.parametrize("real", KINDS, ids=["real", "complex"])

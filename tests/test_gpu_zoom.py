@@ -24,13 +24,13 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pffft_amd as pa  # noqa: E402
-from gpu_kit import guarded, kinds_by, mem_free, need_gpu, same_bits, SENTINEL, TDT, traced, under, uniform_t  # noqa: E402,F401
+from gpu_kit import (assert_refusal, guarded, kinds_by, mem_free, need_gpu, PEAK, refused_in_capture, same_bits, SENTINEL, TDT,  # noqa: E402,F401
+                     traced, under, uniform_t)
 
 SEL_COMPOSED, SEL_FUSED = zm.AB_ZOOM_COMPOSED, zm.AB_ZOOM_FUSED
 DTYPES = [np.float32, np.float64]
 DT = TDT
 BATCHES = (1, 7, 1000)
-PEAK = 8e12
 SHORT = 256
 G = zm.on_grid
 # (N, K, f0, df), each for the failure it can expose: composed below N + K - 1 = 257 (3, 5) (200, 57); the smallest fused shape, odd ends
@@ -316,40 +316,24 @@ def test_graph_replay_capture_rule_and_two_streams():
     s = pa.ZoomSetup(N, K, 0.1, zm.on_grid(0.5 / K), np.float32)
     T = Truth(s, 3)
     st = torch.cuda.Stream()
+
+    def grows():
+        pa.set_variant(SEL_COMPOSED)
+        s.transform_batch(x_t, out_c, pa.FORWARD)
+
     try:
         with torch.cuda.stream(st):
             x_t = torch.empty((batch, 2 * N), device="cuda", dtype=torch.float32).uniform_(-1, 1)
             out_f = torch.full((batch, 2 * K), SENTINEL, device="cuda", dtype=torch.float32)
             out_c = torch.full_like(out_f, SENTINEL)
             st.synchronize()
-            g0 = torch.cuda.CUDAGraph()
-            msg = ""
-            with torch.cuda.graph(g0, stream=st):
-                try:
-                    s.transform_batch(x_t, out_f, pa.FORWARD)
-                except RuntimeError as ex:
-                    msg = str(ex)
-            assert "graph capture" in msg and "(900)" in msg, msg          # the tables: hipErrorStreamCaptureUnsupported
-            del g0
-            st.synchronize()
+            # the tables: hipErrorStreamCaptureUnsupported
+            assert_refusal(refused_in_capture(st, lambda: s.transform_batch(x_t, out_f, pa.FORWARD)), "(900)")
             pa.set_variant(SEL_FUSED)
             s.transform_batch(x_t[:8].contiguous(), None, pa.FORWARD)      # the tables exist; the scratch image of this stream does not
             pa.set_variant(0)
             st.synchronize()
-            g1 = torch.cuda.CUDAGraph()
-            msg = ""
-            with torch.cuda.graph(g1, stream=st):
-                pa.set_variant(SEL_COMPOSED)
-                try:
-                    s.transform_batch(x_t, out_c, pa.FORWARD)
-                except RuntimeError as ex:
-                    msg = str(ex)
-                finally:
-                    pa.set_variant(0)
-            assert "graph capture" in msg and "(900)" in msg, msg
-            del g1
-            st.synchronize()
-            assert bool((out_c == SENTINEL).all()) and bool((out_f == SENTINEL).all()), "a refused call launched something"
+            assert_refusal(refused_in_capture(st, grows, (out_c, out_f)), "(900)")
 
             def calls():
                 pa.set_variant(SEL_FUSED)

@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from abi_kit import L  # noqa: F401
 import accuracy_model as am
 import mdct_model as mm
 import pffft_amd as pa
@@ -14,13 +15,6 @@ import pffft_amd as pa
 MODEL_SIZES = (32, 96, 512, 1024, 2048, 4096, 40960)
 REFUSED = (0, -32, 16, 48, 33, 2 * 7 * 16)
 DTYPES = [np.float32, np.float64]
-
-
-@pytest.fixture(scope="module")
-def L():
-    from pffft_amd import build
-    build.build()
-    return pa.lib()
 
 
 def white(shape, dtype, seed):

@@ -6,20 +6,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from abi_kit import INVALID_HANDLE, INVALID_VALUE, L, prefix, refused  # noqa: F401
 import pffft_amd as pa
 
-INVALID_VALUE, INVALID_HANDLE = 1, 400      # hipErrorInvalidValue, hipErrorInvalidHandle
 P = 0x1000                                  # a non-NULL "device pointer", 16-byte aligned: validation answers before anything reads it
 M, NFRAMES = 1024, 4
 HANDLE = "pffft_hip: bad mdct setup handle"
 PRE = "pffft_hip: mdct: "
-
-
-@pytest.fixture(scope="module")
-def L():
-    from pffft_amd import build
-    build.build()
-    return pa.lib()
 
 
 def dct4(L, pfx, h, src=P, dst=P, rows=1):
@@ -34,17 +27,13 @@ def ola(L, pfx, h, signal=P, signal_stride=0, nsignals=1, nframes=NFRAMES, windo
     return getattr(L, f"{pfx}_hip_mdct_overlap_add_batch")(h, coefs, coefs_stride, nsignals, nframes, window, 1.0, signal, signal_stride, None)
 
 
-def refused(rc, code, text):
-    assert rc == code and pa.last_error() == text, (rc, pa.last_error(), text)
-
-
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 def test_refusals(L, dtype):
     s = pa.MdctSetup(M, dtype=dtype)
     other = pa.MdctSetup(M, dtype=np.float64 if dtype == np.float32 else np.float32)
     plain = pa.Setup(M // 2, pa.COMPLEX, dtype)                 # a transform setup is no mdct handle
     junk = C.create_string_buffer(4096)
-    pfx = "pffftd" if dtype == np.float64 else "pffft"
+    pfx = prefix(dtype)
     h = s.handle
     size = np.dtype(dtype).itemsize
 

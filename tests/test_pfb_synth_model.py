@@ -5,6 +5,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from abi_kit import L, prefix  # noqa: F401
 import frames_model as fm
 import pfb_model as pm
 import pfb_synth_model as sm
@@ -144,11 +145,6 @@ def test_float32_synthesis_against_float64_synthesis(case, proto):
 
 
 # ------------------------------------------------------------------ validation rules, no device
-@pytest.fixture(scope="module")
-def L():
-    return pa.lib()
-
-
 PTR = 0x1000   # a non-NULL "device pointer": validation must answer before anything dereferences or launches
 
 
@@ -163,7 +159,7 @@ def _syn(L, pfx, h, spectra_stride=0, nsignals=1, nframes=4, hop=256, taps=4, si
 def test_validation_before_any_device(L, dtype, transform):
     s = pa.Setup(1024, transform, dtype)
     other = pa.Setup(1024, transform, np.float64 if dtype == np.float32 else np.float32)
-    pfx = "pffftd" if dtype == np.float64 else "pffft"
+    pfx = prefix(dtype)
     N, spp = 1024, (2 if transform == pa.COMPLEX else 1)
     row = N * spp
     need = (3 * 256 + 4 * N) * spp                 # scalars of one signal of 4 frames at hop 256 with 4 taps

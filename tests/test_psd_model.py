@@ -8,6 +8,7 @@ import re
 import numpy as np
 import pytest
 
+from abi_kit import L, prefix  # noqa: F401
 import accuracy_model as am
 import frames_model as fm
 import psd_model as pm
@@ -73,11 +74,6 @@ def test_run_structure_is_visible_in_the_bits():
 
 
 # ------------------------------------------------------------------ validation rules, no device
-@pytest.fixture(scope="module")
-def L():
-    return pa.lib()
-
-
 PTR = 0x1000   # a non-NULL "device pointer": validation must answer before anything dereferences or launches
 
 
@@ -90,7 +86,7 @@ def _psd(L, pfx, h, signal_stride=0, nsignals=1, nframes=4, hop=256, navg=0, out
 def test_validation_before_any_device(L, dtype, transform):
     s = pa.Setup(1024, transform, dtype)
     other = pa.Setup(1024, transform, np.float64 if dtype == np.float32 else np.float32)
-    pfx = "pffftd" if dtype == np.float64 else "pffft"
+    pfx = prefix(dtype)
     N, spp = 1024, (2 if transform == pa.COMPLEX else 1)
     P = N // 2 + 1 if transform == pa.REAL else N
     need = (3 * 256 + N) * spp                     # scalars of one signal of 4 frames at hop 256

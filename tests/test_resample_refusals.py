@@ -6,10 +6,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from abi_kit import INVALID_HANDLE, INVALID_VALUE, L, prefix, refused  # noqa: F401
 import pffft_amd as pa
 import resample_model as rm
 
-INVALID_VALUE, INVALID_HANDLE = 1, 400      # hipErrorInvalidValue, hipErrorInvalidHandle
 P = 0x100000                                # a non-NULL "device pointer", 16-byte aligned: validation answers before anything reads it
 O = 0x400000
 N, M = 1024, 2048
@@ -19,19 +19,8 @@ ALIGN = PRE + "in / out not aligned to one element"
 OVERLAP = PRE + "out overlaps in (there is no in-place form)"
 
 
-@pytest.fixture(scope="module")
-def L():
-    from pffft_amd import build
-    build.build()
-    return pa.lib()
-
-
 def call(L, pfx, h, x=P, out=O, batch=1):
     return getattr(L, f"{pfx}_hip_resample_batch")(h, x, out, batch, 1.0, None)
-
-
-def refused(rc, code, text):
-    assert rc == code and pa.last_error() == text, (rc, pa.last_error(), text)
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
@@ -63,7 +52,7 @@ def test_refusals(L, dtype, real):
     plain = pa.Setup(N, pa.COMPLEX, dtype)                      # a transform setup is no resample handle
     xc = pa.XcorrSetup(N, dtype=dtype)                          # nor is another derived handle
     junk = C.create_string_buffer(4096)
-    pfx = "pffftd" if dtype == np.float64 else "pffft"
+    pfx = prefix(dtype)
     h = s.handle
     el = np.dtype(dtype).itemsize * (1 if real else 2)
 

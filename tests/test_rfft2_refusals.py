@@ -6,10 +6,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from abi_kit import INVALID_HANDLE, INVALID_VALUE, L, prefix, refused  # noqa: F401
 import pffft_amd as pa
 import rfft2_model as r2
 
-INVALID_VALUE, INVALID_HANDLE = 1, 400      # hipErrorInvalidValue, hipErrorInvalidHandle
 P = 0x100000                                # a non-NULL "device pointer", 16-byte aligned: validation answers before anything reads it
 O = 0x4000000
 HANDLE = "pffft_hip: bad rfft2 setup handle"
@@ -19,19 +19,8 @@ OVERLAP = PRE + "out overlaps in (the two sides differ in size: there is no in-p
 FWD, BWD = 0, 1
 
 
-@pytest.fixture(scope="module")
-def L():
-    from pffft_amd import build
-    build.build()
-    return pa.lib()
-
-
 def call(L, pfx, h, x=P, out=O, batch=1, d=FWD):
     return getattr(L, f"{pfx}_hip_rfft2_transform_batch")(h, x, out, batch, d, 1.0, None)
-
-
-def refused(rc, code, text):
-    assert rc == code and pa.last_error() == text, (rc, pa.last_error(), text)
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
@@ -66,7 +55,7 @@ def test_refusals(L, dtype):
     plain = pa.Setup(64, pa.COMPLEX, dtype)                     # a transform setup is no rfft2 handle
     f2 = pa.Fft2Setup(rows, cols, dtype=dtype)                  # nor is the complex 2-D handle
     junk = C.create_string_buffer(4096)
-    pfx = "pffftd" if dtype == np.float64 else "pffft"
+    pfx = prefix(dtype)
     h = s.handle
 
     for bad in (None, other.handle, plain.handle, f2.handle, C.addressof(junk)):

@@ -12,11 +12,11 @@ import pytest
 import accuracy_model as am
 import rfft2_model as r2
 import rfft2conv_model as rc
+from gpu_kit import shape_id
 
 ROOT = os.path.join(os.path.dirname(__file__), "..")
 SHAPES = list(rc.FUSED_SHAPES) + [(48, 80), (16, 1024), (96, 256)]
 BATCH = 37
-shape_id = lambda s: f"{s[0]}x{s[1]}"  # noqa: E731
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=lambda d: np.dtype(d).name)

@@ -9,10 +9,10 @@ import re
 import numpy as np
 import pytest
 
+from abi_kit import INVALID_HANDLE, INVALID_VALUE, L, prefix, refused  # noqa: F401
 import pffft_amd as pa
 import xcorr_model as xm
 
-INVALID_VALUE, INVALID_HANDLE = 1, 400      # hipErrorInvalidValue, hipErrorInvalidHandle
 P = 0x100000                                # a non-NULL "device pointer", 16-byte aligned: validation answers before anything reads it
 Q = 0x200000
 O = 0x400000
@@ -23,19 +23,8 @@ ALIGN = PRE + "x / y / out not aligned to one element"
 PLAIN, PHAT = 0, 1
 
 
-@pytest.fixture(scope="module")
-def L():
-    from pffft_amd import build
-    build.build()
-    return pa.lib()
-
-
 def call(L, pfx, h, x=P, y=Q, out=O, batch=1, w=PLAIN):
     return getattr(L, f"{pfx}_hip_xcorr_batch")(h, x, y, out, batch, w, 1.0, None)
-
-
-def refused(rc, code, text):
-    assert rc == code and pa.last_error() == text, (rc, pa.last_error(), text)
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
@@ -74,7 +63,7 @@ def test_refusals(L, dtype, real):
     plain = pa.Setup(N, pa.COMPLEX, dtype)                      # a transform setup is no xcorr handle
     an = pa.AnalyticSetup(N, dtype=dtype)                       # nor is another derived handle
     junk = C.create_string_buffer(4096)
-    pfx = "pffftd" if dtype == np.float64 else "pffft"
+    pfx = prefix(dtype)
     h = s.handle
     el = np.dtype(dtype).itemsize * (1 if real else 2)
 

@@ -7,6 +7,7 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
+from abi_kit import L, prefix  # noqa: F401
 import accuracy_model as am
 import zoom_model as zm
 import pffft_amd as pa
@@ -21,13 +22,6 @@ def band(N, K, i):
     (-1/2, 1/2).  On the 2^-60 grid (zoom_model.on_grid) except for the small shapes, whose truth can afford the integer reduction."""
     f0, df = [(0.0, 1.0 / N), (0.1, 0.25 / (N * max(K, 2))), (-0.2, -0.37 / N), (-123.456, 1.0 / (3 * N))][i % 4]
     return (f0, df) if N * K <= 2000 else (zm.on_grid(f0), zm.on_grid(df))
-
-
-@pytest.fixture(scope="module")
-def L():
-    from pffft_amd import build
-    build.build()
-    return pa.lib()
 
 
 # ------------------------------------------------------------------ the model computes the zoom transform
@@ -89,7 +83,7 @@ def test_both_reductions_of_the_truth_agree():
 
 # ------------------------------------------------------------------ host-only entries
 def _new(L, N, K, f0, df, dtype):
-    pfx = "pffftd" if np.dtype(dtype) == np.float64 else "pffft"
+    pfx = prefix(dtype)
     return getattr(L, f"{pfx}_hip_zoom_new_setup")(N, K, f0, df), getattr(L, f"{pfx}_hip_zoom_destroy_setup")
 
 
