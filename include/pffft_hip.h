@@ -1107,6 +1107,15 @@ int pffastconv_hip_apply_device(PFFASTCONV_Setup *, const float *d_input, int in
  * launch so that reference-sized calls (BASELINE configs[3]: 255 blocks) fill the chip.  -1 on error. */
 int pffastconv_hip_apply_batch(PFFASTCONV_Setup *, const float *d_input, int inputLen, size_t inputStride,
                                float *d_output, size_t outputStride, int nsignals, int applyFlush, void *stream);
+/* Host arithmetic only.  pffastconv_hip_route: the route a pffastconv_hip_apply_batch call of `nsignals` signals of `inputLen` samples
+ * takes under the calling thread's selector (pffft_hip_set_variant) and the process environment, written into buf as
+ * "<kernel short name> <cfg> <block> <step> <blocks> <last>": the kernel that takes the call's blocks, its configuration (the stride of
+ * fastconv_td_kernel, "big" / "ref" = which filter table a 16384-sample kernel reads, "W4" / "W8" wavefronts of fastconv_split1_kernel,
+ * the FirCfg of fastconv_fused_kernel, "" where a kernel has one form), the internal block length, its valid samples, the blocks per
+ * signal and the outputs of the last one (the time-domain kernel: tiles of the float stream); "" for a call that launches nothing.
+ * `cus` > 0 is taken as the device's number of compute units and no device is touched; `cus` <= 0 asks the current device.  Returns the
+ * length of the text, -1 for an invalid handle or a buffer too small for the text and its terminating 0. */
+int pffastconv_hip_route(const PFFASTCONV_Setup *, int inputLen, int nsignals, int applyFlush, int cus, char *buf, size_t len);
 
 /* Name of the kernel family a setup dispatches to ("c1024_f32", "tiled", "tiny", "stockham", "stockham_rt" = the same kernel on a
  * run-time plan because the size has no generated compile-time plan (no legal size today), "fourstep" = tile / streaming

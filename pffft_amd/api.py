@@ -165,6 +165,8 @@ def lib():
     L.pffastconv_hip_apply_batch.restype = C.c_int
     L.pffastconv_hip_apply_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int,
                                              C.c_int, C.c_void_p]
+    L.pffastconv_hip_route.restype = C.c_int
+    L.pffastconv_hip_route.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
     L.pffft_hip_error_count.restype = C.c_uint
     L.pffastconv_simd_size.restype = C.c_int
     L.pffft_hip_shift_transform_batch.restype = C.c_int
@@ -1326,6 +1328,17 @@ class FastConv(_Handle):
         bl = C.c_int(block_len)
         self._open("pffastconv", h.ctypes.data, h.size, C.byref(bl), flags, shown="pffastconv_new_setup")
         self.block_len, self.flags = bl.value, flags
+
+    def route(self, L, nsig=1, flush=True, cus=0):
+        """pffastconv_hip_route: (kernel, cfg, block, step, blocks, last) of an apply_batch call of nsig signals of L samples under the calling
+        thread's selector - the kernel's short name (None: the call launches nothing), its configuration, the internal block length, its
+        valid samples, the blocks per signal and the last block's outputs.  Host arithmetic only; cus > 0 stands for the device's compute
+        units, so that no device is touched."""
+        buf = C.create_string_buffer(128)
+        if self._L.pffastconv_hip_route(self.handle, int(L), int(nsig), int(bool(flush)), int(cus), buf, len(buf)) < 0:
+            raise RuntimeError("pffastconv_hip_route failed")
+        f = buf.value.decode().split(" ")
+        return (f[0], f[1]) + tuple(int(v) for v in f[2:]) if f[0] else (None, "", 0, 0, 0, 0)
 
     def apply(self, x, flush: bool = True, out=None):
         """Returns (y[:n_out], n_out) like pffastconv_apply (src/pffastconv.c:133-263)."""

@@ -242,14 +242,15 @@ bool is_device_ptr(const void* p);
 bool zero_copy_enabled();
 
 struct FcBatch { int nsig; size_t xstride, ystride; };   // signals of one pffastconv call (1 for the reference entries)
+// one pffastconv call on the blocks of its route (fastconv_tu.hip fir_route): what every FIR block launcher takes
+struct FirCall { const float* x; float* y; int nblk, step, inputLen, lastOut; hipStream_t st; FcBatch fb; };
 
-// dma_tu.hip: the LDS-DMA staged FIR block kernel (fft_dma.h); -1 when the block length has no such kernel
-int launch_fir_dma(Setup* ps, const float* d_Hc, const float* d_x, float* d_y, int nblk, int step, int inputLen, int lastOut,
-                   hipStream_t st, const FcBatch& fb);
-
-// dma_tu.hip: 16384-sample FIR blocks on 256 threads with 32 points per thread (fft_fir32.h); -1: not this block length
-int launch_fir32(Setup* ps, const float* d_Hc, const float* d_x, float* d_y, int nblk, int step, int inputLen, int lastOut,
-                 hipStream_t st, const FcBatch& fb, DevBuf& hp_cache, int pref);
+// dma_tu.hip, on a real setup of Nfft = 2 ps->n and its canonical filter spectrum x 1 / Nfft; a block length the kernel does not have is the
+// caller's error (refused with a text), never a fall-through.  hp_cache / ab_cache: the kernel's own table, built on first use into the caller's setup
+int launch_fir_dma(Setup* ps, const float* d_Hc, const FirCall& c);                              // the lock-step LDS-DMA staged block kernel (fft_dma.h)
+int launch_fir_split(Setup* ps, const float* d_Hc, const FirCall& c, bool plain);                // 16384-sample blocks on the split kernel (fft_split.h)
+int launch_fir32(Setup* ps, const float* d_Hc, const FirCall& c, DevBuf& hp_cache, int pref);    // ... on 256 threads with 32 points per thread (fft_fir32.h)
+int launch_fir_split1(Setup* ps, const float* d_Hc, const FirCall& c, DevBuf& ab_cache);         // few blocks of 8192 / 4096 samples (fft_split.h fastconv_split1_kernel)
 
 // tile_real_tu.hip: REAL transforms beyond LDS in two sweeps (fft_tile.h RMODE): N real points -> canonical half spectrum through a
 // work buffer of tile_rfft_work_elems(N) complex elements per vector; -1: no plan for this length / direction
@@ -265,11 +266,6 @@ const void* one_kernel_ptr(bool is_double, int flags);
 
 // conv_tu.hip: forward -> x H (one filter spectrum, internal layout) -> backward in ONE kernel (fft_conv.h); -1: no fused kernel
 int launch_conv_fused(Setup* s, const void* in, const void* H, void* out, size_t batch, double scaling, int accumulate, hipStream_t st);
-
-// dma_tu.hip: few-block calls on reference-sized blocks (fft_split.h fastconv_split1_kernel); -1: no such kernel for this length
-// (ab_cache: the filter's folded coefficient table, built on first use into the caller's pffastconv setup)
-int launch_fir_split1(Setup* ps, const float* d_Hc, const float* d_x, float* d_y, int nblk, int step, int inputLen, int lastOut,
-                      hipStream_t st, const FcBatch& fb, DevBuf& ab_cache);
 
 // tile_tu.hip: power-of-two sizes beyond LDS in two / three passes (fft_tile.h); canonical complex, in -> out through `work`
 // (same size, distinct from both; in may equal out).  -1 when the size has no tile plan.  layout 3 (round 6, forward only, the complex core

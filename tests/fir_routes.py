@@ -1,10 +1,13 @@
-"""The FIR dispatcher (pffft_amd/csrc/fastconv_tu.hip fc_apply_device / fc_big_nfft, selector 0, default environment) on plain integers, and
+"""The FIR route decision (pffft_amd/csrc/fastconv_tu.hip fir_route / fc_big_nfft, selector 0, default environment) on plain integers, and
 the smallest shapes that decide each of its branches (tests/test_fir_routes.py pins the arithmetic, tests/test_gpu_fir_routes.py walks the
 shapes on the device and asserts from the trace that the predicted kernel ran).
 
 The block schedule a caller observes - how many samples a call produces - is NOT restated here: schedule() takes it from
-oracle/pffft_oracle.py fastconv_geometry / fastconv_blocks, the loop fastconv_apply itself runs.  route() restates the ORDER of the
-dispatcher's branches and its constants, each named next to the line it restates.  Pure integer arithmetic: no device, no library."""
+oracle/pffft_oracle.py fastconv_geometry / fastconv_blocks, the loop fastconv_apply itself runs.  route() is the independent derivation of
+the ORDER of fir_route's branches and of its constants, each named next to the line it derives.  It is held against the library's own
+statement, pffastconv_hip_route (FastConv.route: fir_route itself, no device), field for field: in tests/test_fir_routes.py at the
+hand-computed points, at every edge shape of 256 and 304 CUs and on a seeded grid, and in tests/test_gpu_fir_routes.py at the device's CU
+count beside the kernel trace.  Pure integer arithmetic: no device, no library."""
 from __future__ import annotations
 
 from collections import namedtuple
@@ -22,12 +25,12 @@ BLOCK_KERNELS = KERNELS + ("fastconv_split_kernel", "fastconv_dma_kernel", "fast
 WAVE_MIN_TAPS = 32        # g_fir_wave_min
 WAVE_MAX_TAPS = 850       # g_fir_wave_max
 PART_B = 1024             # PART_B: the wave kernel's blocks are 2 PART_B samples
-WAVE_BLOCKS_PER_CU = 8    # fc_apply_device: `>= 8L * num_cus()` wave blocks
-BIG_MIN_TAPS = 129        # fc_big_nfft: `if (taps <= 128) return 0`
-BIG_SHORT, BIG_LONG = 8192, 16384      # fc_big_nfft: `taps <= g_fir_wave_max ? 8192 : 16384`
-TD_MAX_TAPS = 512         # TD_MAX_TAPS
+WAVE_BLOCKS_PER_CU = 8    # fir_route: `>= FIR_WAVE_BLOCKS_PER_CU * cus` wave blocks
+BIG_MIN_TAPS = 129        # fc_big_nfft: `if (taps <= FIR_BIG_FLOOR_TAPS) return 0` (128)
+BIG_SHORT, BIG_LONG = 8192, 16384      # fc_big_nfft: `taps <= wave_max ? 8192 : 16384`
+TD_MAX_TAPS = 512         # TD_MAX_TAPS (fft_firtd.h)
 TD_TILE = 2048            # TD_TILE = TD_THREADS x TD_PER outputs of one workgroup
-REF_BLOCKS_PER_CU = 2     # fc_apply_device: `Nfft == 16384 && nblk * nsig >= 2L * num_cus()`
+REF_BLOCKS_PER_CU = 2     # fir_route: `Nfft == 16384 && nbt * nsig >= FIR_REF_BLOCKS_PER_CU * cus`
 FUSED_CFG = {512: "C512", 1024: "C1024", 2048: "C2048m", 4096: "C4096m", 8192: "C8192"}      # the switch on Nfft / 2, reference-sized blocks
 BIG_CFG = {1024: "C1024", 2048: "C2048", 4096: "C4096", 8192: "C8192"}                        # the switch on nbig / 2
 
@@ -58,16 +61,16 @@ def _blocks(produced: int, step: int):
 
 def route(taps: int, L: int, nsig: int, flags: int, flush, cus: int, block_len: int = 0) -> Route:
     """The kernel one pffastconv_hip_apply_batch call of nsig signals ends in on a device of `cus` compute units, in the order of
-    fc_apply_device's branches."""
+    fir_route's branches."""
     nfft, _, flen, cf = po.fastconv_geometry(taps, block_len, flags)
     s = schedule(taps, L, flags, flush, block_len)
-    if s.nblk == 0:                                                  # `if (nbt == 0) return 0`
+    if s.nblk == 0:                                                  # `if (nbt == 0) return r`
         return Route(None, "", 0, 0, 0, 0)
     mode = 1 if (flags & CPLX) and cf == 1 else 0                    # two real streams per signal
     produced = s.produced * cf                                       # fc_schedule's *produced: floats of the real stream
     nblk = 2 * s.nblk if mode else s.nblk
     if mode == 0 and cf == 1 and WAVE_MIN_TAPS <= flen <= min(PART_B, WAVE_MAX_TAPS) and produced > 0:
-        wstep = (2 * PART_B - flen + 1) & ~3                         # `wstep = (2 * PART_B - filterLen + 1) & ~3`
+        wstep = (2 * PART_B - flen + 1) & ~3                         # `wstep = (2 * PART_B - flen + 1) & ~3`
         wblk, wlast = _blocks(produced, wstep)
         if wblk * nsig >= WAVE_BLOCKS_PER_CU * cus:
             return Route(WAVE, "", 2 * PART_B, wstep, wblk, wlast)   # (part_P == 1: flen <= PART_B)
@@ -77,7 +80,7 @@ def route(taps: int, L: int, nsig: int, flags: int, flush, cus: int, block_len: 
         nbig = 0
         if not (want <= nfft or want < 2 * flen) and flen >= BIG_MIN_TAPS:
             bblk = (produced + (want - flen)) // (want - flen + 1)
-            if bblk * nsig >= cus:                                   # `bblk * nsig >= num_cus() ? want : 0`
+            if bblk * nsig >= cus:                                   # `bblk * nsig >= cus ? want : 0`
                 nbig = want
         if nbig:
             bstep = nbig - flen + 1

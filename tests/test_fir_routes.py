@@ -1,6 +1,6 @@
 """tests/fir_routes.py without a device: route() at hand-computed points on both sides of every threshold, schedule() against the count
 oracle/pffft_oracle.py fastconv_apply returns and against the library's own (pffastconv_hip_apply_batch with no signals touches no device),
-and the properties of edge_shapes(256) that tests/test_gpu_fir_routes.py relies on."""
+route() against the library's own route (pffastconv_hip_route with the CU count given touches no device either), and the properties of edge_shapes(256) that tests/test_gpu_fir_routes.py relies on."""
 import numpy as np
 import pytest
 
@@ -163,6 +163,110 @@ def test_schedule_is_the_librarys_count_without_a_device(pa, flags):
                 n += 1
         fc.close()
     assert n > 1000
+
+
+# ------------------------------------------------------------------ the model against the library's own route (fir_route, no device)
+ROUTE_GRID_SEED = 20261021
+ROUTE_FLAGS = (0, CPLX, CPLX | SINGLE_FFT, CORRELATION, CPLX | CORRELATION)
+# taps at which a branch of fir_route / fc_big_nfft / the reference's block length changes
+ROUTE_TAP_EDGES = (1, 8, 17, 32, 128, 257, 512, 850, 1024, 2048, 4096, 4097, 8192, 9000)
+
+
+def route_grid(n_setups=300, per_setup=8):
+    """[(taps, flags, [(L, nsig, flush, cus)])]: seeded.  Taps 1 ... 9000, half of them within 2 of an edge; L up to 40000, half of them one
+    to three blocks of a block length the routes use plus a ragged tail; nsig up to 3000, half of them within 1 of a block-count threshold
+    (1, 2, 8 blocks per CU at one to six blocks per signal)."""
+    rng = np.random.default_rng(ROUTE_GRID_SEED)
+    grid = []
+    for i in range(n_setups):
+        taps = int(rng.integers(1, 9001)) if i % 2 else int(min(9000, max(1, rng.choice(ROUTE_TAP_EDGES) + rng.integers(-2, 3))))
+        points = []
+        for j in range(per_setup):
+            cus = (64, 256, 304)[int(rng.integers(0, 3))]
+            L = int(rng.integers(0, 40001)) if j % 2 else int(min(40000, taps - 1 + rng.integers(1, 4) * int(rng.choice((2048, 4096, 8192, 16384))) * rng.random()))
+            nsig = int(rng.integers(1, 3001)) if j % 4 < 2 else int(min(3000, max(1, -(-int(rng.choice((1, 2, 8))) * cus // int(rng.integers(1, 7))) + rng.integers(-1, 2))))
+            points.append((L, nsig, int(rng.integers(0, 2)), cus))
+        grid.append((taps, ROUTE_FLAGS[i % len(ROUTE_FLAGS)], points))
+    return grid
+
+
+def test_route_is_the_librarys_route_without_a_device(pa):
+    """fr.route, the independent derivation, equals pffastconv_hip_route (FastConv.route with the CU count given: fir_route itself, no
+    device), field for field: at every hand-computed point, at every edge shape of 256 and of 304 CUs, and on the seeded grid."""
+    setups = {}
+
+    def lib_route(taps, L, nsig, flags, flush, cus):
+        if (taps, flags) not in setups:
+            setups[(taps, flags)] = pa.FastConv(np.ones(taps, np.float32), 0, flags)
+        return setups[(taps, flags)].route(L, nsig, flush, cus)
+
+    points = [p for p, _ in ROUTE_POINTS]
+    points += [(c.taps, c.L, c.nsig, c.flags, c.flush, cus) for cus in (256, 304) for c in fr.edge_shapes(cus)]
+    n_named = len(points)
+    points += [(taps, L, nsig, flags, flush, cus) for taps, flags, pts in route_grid() for L, nsig, flush, cus in pts]
+    assert len(points) - n_named >= 2000
+    kernels = set()
+    for p in points:
+        want = tuple(fr.route(*p))
+        assert lib_route(*p) == want, (p, "the library says", lib_route(*p), "the model", want)
+        kernels.add(want[:2])
+    for fc in setups.values():
+        fc.close()
+    # the grid alone is no proof of reach, the named points are: every kernel and configuration of the default dispatcher was compared
+    assert kernels == {(None, ""), (WAVE, ""), (GATHER, ""), (TD, "1"), (TD, "2"), (FIR32, "big"), (FIR32, "ref"), (SPLIT1, "W4"), (SPLIT1, "W8"),
+                       (FUSED, "C512"), (FUSED, "C1024"), (FUSED, "C4096"), (FUSED, "C8192")}
+
+
+# (taps, L, nsig, cus) -> route under the selector, worked out by hand as ROUTE_POINTS are; flush = 1.  The shapes are those of
+# tests/test_gpu_round6.py (AB_FIR_SPLIT = 119: the split kernel wherever the default runs fastconv_fused32_kernel) and
+# tests/test_gpu_round4.py (AB_FIR_FEW_LOCKSTEP = 115: the lock-step fused kernel wherever the default runs fastconv_split1_kernel).
+SPLIT16K = "fastconv_split_kernel"
+SELECTOR_POINTS = [
+    (119, (4096, (1 << 22) + 12345, 1, 256), (SPLIT16K, "big", 16384, 12289, 342, 12005), FIR32),
+    (119, (4096, 1 << 17, 40, 256), (SPLIT16K, "big", 16384, 12289, 11, 4087), FIR32),
+    (119, (2048, 1 << 22, 1, 256), (SPLIT16K, "big", 16384, 14337, 293, 5853), FIR32),
+    (119, (1500, 1500000, 3, 256), (SPLIT16K, "big", 16384, 14885, 101, 10001), FIR32),
+    (119, (851, 4000001, 1, 256), (SPLIT16K, "big", 16384, 15534, 258, 6913), FIR32),
+    (119, (6000, 3000000, 2, 256), (SPLIT16K, "ref", 16384, 10385, 289, 3121), FIR32),       # reference blocks of 16384: 578 >= 2 x 256
+    (119, (8192, 1 << 22, 1, 256), (FUSED, "C8192", 16384, 8193, 511, 7683), FUSED),         # 511 blocks < 2 x 256: no selector applies
+    (119, (4096, 20000, 300, 256), (SPLIT16K, "big", 16384, 12289, 2, 3616), FIR32),
+    (115, (4096, 1 << 20, 1, 256), (FUSED, "C4096m", 8192, 4097, 255, 3843), SPLIT1),          # the stated C4 call
+    (115, (2048, 1 << 19, 1, 256), (FUSED, "C2048m", 4096, 2049, 255, 1795), SPLIT1),
+    (115, (1500, 300001, 1, 256), (FUSED, "C2048m", 4096, 2597, 115, 2444), SPLIT1),
+    (115, (3000, 700003, 1, 256), (FUSED, "C4096m", 8192, 5193, 135, 1142), SPLIT1),
+    (115, (2049, 8192 * 3 + 5, 1, 256), (FUSED, "C2048m", 4096, 2048, 12, 5), SPLIT1),
+    (115, (1025, 40001, 1, 256), (FUSED, "C1024", 2048, 1024, 39, 65), FUSED),                 # 2048-sample blocks: no split1 kernel
+    (115, (4096, 5 * 4097 * 300 + 77, 1, 256), (FIR32, "big", 16384, 12289, 500, 9271), FIR32),  # 500 big blocks >= 256: the throughput regime
+]
+
+
+@pytest.mark.parametrize("variant,point,want,default", SELECTOR_POINTS, ids=[f"v{v}-{p[0]}taps-{p[1]}x{p[2]}" for v, p, _, _ in SELECTOR_POINTS])
+def test_route_under_the_second_route_selectors(pa, variant, point, want, default):
+    """The two selectors of the product build that name a second FIR route: the library's route under them at the shapes the GPU tests run,
+    and that selector 0 takes the kernel those tests compare against."""
+    taps, L, nsig, cus = point
+    fc = pa.FastConv(np.ones(taps, np.float32), 0, 0)
+    try:
+        assert fc.route(L, nsig, True, cus)[0] == default == fr.route(taps, L, nsig, 0, 1, cus).kernel
+        pa.set_variant(variant)
+        assert fc.route(L, nsig, True, cus) == want
+    finally:
+        pa.set_variant(0)
+        fc.close()
+
+
+def test_route_query_refusals(pa):
+    """-1 for a handle that is none and for a buffer that cannot hold the text; "" (length 0) for a call that launches nothing."""
+    import ctypes as C
+    lib = pa.lib()
+    fc = pa.FastConv(np.ones(100, np.float32), 0, 0)
+    buf = C.create_string_buffer(64)
+    assert lib.pffastconv_hip_route(None, 2046, 2048, 1, 256, buf, 64) == -1
+    assert lib.pffastconv_hip_route(fc.handle, 2046, 2048, 1, 256, buf, 64) == len("fastconv_wave_kernel  2048 1948 1 1947")
+    assert buf.value == b"fastconv_wave_kernel  2048 1948 1 1947"
+    assert lib.pffastconv_hip_route(fc.handle, 2046, 2048, 1, 256, buf, len(buf.value)) == -1          # no room for the terminating 0
+    assert lib.pffastconv_hip_route(fc.handle, 99, 2048, 1, 256, buf, 1) == 0 and buf.value == b""
+    fc.close()
 
 
 # ------------------------------------------------------------------ edge_shapes

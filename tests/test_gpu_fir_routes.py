@@ -1,13 +1,14 @@
 """Every route of the FIR dispatcher at its smallest deciding shapes, at the truth bar (-m gpu).
 
-tests/fir_routes.py derives the shapes from the device's CU count: both sides of every threshold of fc_apply_device / fc_big_nfft (reached by
+tests/fir_routes.py derives the shapes from the device's CU count: both sides of every threshold of fir_route / fc_big_nfft (reached by
 the number of signals, at one and at two blocks per signal), every tail of the last block (1, 2, 3, 4, 5, step - 1, step outputs) on every
 block kernel and configuration, calls of less than one block, calls that produce nothing, the complex modes and correlation.  With many short
 signals every block is the first and the last of its signal, every hand-over of a persistent workgroup crosses a signal boundary, every block
 zero-fills and stores a ragged tail.  One item per named case:
 
   count     apply_batch returns schedule().produced; with one or two signals the reference library is asked too and must return the same
-  route     the trace shows the kernel (and the instantiation) route() names and no other block kernel
+  route     the trace shows the kernel (and the instantiation) route() names and no other block kernel; the library's own route query
+            (FastConv.route, the device's CU count) names the same kernel and cfg
   truth     the produced samples against the float64 convolution at FIR_* / FIR32_* of tests/test_gpu_accuracy.py, every signal where
             signals x produced x taps <= 2e9, else the first two, the last two and 16 seeded random ones; the worst signal counts
   sentinel  rows are strided (input pitch L cpl + 5, output pitch produced cpl + 3 floats: rows are 4-byte aligned only); the pad floats of
@@ -112,6 +113,7 @@ def test_fir_route(ref, name):
         return fc.apply_batch(xin[:, :fl], bool(c.flush), out=yout)[1]
 
     # ---- count and route
+    assert fc.route(c.L, c.nsig, c.flush)[:2] == (c.kernel, c.cfg), (name, "the library's route query on this device", fc.route(c.L, c.nsig, c.flush))
     if c.kernel is None:
         assert call(x, y) == n == 0, name
         torch.cuda.synchronize()
