@@ -120,6 +120,12 @@ int pffastconv_simd_size(void);
  * when they retire: at most 4096 launches of ONE setup may be in flight at the same time (summed over all
  * streams).  Launches on one stream serialise, so only > 4096 concurrently RUNNING launches could collide.
  * (iii) Scratch of the sizes beyond LDS is kept per stream: the same setup may run on several streams at once.
+ * (iv) STREAM CAPTURE.  A setup's device state is built at its first call on a device (hipMalloc, hipMemset, hipMemcpy): never while
+ * `stream` records into a HIP graph.  A call on a capturing stream whose setup holds no state on the calling thread's device yet returns
+ * hipErrorStreamCaptureUnsupported ("the tables of this setup would have to be built during graph capture") before anything is allocated
+ * or launched, and leaves the setup as it was (pffft_hip_setup_devices does not list that device): run the call once before capturing,
+ * per device.  The same holds for a PFFASTCONV_Setup, whose tables are per ROUTE (see pffastconv_hip_apply_batch), and once a graph has
+ * recorded a launch of one, that setup no longer follows its user to another device: the graph reads its tables where they are.
  *
  * All return 0 on success, otherwise a hipError_t value (pffft_hip_last_error() has the text).
  * `in`, `out`, `a`, `b`, `ab` are DEVICE pointers to `batch` contiguous vectors (N scalars for a
@@ -1104,7 +1110,15 @@ int pffastconv_hip_apply_device(PFFASTCONV_Setup *, const float *d_input, int in
  * floats, outputStride >= the floats one signal produces - both checked, -1 otherwise; any nsignals).
  * Every signal is processed exactly as one pffastconv_hip_apply_device call would (src/pffastconv.c:133-263 per signal,
  * same block schedule, same number of outputs — the return value, per signal); all blocks of all signals share one
- * launch so that reference-sized calls (BASELINE configs[3]: 255 blocks) fill the chip.  -1 on error. */
+ * launch so that reference-sized calls (BASELINE configs[3]: 255 blocks) fill the chip.  -1 on error.
+ * STREAM CAPTURE: the filter tables are built on first use PER ROUTE (pffastconv_hip_route: the reference-block spectrum at the first call
+ * of all, then the big-block spectrum, the partition spectra, the time-domain taps, the coefficient table of the fused32 / split1 kernel,
+ * the work image of the composed path per stream and size) with allocations and a synchronisation of the null stream.  A call on a
+ * capturing stream that lacks one of them returns -1, launches nothing, changes nothing, and pffft_hip_last_error() names "graph capture"
+ * and the missing table: run a call of the SAME shape (signals x length: the route depends on both) once before capturing - a warm-up on
+ * a short signal takes another route.  After a capture has recorded a launch of the setup, nothing it reads is freed before
+ * pffastconv_destroy_setup: a call from another device, and a call whose route needs big blocks of another length than the recorded
+ * one, are refused (-1, with a text) instead of rebuilding the tables; a work image that is outgrown later is kept beside the new one. */
 int pffastconv_hip_apply_batch(PFFASTCONV_Setup *, const float *d_input, int inputLen, size_t inputStride,
                                float *d_output, size_t outputStride, int nsignals, int applyFlush, void *stream);
 /* Host arithmetic only.  pffastconv_hip_route: the route a pffastconv_hip_apply_batch call of `nsignals` signals of `inputLen` samples

@@ -83,7 +83,7 @@ static int analytic_ensure(AnalyticSetup* z, hipStream_t st) {
 template <int WHAT>
 static int analytic_fused(AnalyticSetup* z, const float* in, float* out, size_t batch, hipStream_t st) {
     const size_t N = (size_t)z->N, rout = WHAT == AN_ANALYTIC ? 2 * N : N;
-    return bluestein_fused(z->inner, z->N, batch, [&](auto tag, size_t b0, size_t nb) {
+    return bluestein_fused(z->inner, z->N, batch, st, [&](auto tag, size_t b0, size_t nb) {
         typedef typename decltype(tag)::type C;
         const AnalyticIO<C, WHAT> io{in + b0 * N, out + b0 * rout};
         return bluestein_fused_launch<C>(z->inner, io, (const float*)z->d_H.as<float>(), nb, z->N, st);

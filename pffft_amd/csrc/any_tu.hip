@@ -123,7 +123,7 @@ static int any_ensure(AnySetup* a, hipStream_t st) {
 
 // ------------------------------------------------------------------------------------------------ the two routes (bluestein_host.h)
 static int any_fused(AnySetup* a, const float* in, float* out, size_t batch, int cj, hipStream_t st) {
-    return bluestein_fused(a->inner, a->M, batch, [&](auto tag, size_t b0, size_t nb) {
+    return bluestein_fused(a->inner, a->M, batch, st, [&](auto tag, size_t b0, size_t nb) {
         typedef typename decltype(tag)::type C;
         const AnyChirpIO<C, AnyHold<C>::value> io{in + b0 * 2 * (size_t)a->N, out + b0 * 2 * (size_t)a->N, a->d_chirp.as<cx<float>>(),
                                                   (unsigned)a->N, cj};
@@ -150,7 +150,7 @@ template <int DIRN>
 static int any_real_fused(AnySetup* a, const float* in, float* out, size_t batch, hipStream_t st) {
     const size_t rin = DIRN == FWD ? (size_t)a->N : 2 * (size_t)a->bins(), rout = DIRN == FWD ? 2 * (size_t)a->bins() : (size_t)a->N;
     const DevBuf& Hs = DIRN == FWD ? a->d_H : a->d_Hr;
-    return bluestein_fused(a->inner, a->M, batch, [&](auto tag, size_t b0, size_t nb) {
+    return bluestein_fused(a->inner, a->M, batch, st, [&](auto tag, size_t b0, size_t nb) {
         typedef typename decltype(tag)::type C;
         const AnyRealIO<C, AnyHold<C>::value, DIRN> io{in + b0 * rin, out + b0 * rout, a->d_chirp.as<cx<float>>(), (unsigned)a->N,
                                                        (unsigned)a->bins()};

@@ -19,6 +19,8 @@ int zreorder_batch(Setup* s, const T* in, T* out, size_t batch, int dir, hipStre
     if (!s || s->magic != MAGIC) return (int)hipErrorInvalidHandle;
     if (batch == 0) return 0;
     s = for_device(s);
+    // (every route, also the direct kernel that reads no table: one rule for the first call of a setup, in or outside a stream capture)
+    if (int rc = ensure_device<T>(s, st)) return rc;
     // through an LDS image of the internal layout when a vector fits (fft_aux.h); AB_AUX_DIRECT = the direct kernel
     constexpr int CH = 16 / (int)sizeof(T), BCH = SkIbs<T>::v / CH;
     const size_t vimg = ((size_t)(s->n / 16) * BCH + 1) * 16;   // block image of one vector, bytes
@@ -27,8 +29,6 @@ int zreorder_batch(Setup* s, const T* in, T* out, size_t batch, int dir, hipStre
     const AbSel sel = ab();
     const bool direct = sel.is(AB_AUX_DIRECT), inorder_small = sel.is(AB_INORDER_SMALL);
     if (vbytes <= ZRD_GROUP_BYTES && batch * vbytes >= ((size_t)64 << 20) && !direct && !sel.is(AB_AUX_NO_STREAM) && !inorder_small && in != out) {
-        int rc = ensure_device<T>(s);
-        if (rc) return rc;
         const int G = (int)(ZRD_GROUP_BYTES / vbytes);
         const bool to_canon = dir == PFFFT_FORWARD;
         const size_t img = to_canon ? (size_t)zrd_canon_img16<T>(s->n) * 16 : vimg;
@@ -48,8 +48,7 @@ int zreorder_batch(Setup* s, const T* in, T* out, size_t batch, int dir, hipStre
         }
     }
     if (vimg <= 128 * 1024 && !direct && in != out) {
-        int rc = ensure_device<T>(s);
-        if (rc) return rc;
+        int rc = 0;
         int G = (int)(16384 / vimg);
         if (G < 1) G = 1;
         const size_t lds = (size_t)G * vimg + 16;
@@ -91,6 +90,7 @@ int zconvolve_batch(Setup* s, const T* a, const T* b, T* ab, T scaling, size_t b
     if (!s || s->magic != MAGIC) return (int)hipErrorInvalidHandle;
     if (batch == 0) return 0;
     s = for_device(s);
+    if (int rc = ensure_device<T>(s, st)) return rc;   // (every route: see zreorder_batch)
     const AbSel sel = ::pf::ab();      // (`ab` is also this function's output vector)
     const bool direct = sel.is(AB_AUX_DIRECT), inorder_small = sel.is(AB_INORDER_SMALL);
     size_t total = batch * (size_t)(s->n / 4);
@@ -102,8 +102,6 @@ int zconvolve_batch(Setup* s, const T* a, const T* b, T* ab, T scaling, size_t b
         const unsigned long long Q = 2ull * total * Zd<T>::UPG;   // 16-byte units in the batch
         if (!direct && !sel.is(AB_AUX_NO_STREAM) && !inorder_small && Q / Zd<T>::CHUNK >= 8192u &&
             Q / Zd<T>::CHUNK < 0xffffffffull) {
-            int rc = ensure_device<T>(s);
-            if (rc) return rc;
             unsigned* ctr = take_counters(s, st);
             const int real = s->transform == PFFFT_REAL;
             const dim3 grid((unsigned)num_cus()), blk(ZD_WAVES * 64);
@@ -118,8 +116,6 @@ int zconvolve_batch(Setup* s, const T* a, const T* b, T* ab, T scaling, size_t b
         }
     }
     if (!direct && sizeof(T) == 4) {
-        int rc = ensure_device<T>(s);
-        if (rc) return rc;
         const size_t chunks = (total + ZC_CHUNK - 1) / ZC_CHUNK;
         size_t grid = (size_t)num_cus() * 4;
         if (grid > chunks) grid = chunks;
@@ -173,7 +169,7 @@ int convolve_batch(Setup* s, const T* in, const T* H, T* out, T scaling, size_t 
     if (int rc = check_setup<T>(s)) return rc;
     if (batch == 0) return 0;
     s = for_device(s);
-    int rc = ensure_device<T>(s);
+    int rc = ensure_device<T>(s, st);
     if (rc) return rc;
     if (h_broadcast && !ab().is(AB_CONV_COMPOSED)) {
         rc = launch_conv_fused(s, in, H, out, batch, (double)scaling, accumulate, st);

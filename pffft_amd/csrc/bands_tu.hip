@@ -200,7 +200,7 @@ static int bands_batch(void* setup, const T* signal, size_t signal_stride, size_
         // (the kernel counts frames in 32 bits: longer batches of ONE signal go out in slices; several signals that long are composed)
         if (bands_route_fused(z, hop, signal_stride, ab()) && aligned16(signal) && (!window || aligned16(window)) &&
             bands_fusable_setup(z->inner, &e, window != nullptr, what) && (a.batch <= ROW_SLICE || nsignals == 1)) {
-            if (int rc = inner_on_device(z->inner)) return rc;
+            if (int rc = inner_on_device(z->inner, st)) return rc;
             Setup* s = z->inner;
             const int oneshot = s->route[PFFFT_FORWARD][1].oneshot;
             return for_slices(a.batch, [&](size_t b0, size_t nb) {

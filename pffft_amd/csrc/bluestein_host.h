@@ -66,9 +66,9 @@ static int bluestein_fused_launch(Setup* s, const IO& io, const float* H, size_t
 // calling thread's device; the batch goes out in slices on the same stream (for_slices).  launch(CfgTag<C>(), first row, rows) forms the
 // policy object of that slice and calls bluestein_fused_launch<C>.
 template <class F>
-static int bluestein_fused(Setup* inner, int M, size_t batch, F&& launch) {
+static int bluestein_fused(Setup* inner, int M, size_t batch, hipStream_t st, F&& launch) {
     typedef ConvPick<float> P;
-    if (int rc = inner_on_device(inner)) return rc;
+    if (int rc = inner_on_device(inner, st)) return rc;
     return for_slices(batch, [&](size_t b0, size_t nb) {
         switch (M) {
             case 512: return launch(CfgTag<P::C512>(), b0, nb);

@@ -99,7 +99,7 @@ static int csd_batch(Setup* s, const T* x, size_t x_stride, const T* y, size_t y
     const int kwhat = csd_kernel_what(what, navg);         // what the run kernels store
     const size_t W = csd_part_row(what, P);                // scalars of one run's partial row
     s = for_device(s);
-    if ((rc = ensure_device_any(s))) return rc;
+    if ((rc = ensure_device_any(s, st))) return rc;
     CsdSel e;
     bool fused = false;
     if constexpr (sizeof(T) == 4)

@@ -92,7 +92,7 @@ static int dct2d_fused_launch(Dct2dSetup* z, const cx<float>* tabc, const cx<flo
 
 // The tables come from the two 1-D handles (built at their first use: not during a capture), W_64 and the counters from `inner`.
 static int dct2d_fused(Dct2dSetup* z, const float* in, float* out, size_t batch, hipStream_t st) {
-    if (int rc = inner_on_device(z->inner)) return rc;
+    if (int rc = inner_on_device(z->inner, st)) return rc;
     const cx<float>*tabc = nullptr, *tabr = nullptr;
     if (int rc = dct_device_table(z->along_cols, st, &tabc)) return rc;
     if (int rc = dct_device_table(z->along_rows, st, &tabr)) return rc;

@@ -142,7 +142,7 @@ static int dct_transform_batch(void* setup, const T* in, T* out, size_t batch, h
     const size_t len = batch * (size_t)z->N * sizeof(T);   // the same rows in place, or rows that do not overlap
     if (in != out && ranges_overlap((uintptr_t)in, len, (uintptr_t)out, len)) return bad("dct: in and out overlap without being equal");
     Setup* s = for_device(z->inner);   // the object that holds the inner setup's tables on the calling thread's device
-    int rc = ensure_device_any(s);
+    int rc = ensure_device_any(s, st);
     if (rc) return rc;
     const cx<T>* tab = nullptr;
     if ((rc = dct_table<T>(z, s, st, &tab))) return rc;
@@ -158,7 +158,7 @@ int dct_device_table(void* setup, hipStream_t st, const cx<float>** tab) {
     DctSetup* z = typed_handle<DctSetup, float>(setup);
     if (!z) return (int)hipErrorInvalidHandle;
     Setup* s = for_device(z->inner);
-    if (int rc = ensure_device_any(s)) return rc;
+    if (int rc = ensure_device_any(s, st)) return rc;
     return dct_table<float>(z, s, st, tab);
 }
 

@@ -26,8 +26,15 @@ static int fir_dma_cfg(Setup* ps, const float* d_Hc, const FirCall& c) {
     return 0;
 }
 
-// W_m^j (m = 1024, 512) for the wave-local sub-transforms of the split kernels: one table per device and length
-static int split_sub_table(const cx<float>** out, int m = 1024) {
+// what fc_refuse_capture (fastconv_tu.hip) says, for the tables the launchers here build on first use
+static int refuse_capture(const char* what) {
+    return bad((std::string("pffastconv: ") + what + " would have to be built during graph capture: run a call of this shape once before "
+                "capturing").c_str(), hipErrorStreamCaptureUnsupported);
+}
+
+// W_m^j (m = 1024, 512) for the wave-local sub-transforms of the split kernels: one table per device and length, uploaded at the first
+// call of the PROCESS that needs it (whatever setup it belongs to) - not while `st` records into a HIP graph
+static int split_sub_table(const cx<float>** out, hipStream_t st, int m = 1024) {
     static std::mutex mu;
     static std::map<long long, cx<float>*> tabs;
     int dev = 0;
@@ -36,6 +43,7 @@ static int split_sub_table(const cx<float>** out, int m = 1024) {
     const long long key = (long long)dev * 65536 + m;
     auto it = tabs.find(key);
     if (it == tabs.end()) {
+        if (stream_capturing(st)) return refuse_capture("the process-wide sub-transform table of the split kernels");
         const std::vector<cx<float>> tw = unit_roots<float>(m, m);
         cx<float>* d = nullptr;   // (cached for the life of the process, never freed: no owner with static storage, pf_devmem.h)
         PF_CHECK(hipMalloc((void**)&d, sizeof(cx<float>) * m));
@@ -49,10 +57,13 @@ static int split_sub_table(const cx<float>** out, int m = 1024) {
 // A per-filter coefficient table of a block kernel (`floats` floats out of the canonical spectrum d_Hc by `coef_kernel` on `wg` threads):
 // built ONCE and COMPLETE before the pointer is published - null stream + synchronisation, like every other lazily built table
 // (fc_spectrum, split_sub_table).  Built on the caller's stream (round 4) a second call on another non-blocking stream saw the pointer set
-// and could read a half-written table: the setup's mutex orders hosts, not streams.
+// and could read a half-written table: the setup's mutex orders hosts, not streams.  `st`, the call's stream, is only asked whether it
+// records into a HIP graph: a missing table is then refused, named by `what`.
 template <class K>
-static int fir_coef_table(DevBuf& cache, K coef_kernel, const char* name, int wg, size_t floats, Setup* ps, const float* d_Hc) {
+static int fir_coef_table(DevBuf& cache, K coef_kernel, const char* name, const char* what, int wg, size_t floats, Setup* ps, const float* d_Hc,
+                          hipStream_t st) {
     if (cache) return 0;
+    if (stream_capturing(st)) return refuse_capture(what);
     DevBuf t;
     if (int rc = t.grow(sizeof(float) * floats)) return rc;
     hipLaunchKernelGGL(coef_kernel, dim3(1), dim3(wg), 0, nullptr, (const cx<float>*)d_Hc, ps->d_twr.as<cx<float>>(), t.as<vec4<float>>());
@@ -68,10 +79,12 @@ static int fir_split1(Setup* ps, const float* d_Hc, const FirCall& c, DevBuf& ab
     typedef SplitOneT<W> S;
     ps = for_device(ps);
     auto k = fastconv_split1_kernel<W>;
-    int rc = fir_coef_table(ab_cache, fastconv_split1_coef_kernel<W>, "fastconv_split1_coef_kernel", S::WG, 4 * (size_t)S::n, ps, d_Hc);
-    if (rc) return rc;
     const cx<float>* tw512 = nullptr;
-    if ((rc = split_sub_table(&tw512, S::M))) return rc;
+    int rc = split_sub_table(&tw512, c.st, S::M);
+    if (rc) return rc;
+    if ((rc = fir_coef_table(ab_cache, fastconv_split1_coef_kernel<W>, "fastconv_split1_coef_kernel", "the split1 coefficient table of this setup",
+                             S::WG, 4 * (size_t)S::n, ps, d_Hc, c.st)))
+        return rc;
     size_t resident = 0;
     if ((rc = loop_resident(k, S::WG, S::LDS_BYTES, &resident))) return rc;
     const size_t grid = loop_grid(resident, (size_t)c.nblk * c.fb.nsig, 0).grid;   // (a static stride: no counters)
@@ -106,7 +119,7 @@ static int fir_split(Setup* ps, const float* d_Hc, const FirCall& c) {
     auto k = fastconv_split_kernel<PSYNC, SPREAD, W>;
     const cx<float>* tw1024 = nullptr;
     size_t resident = 0;
-    int rc = split_sub_table(&tw1024);
+    int rc = split_sub_table(&tw1024, c.st);
     if (!rc) rc = loop_resident(k, S::WG, S::LDS_BYTES, &resident);
     if (rc) return rc;
     const XcdLaunch l = xcd_take(ps, c.st, resident, (size_t)c.nblk * c.fb.nsig);
@@ -133,7 +146,8 @@ template <int PREF>
 static int fir32(Setup* ps, const float* d_Hc, const FirCall& c, DevBuf& hp_cache) {
     ps = for_device(ps);
     auto k = fastconv_fused32_kernel<PREF>;
-    int rc = fir_coef_table(hp_cache, fir32_coef_kernel, "fir32_coef_kernel", Fir32::WG, 4 * (size_t)Fir32::n, ps, d_Hc);
+    int rc = fir_coef_table(hp_cache, fir32_coef_kernel, "fir32_coef_kernel", "the fir32 coefficient table of this setup", Fir32::WG,
+                            4 * (size_t)Fir32::n, ps, d_Hc, c.st);
     if (rc) return rc;
     size_t resident = 0;
     if ((rc = loop_resident(k, Fir32::WG, Fir32::LDS_BYTES, &resident))) return rc;

@@ -36,6 +36,9 @@ struct FastConv : FirGeom {
     std::mutex mu;
     bool ready = false;     // set only after EVERY step of fc_ensure_device succeeded
     int device = -1;
+    // a launch of this setup was recorded into a HIP graph (on d_Hc_big / st_big: recorded_big): a replay reads the table addresses it froze, so
+    // from then on nothing of them is freed before pffastconv_destroy_setup - no move to another device, no other internal block length
+    bool recorded = false, recorded_big = false;
     // (device tables, work images and staging: DevBuf / PinnedBuf / StreamScratch of pf_devmem.h, freed with the setup)
     DevBuf d_Hf;
     DevBuf d_Hc;  // canonical-order filter spectrum * 1/Nfft for the fused kernel
@@ -224,6 +227,13 @@ static void fc_release_device(FastConv* s) {
 // The spectrum of `count` time-domain filter images of Nfft floats (:99-108) as the block kernels read it: upload -> forward transform
 // (the internal layout: kept in *keep_internal when asked) -> canonical order (pffft_zreorder) -> x scale, built on the null stream and
 // COMPLETE before the caller publishes it.  A failed build leaves both buffers empty; the caller's cached length / count stays zero.
+// A table that does not exist yet is built with hipMalloc, launches on the null stream and a synchronisation: never while the call's stream
+// records into a HIP graph.  Refused before anything is allocated or dropped; `what` names the missing table in the text.
+static int fc_refuse_capture(const char* what) {
+    return bad((std::string("pffastconv: ") + what + " of this setup would have to be built during graph capture: run a call of this shape "
+                "once before capturing").c_str(), hipErrorStreamCaptureUnsupported);
+}
+
 static int fc_spectrum(PFFFT_Setup* st, const float* host_images, int count, int Nfft, float scale, DevBuf& Hc, DevBuf* keep_internal) {
     const size_t bytes = sizeof(float) * (size_t)count * Nfft;
     DevBuf tmp;
@@ -248,14 +258,20 @@ static int fc_spectrum(PFFFT_Setup* st, const float* host_images, int count, int
 // A PFFASTCONV_Setup is used by one thread at a time (the reference's is "not shareable", include/pffft/pffastconv.h:77-80,142-143) and
 // holds the filter's tables on ONE device: the calling thread's current one.  Round 6: a call from another device no longer fails - the
 // tables are released and rebuilt there (the filter is kept on the host), i.e. the setup follows its user from device to device; a caller
-// that alternates between devices call by call should hold one setup per device.
-static int fc_ensure_device(FastConv* s) {
+// that alternates between devices call by call should hold one setup per device.  Once a HIP graph has recorded a launch of the setup it
+// stays where it is: a replay reads the tables at the addresses it froze.  `capturing`: the call's stream records right now.
+static int fc_ensure_device(FastConv* s, bool capturing) {
     int dev = -1;
     if (int rc = current_device_key(&dev)) return rc;
     if (s->ready) {
         if (dev == s->device) return 0;
+        if (s->recorded)
+            return bad("pffastconv: a captured graph reads the tables of this setup on the device of its first calls: they stay there until "
+                       "pffastconv_destroy_setup (one setup per device)", hipErrorInvalidDevice);
+        if (capturing) return fc_refuse_capture("the reference-block spectrum (on the calling thread's device)");
         fc_release_device(s);
     }
+    if (capturing) return fc_refuse_capture("the reference-block spectrum");
     // (a failed build: a later call, on whatever device, starts over instead of launching on half-built tables)
     if (int rc = fc_spectrum(s->st, s->h_filter_image.data(), 1, s->Nfft, s->scale, s->d_Hc, &s->d_Hf)) return rc;
     s->device = dev;
@@ -263,8 +279,12 @@ static int fc_ensure_device(FastConv* s) {
     return 0;
 }
 
-static int fc_ensure_big(FastConv* s, int Nfft_big) {
+static int fc_ensure_big(FastConv* s, int Nfft_big, bool capturing) {
     if (s->Nfft_big == Nfft_big) return 0;
+    if (capturing) return fc_refuse_capture("the big-block spectrum");
+    if (s->recorded_big)
+        return bad("pffastconv: a captured graph reads the big-block spectrum of this setup: a call that needs another internal block length "
+                   "would free it (use a second setup for such calls)", hipErrorInvalidValue);
     if (s->st_big) { pffft_destroy_setup(s->st_big); s->st_big = nullptr; }
     s->d_Hc_big.reset(); s->d_fir32_hp.reset(); s->Nfft_big = 0;
     s->st_big = pffft_new_setup(Nfft_big, PFFFT_REAL);
@@ -276,9 +296,10 @@ static int fc_ensure_big(FastConv* s, int Nfft_big) {
     return 0;
 }
 
-static int fc_ensure_part(FastConv* s) {
+static int fc_ensure_part(FastConv* s, bool capturing) {
     const int P = (s->filterLen + PART_B - 1) / PART_B;
     if (s->part_P == P && s->d_Hp) return 0;
+    if (capturing) return fc_refuse_capture("the partition spectra");
     const int Nfft = 2 * PART_B;
     if (!s->st_part) s->st_part = pffft_new_setup(Nfft, PFFFT_REAL);
     if (!s->st_part) { g_last_error = "pffastconv: internal setup failed"; return (int)hipErrorInvalidValue; }
@@ -292,12 +313,13 @@ static int fc_ensure_part(FastConv* s) {
 }
 
 // the table a route names, built on first use
-static int fc_ensure_table(FastConv* s, const FirRoute& r) {
+static int fc_ensure_table(FastConv* s, const FirRoute& r, bool capturing) {
     switch (r.table) {
-        case FT_BIG: return fc_ensure_big(s, r.block);
-        case FT_PART: return fc_ensure_part(s);
+        case FT_BIG: return fc_ensure_big(s, r.block, capturing);
+        case FT_PART: return fc_ensure_part(s, capturing);
         case FT_TD:
             if (s->d_td) return 0;
+            if (capturing) return fc_refuse_capture("the time-domain taps");
             if (int rc = s->d_td.grow(sizeof(float) * s->h_td.size())) return rc;
             PF_CHECK(hipMemcpy(s->d_td.get(), s->h_td.data(), sizeof(float) * s->h_td.size(), hipMemcpyHostToDevice));
             return 0;
@@ -383,10 +405,10 @@ static int fc_launch_td(FastConv* s, const FirCall& c, int stride) {
 // composed path: signal by signal on the same stream through one work image
 static int fc_launch_composed(FastConv* s, const FirCall& c) {
     const int Nfft = s->Nfft, nblk = c.nblk, mode = ((s->flags & PFFASTCONV_HIP_CPLX_INP_OUT) && s->cplxFactor == 1) ? 1 : 0;
-    StreamScratch::Entry& wk = s->work.acquire(c.st);
-    int rc = s->work.grow(wk, 0, sizeof(float) * (size_t)nblk * Nfft);
+    void* buf = nullptr;   // (never grown while the stream records: a replay runs on the pointer it froze; outgrown later, it is retired)
+    int rc = scratch_buffer(s->work, c.st, sizeof(float) * (size_t)nblk * Nfft, "pffastconv: the work image", &buf);
     if (rc) return rc;
-    float* const d_work = wk.buf[0].as<float>();
+    float* const d_work = (float*)buf;
     const unsigned grid = (unsigned)std::min<size_t>(((size_t)nblk * Nfft + 255) / 256, (size_t)num_cus() * 16);
     for (int sig = 0; sig < c.fb.nsig; ++sig) {
         const float* xs = c.x + (size_t)sig * c.fb.xstride;
@@ -405,32 +427,38 @@ static int fc_launch_composed(FastConv* s, const FirCall& c) {
 static int fc_apply_device(FastConv* s, const float* d_x, int cplxInputLen, float* d_y, int flush, hipStream_t st,
                            int* produced_out, const FcBatch& fb = FcBatch{1, 0, 0}) {
     std::lock_guard<std::mutex> lk(s->mu);
-    int rc = fc_ensure_device(s);
+    const bool capturing = stream_capturing(st);
+    int rc = fc_ensure_device(s, capturing);
     if (rc) return rc;
     const FirRoute r = fir_route(*s, cplxInputLen, fb.nsig, flush, num_cus(), ab(), env(), g_fir_wave_min, g_fir_wave_max);
     *produced_out = r.produced / s->cplxFactor;  // :200 / :261
     if (r.kind == FIR_NONE) return 0;
-    if ((rc = fc_ensure_table(s, r))) return rc;
+    if ((rc = fc_ensure_table(s, r, capturing))) return rc;
     const FirCall c{d_x, d_y, r.blocks, r.step, s->cplxFactor * cplxInputLen, r.last, st, fb};
     const bool big = r.table == FT_BIG;
     Setup* const ps = big ? s->st_big : s->st;
     const float* const Hc = (big ? s->d_Hc_big : s->d_Hc).as<float>();
-    switch (r.kind) {
-        case FIR_TD: return fc_launch_td(s, c, r.cfg);
-        // one wavefront per 2048-sample block, step = 2048 - taps + 1 (fft_fir.h fastconv_wave_kernel): filters up to 1024 taps
-        case FIR_WAVE: return fc_launch_waves(s, fastconv_wave_kernel<FirPartCfg::C1024, 3>, 1, c, 4, 0, c.step);
-        case FIR_FIR32: return launch_fir32(ps, Hc, c, big ? s->d_fir32_hp : s->d_fir32_hp_ref, r.cfg);
-        case FIR_SPLIT: return launch_fir_split(ps, Hc, c, r.cfg == 0);
-        case FIR_SPLIT1: return launch_fir_split1(ps, Hc, c, s->d_split1_ab);
-        case FIR_GATHER: return fc_launch_composed(s, c);
-        case FIR_FUSED: return FIR_FUSED_LAUNCH[r.cfg](ps, Hc, c);
+    auto launch = [&]() -> int {
+        switch (r.kind) {
+            case FIR_TD: return fc_launch_td(s, c, r.cfg);
+            // one wavefront per 2048-sample block, step = 2048 - taps + 1 (fft_fir.h fastconv_wave_kernel): filters up to 1024 taps
+            case FIR_WAVE: return fc_launch_waves(s, fastconv_wave_kernel<FirPartCfg::C1024, 3>, 1, c, 4, 0, c.step);
+            case FIR_FIR32: return launch_fir32(ps, Hc, c, big ? s->d_fir32_hp : s->d_fir32_hp_ref, r.cfg);
+            case FIR_SPLIT: return launch_fir_split(ps, Hc, c, r.cfg == 0);
+            case FIR_SPLIT1: return launch_fir_split1(ps, Hc, c, s->d_split1_ab);
+            case FIR_GATHER: return fc_launch_composed(s, c);
+            case FIR_FUSED: return FIR_FUSED_LAUNCH[r.cfg](ps, Hc, c);
 #ifdef PFFFT_HIP_VARIANTS
-        case FIR_DMA: return launch_fir_dma(ps, Hc, c);
-        case FIR_PART: return FIR_PART_LAUNCH[r.cfg - 1](s, c);
+            case FIR_DMA: return launch_fir_dma(ps, Hc, c);
+            case FIR_PART: return FIR_PART_LAUNCH[r.cfg - 1](s, c);
 #endif
-        default: break;
-    }
-    return bad("pffastconv: the route names a kernel this build does not have");
+            default: break;
+        }
+        return bad("pffastconv: the route names a kernel this build does not have");
+    };
+    rc = launch();
+    if (!rc && capturing) { s->recorded = true; s->recorded_big |= big; }   // (a refused call recorded nothing)
+    return rc;
 }
 
 }  // namespace pf

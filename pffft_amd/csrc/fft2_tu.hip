@@ -56,9 +56,9 @@ static Fft2Setup* fft2_new_setup(int rows, int cols, int is_double) {
 // ------------------------------------------------------------------------------------------------ the routes
 // The counters come from the rows' inner setup; the W_64 values from the table W_64^j of whichever inner setup has length 64.
 static int fft2_fused(Fft2Setup* z, const float* in, float* out, size_t batch, int dir, float scaling, hipStream_t st) {
-    if (int rc = inner_on_device(z->inner)) return rc;
+    if (int rc = inner_on_device(z->inner, st)) return rc;
     if (z->inner_rows != z->inner)
-        if (int rc = inner_on_device(z->inner_rows)) return rc;
+        if (int rc = inner_on_device(z->inner_rows, st)) return rc;
     Setup* s64 = z->cols == 64 ? z->inner : z->rows == 64 ? z->inner_rows : nullptr;
     const cx<float>* tw64 = s64 ? s64->d_tw.as<cx<float>>() : nullptr;
     const size_t image = (size_t)z->rows * z->cols * 2;
@@ -126,9 +126,9 @@ static bool fft2conv_fused_now(const Fft2Setup* z, int h_broadcast, const AbSel&
 }
 
 static int fft2conv_fused(Fft2Setup* z, const float* in, const float* H, float* out, float scaling, size_t batch, int conj_h, hipStream_t st) {
-    if (int rc = inner_on_device(z->inner)) return rc;
+    if (int rc = inner_on_device(z->inner, st)) return rc;
     if (z->inner_rows != z->inner)
-        if (int rc = inner_on_device(z->inner_rows)) return rc;
+        if (int rc = inner_on_device(z->inner_rows, st)) return rc;
     Setup* s64 = z->cols == 64 ? z->inner : z->rows == 64 ? z->inner_rows : nullptr;
     const cx<float>* tw64 = s64 ? s64->d_tw.as<cx<float>>() : nullptr;
     const cx<float>* G = reinterpret_cast<const cx<float>*>(H);

@@ -77,7 +77,7 @@ static int frames_transform_batch(Setup* s, const T* signal, size_t signal_strid
         return rc == ARGS_EMPTY ? 0 : rc;
 
     s = for_device(s);
-    if (int rc = ensure_device_any(s)) return rc;
+    if (int rc = ensure_device_any(s, st)) return rc;
     const AbSel sel = ab();
     if constexpr (sizeof(T) == 4) {
         FramesSel e;

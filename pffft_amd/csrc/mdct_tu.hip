@@ -134,7 +134,7 @@ static int mdct_composed_rows(MdctSetup* z, Setup* s, const T* in, size_t in_str
 template <typename T>
 static int mdct_open(MdctSetup* z, hipStream_t st, Setup** s, MdctTabs* tb) {
     *s = for_device(z->inner);
-    if (int rc = ensure_device_any(*s)) return rc;
+    if (int rc = ensure_device_any(*s, st)) return rc;
     const cx<T>*a = nullptr, *b = nullptr;
     if (int rc = mdct_tables<T>(z, *s, st, &a, &b)) return rc;
     tb->a = a; tb->b = b;

@@ -250,7 +250,7 @@ template <typename T, class Gather>
 static int synthesis_runs(Setup* s, const T* spectra, size_t spectra_stride, size_t nsignals, size_t nframes, size_t hop, size_t span,
                           size_t min_run, int ordered, T* signal, size_t signal_stride, hipStream_t st, Gather&& gather) {
     s = for_device(s);
-    int rc = ensure_device_any(s);
+    int rc = ensure_device_any(s, st);
     if (rc) return rc;
     const size_t row = s->vec_scalars, samples = (nframes - 1) * hop + span, batch = nsignals * nframes, cap = cap_rows(row * sizeof(T));
     std::lock_guard<std::mutex> lk(s->frames.mu);
@@ -387,9 +387,9 @@ struct InnerOwner {
 
 // `inner` with its tables on the calling thread's device, for a handle that serves one device: where for_device would answer with a
 // replica, the handle's own tables are on another device and the call is refused
-inline int inner_on_device(Setup* inner) {
+inline int inner_on_device(Setup* inner, hipStream_t st) {
     if (for_device(inner) != inner) return bad("this setup holds its tables on another device", hipErrorInvalidDevice);
-    return ensure_device_any(inner);
+    return ensure_device_any(inner, st);
 }
 
 // The PUBLIC entries on an inner setup of the scalar type T (they validate and resolve the device: transform_batch_any and its kin do not)

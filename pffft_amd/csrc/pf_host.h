@@ -220,10 +220,10 @@ int validate_layout(FILE* dbg);
 
 // ---- pffft_hip.hip: the lazy device state, the LDS-resident launchers, the batched transform.  transform_batch / ensure_device are
 // instantiated there for float and double; the *_any twins serve the composed units behind type-erased pointers.
-template <typename T> int ensure_device(Setup* s);
+template <typename T> int ensure_device(Setup* s, hipStream_t st);
 template <typename T> int transform_batch(Setup* s, const T* in, T* out, size_t batch, int dir, int ordered, hipStream_t st);
 int transform_batch_any(Setup* s, const void* in, void* out, size_t batch, int dir, int ordered, hipStream_t st);
-int ensure_device_any(Setup* s);
+int ensure_device_any(Setup* s, hipStream_t st);
 int shift_transform_batch(Setup* s, const float* in, float* out, size_t batch, int ordered, double rate, double phase_rad, hipStream_t st);
 // the measured table of the register-tiled kernels (fft_tiled.h): the one planner input that needs kernel addresses; false: no kernel for n
 bool tiled_pick_any(bool is_double, int n, int dir, int real, int ordered, TiledSel* e);

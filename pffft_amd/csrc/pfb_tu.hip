@@ -81,7 +81,7 @@ static int pfb_transform_batch(Setup* s, const T* signal, size_t signal_stride, 
         return rc == ARGS_EMPTY ? 0 : rc;
 
     s = for_device(s);
-    if (int rc = ensure_device_any(s)) return rc;
+    if (int rc = ensure_device_any(s, st)) return rc;
     const AbSel sel = ab();
     if constexpr (sizeof(T) == 4) {
         // (the kernel counts frames in 32 bits: longer batches of ONE signal go out in slices; several signals that long are composed)

@@ -67,12 +67,18 @@ unsigned* take_counters(Setup* s, hipStream_t st, unsigned pairs) {
     return ring + 2 * (s->ctr_slot.fetch_add(pairs) % CTR_RING);
 }
 
+// The lazy device state of `s`, built at its first call with hipMalloc / hipMemset / hipMemcpy - none of which may run while `st` records
+// into a HIP graph: such a first call is refused before anything is allocated (the stream is asked on this branch only: a setup whose
+// tables stand pays no query).
 template <typename T>
-int ensure_device(Setup* s) {
+int ensure_device(Setup* s, hipStream_t st) {
     std::lock_guard<std::mutex> lk(s->mu);
     if (s->dev_ready) return check_device(s);
     int rc = check_device(s);
     if (rc) return rc;
+    if (stream_capturing(st))
+        return bad("the tables of this setup would have to be built during graph capture: run the call once before capturing",
+                   hipErrorStreamCaptureUnsupported);
     if ((rc = alloc_counter_ring(s))) return rc;   // every kernel family may take the in-order path (zconvolve on K_BIG too)
     if (s->kernel == K_BIG) {
         for (int i = 0; i < 2; ++i) {
@@ -101,8 +107,8 @@ int ensure_device(Setup* s) {
     s->dev_ready = true;
     return 0;
 }
-template int ensure_device<float>(Setup*);
-template int ensure_device<double>(Setup*);
+template int ensure_device<float>(Setup*, hipStream_t);
+template int ensure_device<double>(Setup*, hipStream_t);
 
 // ------------------------------------------------------------------------------------------------
 // launchers
@@ -420,7 +426,7 @@ int transform_batch(Setup* s, const T* in, T* out, size_t batch, int dir, int or
     if ((dir != PFFFT_FORWARD && dir != PFFFT_BACKWARD)) { g_last_error = "pffft_hip: bad direction"; return (int)hipErrorInvalidValue; }
     if (batch == 0) return 0;
     s = for_device(s);        // the object that holds this setup's tables on the calling thread's device
-    int rc = ensure_device<T>(s);
+    int rc = ensure_device<T>(s, st);
     if (rc) return rc;
     const AbSel sel = ab();
     Route tmp;
@@ -463,7 +469,7 @@ int transform_batch_any(Setup* s, const void* in, void* out, size_t batch, int d
     if (s->is_double) return transform_batch<double>(s, (const double*)in, (double*)out, batch, dir, ordered, st);
     return transform_batch<float>(s, (const float*)in, (float*)out, batch, dir, ordered, st);
 }
-int ensure_device_any(Setup* s) { return s->is_double ? ensure_device<double>(s) : ensure_device<float>(s); }
+int ensure_device_any(Setup* s, hipStream_t st) { return s->is_double ? ensure_device<double>(s, st) : ensure_device<float>(s, st); }
 
 // frequency shift (src/pf_mixer.cpp) immediately followed by the forward FFT, the usual SDR
 // chain.  The batch is ONE stream of batch*N complex samples, sample g gets exp(j (phase_rad + 2 pi rate g)).
@@ -477,7 +483,7 @@ int shift_transform_batch(Setup* s, const float* in, float* out, size_t batch, i
     }
     if (batch == 0) return 0;
     s = for_device(s);
-    int rc = ensure_device<float>(s);
+    int rc = ensure_device<float>(s, st);
     if (rc) return rc;
     const double phase_turns = phase_rad / pfmix::MIX_TWO_PI;
     if (s->kernel == K_C1024_F32 && !ab().is(AB_AUX_DIRECT) && batch < (1ull << 32))   // AB_AUX_DIRECT: the two-pass composition (second route of the tests)

@@ -322,9 +322,15 @@ int setup_devices(Setup* s, int* out, int max) {
     if (!s || s->magic != MAGIC) return 0;
     std::lock_guard<std::mutex> lk(s->mu);
     int n = 0;
+    // (a bound object whose tables were never built - its first call was refused, e.g. during a stream capture - holds nothing there)
     const int bound = s->device.load();
-    if (bound >= 0) { if (out && n < max) out[n] = bound; ++n; }
-    for (auto& kv : s->replicas) { if (out && n < max) out[n] = kv.first; ++n; }
+    if (bound >= 0 && s->dev_ready) { if (out && n < max) out[n] = bound; ++n; }
+    for (auto& kv : s->replicas) {
+        std::lock_guard<std::mutex> lr(kv.second->mu);
+        if (!kv.second->dev_ready) continue;
+        if (out && n < max) out[n] = kv.first;
+        ++n;
+    }
     return n;
 }
 

@@ -57,7 +57,7 @@ static int psd_batch(Setup* s, const T* signal, size_t signal_stride, size_t nsi
     const size_t spp = a.spp, row = a.row, P = a.out_row, hop_s = a.hop_s;
     const size_t G = nframes / navg, V = nsignals * G;     // V output rows; row v = i G + g
     s = for_device(s);
-    if ((rc = ensure_device_any(s))) return rc;
+    if ((rc = ensure_device_any(s, st))) return rc;
     PsdSel e;
     bool fused = false;
     if constexpr (sizeof(T) == 4)

@@ -79,8 +79,8 @@ static int resample_fused_launch(ResampleSetup* z, const float* in, float* out, 
 template <int REAL>
 static int resample_fused(ResampleSetup* z, const float* in, float* out, size_t batch, float s, hipStream_t st) {
     const size_t spp = REAL ? 1 : 2;
-    if (int rc = inner_on_device(z->inner)) return rc;
-    if (int rc = inner_on_device(z->inner_m)) return rc;
+    if (int rc = inner_on_device(z->inner, st)) return rc;
+    if (int rc = inner_on_device(z->inner_m, st)) return rc;
     return for_slices(batch, [&](size_t b0, size_t nb) {
         const float* src = in + b0 * (size_t)z->N * spp;
         float* dst = out + b0 * (size_t)z->M * spp;

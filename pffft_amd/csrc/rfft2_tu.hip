@@ -64,9 +64,9 @@ static Rfft2Setup* rfft2_new_setup(int rows, int cols, int is_double) {
 // ------------------------------------------------------------------------------------------------ the routes
 // The counters come from the columns' inner setup; the W_64 values from the table W_64^j of whichever complex setup has length 64.
 static int rfft2_fused(Rfft2Setup* z, const float* in, float* out, size_t batch, int dir, float scaling, hipStream_t st) {
-    if (int rc = inner_on_device(z->inner_rows)) return rc;
+    if (int rc = inner_on_device(z->inner_rows, st)) return rc;
     if (z->inner64)
-        if (int rc = inner_on_device(z->inner64)) return rc;
+        if (int rc = inner_on_device(z->inner64, st)) return rc;
     Setup* s64 = z->rows == 64 ? z->inner_rows : z->inner64;
     const cx<float>* tw64 = s64 ? s64->d_tw.as<cx<float>>() : nullptr;
     const size_t real_image = (size_t)z->rows * z->cols, spec_image = (size_t)z->rows * (z->cols / 2 + 1) * 2;
@@ -149,9 +149,9 @@ static bool rfft2conv_fused_now(const Rfft2Setup* z, int h_broadcast, const AbSe
 }
 
 static int rfft2conv_fused(Rfft2Setup* z, const float* in, const float* H, float* out, float scaling, size_t batch, int conj_h, hipStream_t st) {
-    if (int rc = inner_on_device(z->inner_rows)) return rc;
+    if (int rc = inner_on_device(z->inner_rows, st)) return rc;
     if (z->inner64)
-        if (int rc = inner_on_device(z->inner64)) return rc;
+        if (int rc = inner_on_device(z->inner64, st)) return rc;
     Setup* s64 = z->rows == 64 ? z->inner_rows : z->inner64;
     const cx<float>* tw64 = s64 ? s64->d_tw.as<cx<float>>() : nullptr;
     const cx<float>* G = reinterpret_cast<const cx<float>*>(H);

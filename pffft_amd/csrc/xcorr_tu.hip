@@ -63,7 +63,7 @@ static int xcorr_fused_launch(Setup* s, const XcorrIO<C, REAL>& io, size_t batch
 template <int REAL, int AUTO>
 static int xcorr_fused(XcorrSetup* z, const float* x, const float* y, float* out, size_t batch, int weight, float s, hipStream_t st) {
     const size_t spp = REAL ? 1 : 2;
-    return bluestein_fused(z->inner, z->N, batch, [&](auto tag, size_t b0, size_t nb) {
+    return bluestein_fused(z->inner, z->N, batch, st, [&](auto tag, size_t b0, size_t nb) {
         typedef typename decltype(tag)::type C;
         const XcorrIO<C, REAL> io{x + b0 * (size_t)z->len_x * spp, y + b0 * (size_t)z->len_y * spp, out + b0 * (size_t)z->nlags * spp,
                                   (unsigned)z->len_x, (unsigned)z->len_y, z->m0, (unsigned)z->nlags, s};

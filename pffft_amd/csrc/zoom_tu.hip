@@ -198,7 +198,7 @@ static int zoom_ensure(ZoomSetup* z, hipStream_t st) {
 
 // ------------------------------------------------------------------------------------------------ the two routes (bluestein_host.h)
 static int zoom_fused(ZoomSetup* z, const float* in, float* out, size_t batch, int cj, hipStream_t st) {
-    return bluestein_fused(z->inner, z->M, batch, [&](auto tag, size_t b0, size_t nb) {
+    return bluestein_fused(z->inner, z->M, batch, st, [&](auto tag, size_t b0, size_t nb) {
         typedef typename decltype(tag)::type C;
         const ZoomIO<C, ZoomHold<C>::value> io{in + b0 * 2 * (size_t)z->N, out + b0 * 2 * (size_t)z->K, z->d_a.as<cx<float>>(),
                                                z->d_c.as<cx<float>>(), (unsigned)z->N, (unsigned)z->K, cj};
